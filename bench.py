@@ -9,6 +9,12 @@ matrices are resident in HBM before the timed region.  `value` = reference flop 
 (tfqmrgpu_bsrsv_getInfo, the number the reference's own `bench_tfqmrgpu tfQMR` divides by its solver
 time, bench_tfqmrgpu.cu:200-204) / wall time, summed over all GPUs.
 
+A plain run does what that figure needs: set-up, --warmup solves, --steps timed solves, one JSON line (`value`,
+`ms_per_step`, iterations, residual, the configuration).  --full adds everything that takes runs or instrumentation of its
+own: HIP events on the fused multiplies inside the timed region and one further profiled solve behind it (`kernels`,
+`roofline*`), the stand-alone multiplies, the re-solve, the mixed-precision solve, the collectives and the CPU baseline.
+--dump-outputs DIR writes what the last timed solve handed back (dump_outputs); the inputs depend on the arguments alone.
+
 --gpus N, one process per GPU: weak scaling by default, every rank owns its own 49 block columns of a N*49-column
 system (same A, same sparsity, own shadow vector); `--workload cfg4` is BASELINE config 4, strong scaling: the 256
 block columns of one 16x16 complex<double> system split N ways with the product's tfqmrgpuExt_shardColumns.  The only
@@ -163,6 +169,24 @@ def cpu_baseline(pr, prec, threads):
     return out
 
 
+def dump_outputs(directory, s, pr, prec, st, info, rank, world):
+    """What a caller of the timed path receives from its last solve: X (getMatrix('X'): [block, row, column, re | im] in float64
+    for z, float32 for c) and status, iterations, residual, flops (getInfo).  X is sampled when it is larger than 32 MB / world:
+    a fixed, seeded choice of its blocks, whose indices are written beside it.  Rank r > 0 of several writes rank<r>_*.npy."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    name = lambda n: os.path.join(directory, ("rank%d_" % rank if rank else "") + n + ".npy")
+    real = torch.float64 if prec == "z" else torch.float32
+    dX = torch.empty((pr.nnzbX, pr.LM, pr.LN, 2), dtype=real, device="cuda")
+    s.get_matrix_device(dX.data_ptr())
+    n = min(pr.nnzbX, (32 << 20) // world // (dX[0].numel() * dX.element_size()))
+    blocks = np.arange(pr.nnzbX) if n == pr.nnzbX else np.sort(np.random.default_rng(0).choice(pr.nnzbX, n, replace=False))
+    X = dX[torch.from_numpy(blocks).cuda()].cpu().numpy()
+    np.save(name("X"), X)
+    np.save(name("X_blocks"), blocks.astype(np.float64))
+    np.save(name("solve_info"), np.array([st, info["iterations"], info["residual"], info["flops"]], dtype=np.float64))
+
+
 def launch_ranks(n, argv):
     """python bench.py --gpus N without a launcher: start N ranks as children of THIS process, which has not touched the GPU
     (nothing imported torch yet), relay the output, exit with the launcher's code"""
@@ -185,6 +209,9 @@ def main():
     ap.add_argument("--no-mixed", action="store_true", help="skip the mixed-precision solve of the same system")
     ap.add_argument("--no-collectives", action="store_true", help="skip pricing the stopping test's collectives on one rank (RCCL communicator / host callback)")
     ap.add_argument("--launcher", action="store_true", help="go through torch.distributed.run even for one rank")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel events and rooflines, stand-alone multiplies, "
+                    "re-solve, mixed precision, collectives, CPU baseline (the --no-* and --multiply-reps options apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write X and the solve info of the last timed solve as DIR/*.npy")
     args = ap.parse_args()
 
     if "RANK" not in os.environ and (args.gpus > 1 or args.launcher):
@@ -268,8 +295,9 @@ def main():
 
         # HIP events on the solver's stream inside the timed region bracket the two fused multiplies (the roofline kernels);
         # events around all eleven kernel classes would cost the solve 1.7 % (176 events per 16 iterations,
-        # scripts/prof_overhead.py): the full breakdown comes from one further solve behind the timed region
-        s.set_profiling(2)
+        # scripts/prof_overhead.py): the full breakdown comes from one further solve behind the timed region (--full only)
+        if args.full:
+            s.set_profiling(2)
         prof = {}
         flops = iters = 0
         barrier()
@@ -279,18 +307,22 @@ def main():
             info = s.get_info()
             flops += info["flops"]
             iters += info["iterations"]
-            add_profile(prof)
+            if args.full:
+                add_profile(prof)
         barrier()
         elapsed = time.perf_counter() - t0
-        s.set_profiling(1)
-        prof_all = {}
-        s.solve(pr.tolerance, args.max_iterations)      # (every rank: the solve holds the ranks' stopping-test all-reduces)
-        add_profile(prof_all)
-        barrier()
-        s.set_profiling(0)
-        for k in ("spmm_v4_dot", "spmm_v5_nrm_dot"):
-            prof_all[k] = prof[k]
-        prof = prof_all
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, s, pr, prec, st, info, rank, world)
+        if args.full:
+            s.set_profiling(1)
+            prof_all = {}
+            s.solve(pr.tolerance, args.max_iterations)      # (every rank: the solve holds the ranks' stopping-test all-reduces)
+            add_profile(prof_all)
+            barrier()
+            s.set_profiling(0)
+            for k in ("spmm_v4_dot", "spmm_v5_nrm_dot"):
+                prof_all[k] = prof[k]
+            prof = prof_all
         if distributed:
             red = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
             dist.all_reduce(red, op=dist.ReduceOp.MAX)
@@ -304,6 +336,25 @@ def main():
         out = None
         if rank == 0:
             nPairs = view["nPairs"]
+            S = pr.nnzbX * 2 * pr.LM * pr.LN * (8 if prec == "z" else 4)
+            out = {
+                "metric": "tfQMR solve throughput to 1e-9 residual (reference flop count / solve time); iterations/s and BSR multiply GB/s + TFLOP/s in extra keys",
+                "value": round(flops / elapsed / 1e12, 4), "unit": "TFLOP/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+                "higher_is_better": True, "scaling": "strong" if args.workload.startswith("cfg4") else "weak", "vs_baseline": None,
+                "dtype": "f64" if prec == "z" else "f32", "data": "synthetic",
+                "config": {"workload": desc, "name": args.workload, "mb": pr.mb, "nnzbA": pr.nnzbA, "nnzbX_per_gpu": pr.nnzbX,
+                           "block_columns_per_gpu": view["nCols"], "rhs_per_gpu": view["nCols"] * pr.LN, "pairs": nPairs,
+                           "threshold": pr.tolerance, "sharding": "block columns of X/B per GPU, max-all-reduce of the stopping test",
+                           "reduce_path": reduce_path if distributed else "none (one rank)"},
+                "iterations_per_solve": iters / args.steps,
+                "iterations_per_second": round(iters_all / world / elapsed, 2),
+                "rhs_iterations_per_second": round(iters_all * view["nCols"] * pr.LN / elapsed, 1),
+                "solve_status": int(st), "residual": info["residual"],
+                "buffer_GB_per_gpu": round(nbytes / 1e9, 3), "vector_MB": round(S / 1e6, 1),
+            }
+        if rank == 0 and args.full:
             nA_ref = len(np.unique(view["pairs"][0::2]))
             model = kernel_model(pr, prec, nPairs, nA_ref, hash_in_registers=hash_shapes(prec, pr.LM, pr.LN))
             # avg_ms: launches that did work in steady iterations; avg_ms_all_launches also counts the launches that were enqueued ahead
@@ -539,25 +590,9 @@ def main():
                 collectives["note"] = ("one rank: what the reductions of the multi-GPU protocol add to this rank's own solve (launches, the vote, no fold of small plans); "
                                        "the wire time of N > 1 ranks comes on top")
 
-            S = pr.nnzbX * 2 * pr.LM * pr.LN * (8 if prec == "z" else 4)
             it_bytes = sum(model[k][0] for k in ("xpay_v6", "spmm_v4_dot", "v5_nrm", "x_v6_v7", "spmm_v5_nrm_dot"))
             it_ms = sum(v["avg_ms"] for k, v in per_kernel.items() if k != "probe")       # every class runs once per (steady) iteration
-            out = {
-                "metric": "tfQMR solve throughput to 1e-9 residual (reference flop count / solve time); iterations/s and BSR multiply GB/s + TFLOP/s in extra keys",
-                "value": round(flops / elapsed / 1e12, 4), "unit": "TFLOP/s",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-                "higher_is_better": True, "scaling": "strong" if args.workload.startswith("cfg4") else "weak", "vs_baseline": None,
-                "dtype": "f64" if prec == "z" else "f32", "data": "synthetic",
-                "config": {"workload": desc, "name": args.workload, "mb": pr.mb, "nnzbA": pr.nnzbA, "nnzbX_per_gpu": pr.nnzbX,
-                           "block_columns_per_gpu": view["nCols"], "rhs_per_gpu": view["nCols"] * pr.LN, "pairs": nPairs,
-                           "threshold": pr.tolerance, "sharding": "block columns of X/B per GPU, max-all-reduce of the stopping test",
-                           "reduce_path": reduce_path if distributed else "none (one rank)"},
-                "iterations_per_solve": iters / args.steps,
-                "iterations_per_second": round(iters_all / world / elapsed, 2),
-                "rhs_iterations_per_second": round(iters_all * view["nCols"] * pr.LN / elapsed, 1),
-                "solve_status": int(st), "residual": info["residual"],
-                "buffer_GB_per_gpu": round(nbytes / 1e9, 3), "vector_MB": round(S / 1e6, 1),
+            out.update({
                 "roofline": rl,
                 "roofline_dominant": rl_dominant,
                 "roofline_kernels": rl_all,
@@ -576,7 +611,7 @@ def main():
                 "kernels_source": "spmm_v4_dot, spmm_v5_nrm_dot: HIP events inside the timed region (all %d solves); other classes: one further solve behind it; "
                                   "avg_ms = launches of steady iterations (the first iteration of a solve does not read the vectors that are zero there: "
                                   "avg_ms_first_iteration, fewer bytes)" % args.steps,
-            }
+            })
             if world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(pr, prec, min(16, os.cpu_count() or 1))
         s.close()

@@ -68,6 +68,43 @@ def record(ref, name, pr, solves, keep_x=True):
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
 
 
+def record_reference_pins(ref):
+    """reference_pins.npz: what the tests that compare with the reference library directly read from it -- the stencil system of
+    tests/test_oracle_pins.py::test_against_live_reference (index lists, z and c solves), the createPlan status and index lists of
+    the 120 random patterns of tests/test_abi.py::test_create_plan_random_patterns_bit_exact, and the createPlan status of
+    65 536 block rows (test_block_rows_beyond_the_reference_s_int_overflow)"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from test_abi import _random_pattern_problem
+    keys = ("pairs", "starts", "subset", "colindx", "original_bsrColIndX")
+    out = {}
+    pr = PR.stencil_2d(5, 5, 4, 8, 3, seed=77, radius=2.0)
+    an = ref.analyse(pr)
+    for k in keys:
+        out["stencil_plan_" + k] = an[k]
+    for prec, tol in (("z", 1e-9), ("c", 1e-4)):
+        st, X, info = ref.solve_staged(pr, prec, threshold=tol, max_iterations=200)
+        tag = "stencil_solve_%s_" % prec
+        out[tag + "status"] = np.int64(st)
+        out[tag + "iterations"] = np.int64(info["iterations"])
+        out[tag + "flops"] = np.float64(info["flops"])
+        out[tag + "X"] = X.astype(np.complex128 if prec == "z" else np.complex64)
+    rng = np.random.default_rng(20260)
+    status = []
+    for case in range(120):
+        r = ref.analyse(_random_pattern_problem(rng))
+        status.append(T.decode(r["status"])[0])
+        if r["status"] == 0:
+            for k in keys:
+                out["random_%d_%s" % (case, k)] = r[k]
+    out["random_status_code"] = np.array(status, dtype=np.int64)
+    mb = 65536
+    rp = np.arange(mb + 1, dtype=np.int32)
+    big = T.Problem(rp, np.arange(mb, dtype=np.int32), np.broadcast_to(np.eye(4), (mb, 4, 4)), rp, np.zeros(mb, np.int32),
+                    np.minimum(rp, 1).astype(np.int32), [0], np.eye(4)[None], None, 1e-9)
+    out["rows_65536_status"] = np.array(T.decode(ref.create_plan(big)[0])[:2], dtype=np.int64)
+    np.savez_compressed(os.path.join(HERE, "reference_pins.npz"), **out)
+
+
 def main():
     if not O.have_ref():
         sys.exit("oracle/_ref is missing: run `make -C oracle ref` where /root/reference exists")
@@ -85,6 +122,7 @@ def main():
     record(ref, "dense_random_rect", PR.dense_random(mb=4, LM=4, LN=8, ncols=3, seed=21), [("z", 1e-10, 500)])
     record(ref, "stencil_8x8", PR.stencil_2d(6, 5, 8, 8, 3, seed=3, radius=2.5), [("z", 1e-9, 300), ("c", 1e-4, 300)])
     record(ref, "stencil_8x32", PR.stencil_2d(5, 4, 8, 32, 2, seed=4), [("z", 1e-9, 300)])
+    record_reference_pins(ref)
 
 
 if __name__ == "__main__":

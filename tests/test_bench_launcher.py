@@ -22,7 +22,7 @@ def _run(args):
     return json.loads(lines[0])
 
 
-SMALL = ["--workload", "fd2d_16x16_z_small", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-hbm-multiply", "--multiply-reps", "2"]
+SMALL = ["--full", "--workload", "fd2d_16x16_z_small", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-hbm-multiply", "--multiply-reps", "2"]
 
 
 def test_one_rank_through_the_launcher_equals_the_plain_run():
@@ -35,6 +35,21 @@ def test_one_rank_through_the_launcher_equals_the_plain_run():
     for k in ("roofline", "roofline_multiply", "roofline_iteration", "kernels"):
         assert k in launched
     assert launched["roofline"]["kernel"] in ("spmm_v4_dot", "spmm_v5_nrm_dot") and 0 < launched["roofline"]["frac"] < 1
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_solve(tmp_path):
+    """without --full: the headline keys only, --steps timed solves, and --dump-outputs writes X of the last timed solve (all of it
+    at this size) and its getInfo figures as float .npy files"""
+    import numpy as np
+    line = _run(["--gpus", "1", "--workload", "fd2d_16x16_z_small", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["dtype"] == "f64" and line["solve_status"] == 0
+    assert not any(k.startswith("roofline") or k in ("kernels", "cpu_baseline", "mixed_precision") for k in line)
+    X, blocks, info = (np.load(str(tmp_path / (n + ".npy"))) for n in ("X", "X_blocks", "solve_info"))
+    assert X.dtype == np.float64 and X.shape == (line["config"]["nnzbX_per_gpu"], 16, 16, 2) and np.isfinite(X).all()
+    assert np.array_equal(blocks, np.arange(X.shape[0])) and np.abs(X).max() > 0
+    assert info[0] == line["solve_status"] and info[1] == line["iterations_per_solve"] and info[2] == line["residual"]
 
 
 def test_two_ranks_when_two_gpus_are_visible():
