@@ -1,5 +1,5 @@
 """The DEFAULT shadow vector (counter-based hash) is what bench.py times: for 16 x 16 blocks the fused multiply kernels
-do not even read it, they recompute it in registers (k_spmm_mfma<..., HASH = true>, tfq_spmm.hip).  These tests pin
+do not even read it, they recompute it in registers (k_spmm_mfma<..., HASH = true>, tfq_spmm_mfma.hip).  These tests pin
 that variant to the CPU oracle the same way the glibc-mode tests pin the other one: the oracle is fed with the very
 same vector (numpy restatement of tfq_device.hpp: shadow_key / shadow_value) and must take the same iterations
 with the same bound history (reference algorithm: tfqmrgpu_core.hxx:189-304).  Needs an MI355X (`pytest -m gpu`)."""
@@ -156,8 +156,7 @@ SWITCHES = [dict(TFQMRGPU_3M=1), dict(TFQMRGPU_3M=2), dict(TFQMRGPU_EPI_PREFETCH
             dict(TFQMRGPU_ILV=0),     # ILV=0: 16 x 16 and 8 x 8 z plans keep the native element order (k_spmm_mfma / k_spmm_mfma8)
             dict(TFQMRGPU_A_STREAM=0), dict(TFQMRGPU_CLAMP=0),
             dict(TFQMRGPU_FOLD_MAX=0),   # the column operations as launches of their own (plans of at most 384 chunks fold them into the producers' tails)
-            dict(TFQMRGPU_FOLD_MAX=100000),
-            dict(TFQMRGPU_ILV16_LDS_KIB=60)]   # the occupancy probe of k_spmm_ilv16: unused dynamic LDS, two work groups per CU   # ... and folded where the product does not (the first fixture below has 256 chunks)
+            dict(TFQMRGPU_FOLD_MAX=100000)]   # ... and folded where the product does not (the first fixture below has 256 chunks)
 
 
 @pytest.mark.parametrize("name,prec,tol", [("stencil:16:16:16:16:4:7:5", "z", 1e-9), ("stencil:8:8:32:32:2:3:13", "z", 1e-9),
@@ -175,7 +174,7 @@ def test_tuning_switches_change_code_paths_not_results(tmp_path, name, prec, tol
         assert int(got["status"]) == 0 and int(got["iterations"]) == int(base["iterations"]), sw
         assert np.allclose(got["history"], base["history"], rtol=1e-6, atol=0), sw
         assert np.abs(got["X"] - base["X"]).max() <= 1e-9 * np.abs(base["X"]).max(), sw
-        if "TFQMRGPU_DEPTH" in sw or "TFQMRGPU_ORDER" in sw or "TFQMRGPU_ORDER_G" in sw or "TFQMRGPU_A_STREAM" in sw or "TFQMRGPU_FOLD_MAX" in sw or "TFQMRGPU_ILV16_LDS_KIB" in sw:
+        if "TFQMRGPU_DEPTH" in sw or "TFQMRGPU_ORDER" in sw or "TFQMRGPU_ORDER_G" in sw or "TFQMRGPU_A_STREAM" in sw or "TFQMRGPU_FOLD_MAX" in sw:
             assert np.array_equal(got["X"], base["X"]), sw   # these change WHEN things run, never what is added to what
 
 

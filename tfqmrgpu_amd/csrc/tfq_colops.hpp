@@ -86,7 +86,7 @@ __device__ inline bool fold_arrive(uint32_t* counter, uint32_t expected, int* la
 // ---- columns of many chunks: several work groups per column (r04) ------------------------------------------------------------
 // One work group per block column is 2-49 work groups on a 256-CU part: a column of BASELINE config 3, 4 or 5 has 4096 chunk records, and
 // k_dec35 / k_dec34 / k_decT took 17-35 us each there -- 9 % of config 3's iteration, 4 % of config 4's and 5's -- in a kernel that is nothing
-// but a few round trips to memory per lane group.  Long columns (col_segments below) are summed by S work groups:
+// but a few round trips to memory per lane group.  Long columns (col_segments, tfq_plan.hpp) are summed by S work groups:
 // work group `seg` sums its share of the records (contiguous, balanced: the same lane-group order as column_sum inside the share), leaves it
 // in DevPlan::colPart, and the LAST one to arrive (the column's arrival counter, fold_arrive) adds the S shares IN ORDER and runs the
 // column's update.  The order of every sum is fixed by (n, LN) alone: results do not depend on which work group is last, nor on the
@@ -95,9 +95,7 @@ __device__ inline bool fold_arrive(uint32_t* counter, uint32_t expected, int* la
 // A segment is what one work group sums in ONE round of loads (256 / LN lane groups x 16 records in flight: 256 records for LN = 16, 128 for 32); columns
 // of at most four such rounds stay with one work group -- the arrival costs a few microseconds (P2's columns of 705 records, three rounds: 11 us per
 // column kernel either way), BASELINE config 3's, 4's and 5's columns of 1024-4096 records are cut (17-37 -> 10-17 us, profiles/r04_vector_kernels.txt).
-__host__ __device__ inline uint32_t col_seg_len(int LN) { return uint32_t(256 / LN) * 16u; }
-__host__ __device__ inline uint32_t col_segments(uint32_t n, int LN) { return (n <= 4 * col_seg_len(LN)) ? 1u : (n + col_seg_len(LN) - 1) / col_seg_len(LN); }
-constexpr uint32_t kColSlot = 64;      // granule of the slot numbering below (<= the shortest segment: LN = 64)
+// (col_seg_len, col_segments, kColSlot: tfq_plan.hpp, where the plan sizes DevPlan::colPart by the same rule)
 // the slot of (column, segment) in colPart: c0 / K + col + seg is unique for any K <= the segment length (floor(c1 / K) + 1 >= floor(c0 / K) + ceil(n / K) >= segments)
 __device__ inline size_t col_part_slot(uint32_t c0, uint32_t col, uint32_t seg) { return size_t(c0 / kColSlot) + col + seg; }
 

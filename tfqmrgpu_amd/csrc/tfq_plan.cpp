@@ -286,7 +286,7 @@ tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
         target = std::min<size_t>(std::max<size_t>(target, 8 * 1024), maxKiB * 1024);
         uint32_t CH = uint32_t(std::max<size_t>(1, target / blockBytes));
         // every wave of a work group wants a unit of work: the MFMA multiply cuts a block into strips of 16 or
-        // 32 rows (RowTiles in tfq_spmm.hip), one strip per wave and pass
+        // 32 rows (RowTiles in tfq_spmm_mfma.hip), one strip per wave and pass
         if (LM % 16 == 0 && LN % 16 == 0) {
             int const mt = LM / 16, ms = (mt % 2 == 0 && 2 * (LN / 16) * p.realBytes <= 32) ? 2 : 1;
             uint32_t const perBlock = uint32_t(mt / ms);
@@ -376,15 +376,11 @@ tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
     take(p.wPz, nChunks * 2 * LN * sizeof(double));
     take(p.wPd, nChunks * LN * sizeof(double));
     take(p.wColRec, size_t(p.nCols) * 2 * sizeof(double)); // per-column stopping-test record
-    {   // long columns are summed by several work groups (tfq_colops.hpp: col_segments, column_total; the same two formulas)
-        uint32_t const segLen = uint32_t(256 / LN) * 16u;
+    {   // long columns are summed by several work groups (tfq_colops.hpp: column_total)
         p.colSegMax = 1;
-        for (uint32_t jb = 0; jb < p.nCols; ++jb) {
-            uint32_t const n = p.chunks.colPtr[jb + 1] - p.chunks.colPtr[jb];
-            p.colSegMax = std::max(p.colSegMax, (n <= 4 * segLen) ? 1u : (n + segLen - 1) / segLen);
-        }
-        uint32_t const K = 64;             // kColSlot
-        take(p.wColPart, (nChunks / K + p.nCols + 2) * 3 * size_t(LN) * sizeof(double));
+        for (uint32_t jb = 0; jb < p.nCols; ++jb)
+            p.colSegMax = std::max(p.colSegMax, col_segments(p.chunks.colPtr[jb + 1] - p.chunks.colPtr[jb], LN));
+        take(p.wColPart, (nChunks / kColSlot + p.nCols + 2) * 3 * size_t(LN) * sizeof(double));
     }
     take(p.wChunkFirst, (nChunks + 1) * sizeof(uint32_t));
     take(p.wChunkCol, nChunks * sizeof(uint32_t));

@@ -19,6 +19,13 @@ inline tfqmrgpuStatus_t err(int code, int line = 0, int key = 0) {
 
 inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
+// Long block columns are summed by several work groups (tfq_colops.hpp: column_total).  A segment is what one work group sums in ONE
+// round of loads (256 / LN lane groups x 16 records in flight); columns of at most four segments stay with one work group.  The plan sizes
+// DevPlan::colPart by the same rule: a column with more segments than the plan counted would never see its last arrival.
+constexpr uint32_t col_seg_len(int LN) { return uint32_t(256 / LN) * 16u; }
+constexpr uint32_t col_segments(uint32_t n, int LN) { return (n <= 4 * col_seg_len(LN)) ? 1u : (n + col_seg_len(LN) - 1) / col_seg_len(LN); }
+constexpr uint32_t kColSlot = 64;      // granule of the slot numbering of colPart (tfq_colops.hpp: col_part_slot; <= the shortest segment: LN = 64)
+
 struct Window { size_t offset = 0, bytes = 0; };
 
 // one unit of work of the vector kernels: a run of blocks inside ONE block column

@@ -6,7 +6,7 @@
 #include <cstdlib>
 
 namespace tfq {
-// block columns multiplied together at most (tfq_plan.cpp: Plan::colBatch, tfq_spmm.hip: k_spmm_ilv8b; with 4 hipcc does not fit the registers of
+// block columns multiplied together at most (tfq_plan.cpp: Plan::colBatch, tfq_spmm_ilv8.hip: k_spmm_ilv8b; with 4 hipcc does not fit the registers of
 // three waves per SIMD without scratch)
 constexpr int kColBatchMax = 2;
 // plans of at most this many chunks fold their column operations into the producers' tails (tfq_colops.hpp; r01-r03: 128 with fenced arrivals; r04: the

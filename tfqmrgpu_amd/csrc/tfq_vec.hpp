@@ -1,4 +1,4 @@
-// internal launch interface of the vector / column kernels (tfq_vec.hip) and the multiply (tfq_spmm.hip)
+// internal launch interface of the vector / column kernels (tfq_vec.hip) and the multiply (tfq_spmm.hip, tfq_spmm.hpp)
 #pragma once
 #include "tfq_device.hpp"
 
