@@ -15,9 +15,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 def problem(name):
     from tfqmrgpu_amd import problems as PR
-    if name.startswith("stencil:"):    # stencil:nx:ny:LM:LN:ncols:seed:points
-        _, nx, ny, lm, ln, nc, seed, points = name.split(":")
-        return PR.stencil_2d(int(nx), int(ny), int(lm), int(ln), int(nc), seed=int(seed), points=int(points))
+    if name.startswith("stencil:"):    # stencil:nx:ny:LM:LN:ncols:seed:points[:radius of each column, "-" = dense]
+        f = name.split(":")
+        _, nx, ny, lm, ln, nc, seed, points = f[:8]
+        radius = [None if r == "-" else float(r) for r in f[8].split(",")] if len(f) > 8 else None
+        return PR.stencil_2d(int(nx), int(ny), int(lm), int(ln), int(nc), seed=int(seed), points=int(points), radius=radius)
     from conftest import load_problem
     return load_problem(name)
 

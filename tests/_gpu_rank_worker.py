@@ -21,8 +21,8 @@ def main():
     assert torch.cuda.is_available(), "no GPU: the product has no CPU fallback"
     torch.cuda.set_device(0)
     import tfqmrgpu_amd as T
-    from conftest import load_problem
-    pr = load_problem(name)
+    from _env_worker import problem      # a golden fixture or a `stencil:` spec
+    pr = problem(name)
     sub, xb, bb = T.shard_columns(pr, world, rank)
     calls = [0]
 

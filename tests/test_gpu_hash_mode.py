@@ -178,6 +178,32 @@ def test_tuning_switches_change_code_paths_not_results(tmp_path, name, prec, tol
             assert np.array_equal(got["X"], base["X"]), sw   # these change WHEN things run, never what is added to what
 
 
+# Long columns: the column kernels sum a column of more than 4 x col_seg_len(LN) chunks in col_segments shares (several work groups, then the
+# shares in order), so a plan with such a column must never fold its column operations into the multiplies' tails, where one work group
+# sums the whole column in another order.  Each fixture proves the path it stands for with the restated chunk and segment rules.
+FOLD_LIMIT_CASES = [("stencil:20:15:8:64:1:5:5", 300, True),      # 8 x 64 z (k_spmm_ilv8w), one block per chunk: 300 chunks, 5 segments, <= 384
+                    ("stencil:40:30:16:64:1:5:5", 300, True),     # 16 x 64 z (k_spmm_mfma), 4 blocks per chunk: the same column of 300 chunks
+                    ("stencil:70:60:16:16:1:7:5", 1050, False)]   # 16 x 16 z (k_spmm_ilv16): 1050 chunks (5 segments at LN = 16), past kFoldMax
+
+
+@pytest.mark.parametrize("name,chunks,small", FOLD_LIMIT_CASES)
+def test_fold_limit_changes_no_bit_of_a_segmented_column(tmp_path, name, chunks, small):
+    """the product, the lab build with TFQMRGPU_FOLD_MAX=0 (never fold) and with 100000 (fold every plan the rule allows): the order of every
+    column sum depends on (chunks of the column, LN) alone, so the solve must not differ in a single bit"""
+    import _env_worker
+    from plan_paths import FOLD_MAX, plan_paths
+    pr = _env_worker.problem(name)
+    ch, seg, folds = plan_paths(pr, "z")
+    assert ch == [chunks] and seg[0] > 1 and (sum(ch) <= FOLD_MAX) == small and not folds
+    base = _worker(tmp_path, "default", name, "z", 1e-9)
+    assert int(base["status"]) == 0
+    for n, sw in enumerate([dict(TFQMRGPU_FOLD_MAX=0), dict(TFQMRGPU_FOLD_MAX=100000)]):
+        got = _worker(tmp_path, "fold%d" % n, name, "z", 1e-9, **sw)
+        assert int(got["status"]) == 0 and int(got["iterations"]) == int(base["iterations"]), sw
+        assert np.array_equal(got["history"], base["history"]) and float(got["residual"]) == float(base["residual"]), sw
+        assert np.array_equal(got["X"], base["X"]), sw
+
+
 @pytest.mark.parametrize("name", ["stencil:40:40:8:8:5:7:5", "stencil:60:60:8:8:2:3:5", "stencil:64:40:8:8:3:11:5"])   # batches (2, 2, 1) | (2) | (2, 1) of block columns; 500 | 450 | 480 chunks (plans of at most 384 fold their column operations instead)
 def test_column_batches_change_no_bit(tmp_path, name):
     """8 x 8 complex<double>: block columns with identical row patterns are multiplied two at a time (k_spmm_ilv8b: one A fetch for both, plans of more

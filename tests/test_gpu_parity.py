@@ -62,7 +62,9 @@ def test_solve_matches_oracle_and_golden(oracle, name):
             assert len(h) == len(h0)
             half = (len(h) + 1) // 2
             assert np.allclose(h[:half], h0[:half], rtol=t["half"], atol=0), (name, np.abs(h[:half] / h0[:half] - 1).max())
-            assert np.allclose(h, h0, rtol=t["hist"], atol=0), (name, np.abs(h / h0 - 1).max())
+            big = np.abs(h0) > t.get("hist_floor", 0.0)        # (entries at the noise floor: absolutely, see tests/tolerances.py)
+            assert np.allclose(h[big], h0[big], rtol=t["hist"], atol=0), (name, np.abs(h[big] / h0[big] - 1).max())
+            assert np.all(np.abs(h[~big] - h0[~big]) <= t["hist"] * t.get("hist_floor", 0.0)), (name, np.abs(h[~big] - h0[~big]).max(initial=0))
             # (not pytest.approx: its default absolute tolerance of 1e-12 would swallow residuals of 1e-10)
             assert abs(info["residual"] - info0["residual"]) <= t["res"] * info0["residual"], (name, info["residual"] / info0["residual"] - 1)
             assert abs(info["residual"] - float(g[tag + "residual"])) <= t["res"] * float(g[tag + "residual"]), name
@@ -122,7 +124,7 @@ def _user_array(blocks, layout, trans):
 
 
 @pytest.mark.parametrize("prec", ["z", "c"])
-@pytest.mark.parametrize("shape", [(4, 4), (8, 8), (8, 10), (8, 32), (8, 64), (16, 16), (16, 32), (32, 32), (16, 64), (32, 64), (64, 64)])   # 16 x 16, 8 x 8 | 32 | 64 z / 16 x 16, 16 | 32 | 64 x 32 | 64 c: plans with groups of rows interleaved
+@pytest.mark.parametrize("shape", [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8, 64), (16, 16), (16, 32), (32, 32), (16, 64), (32, 64), (64, 64)])   # all 15 shapes; 16 x 16, 8 x 8 | 9 | 10 | 32 | 64 z / 16 x 16, 8 | 16 | 32 | 64 x 8 | 32 | 64 c: plans with groups of rows interleaved
 def test_set_get_matrix_layouts(prec, shape):
     LM, LN = shape
     pr = PR.stencil_2d(4, 3, LM, LN, 3, seed=12, radius=1.6)
@@ -595,7 +597,7 @@ def test_multiply_rows_with_more_products_than_the_index_patch_holds(torch_cuda,
 
 
 @pytest.mark.parametrize("prec", ["z", "c"])
-@pytest.mark.parametrize("shape", [(16, 16), (8, 8), (4, 5), (4, 4), (4, 8), (4, 32), (8, 9), (32, 32), (16, 64), (32, 64), (64, 64)])
+@pytest.mark.parametrize("shape", [(16, 16), (8, 8), (4, 5), (4, 4), (4, 8), (4, 32), (8, 9), (8, 10), (8, 32), (8, 64), (16, 32), (32, 32), (16, 64), (32, 64), (64, 64)])   # all 15 shapes
 def test_apply_operator_on_plan_data(oracle, prec, shape):
     """X := A*X with the solver's own multiply kernel and block / element order (16 x 16 z: row pairs interleaved)
     against the oracle's product on the caller's order (reference contract: tfqmrgpu_blockmult.hxx:9-93)"""
@@ -618,6 +620,53 @@ def test_apply_operator_on_plan_data(oracle, prec, shape):
         assert np.array_equal(s.get_matrix(), got)
     eps = 1e-13 if prec == "z" else 3e-5
     assert np.abs(got - want).max() <= eps * LM * 6 * max(1.0, np.abs(want).max())
+
+
+def _long_rows(LM, LN, seed):
+    """about 3500 Y blocks, ragged (a dense block column and one of radius 20 on a 50 x 45 grid), several chunks per column, and runs of 24 block
+    rows with about 150 A blocks each: a chunk there holds more products than the 4-row kernels' LDS index patch (kPairs)"""
+    pr = PR.stencil_2d(50, 45, LM, LN, 2, seed=seed, radius=[None, 20.0])
+    rng = np.random.default_rng(seed)
+    rp, ci, A = [0], [], []
+    for r in range(pr.mb):
+        lo, hi = pr.rowPtrA[r], pr.rowPtrA[r + 1]
+        cols, blocks = list(pr.colIndA[lo:hi]), list(pr.A[lo:hi])
+        if r % 97 < 24:
+            extra = sorted(set(rng.choice(pr.mb, 150, replace=False).tolist()) - set(cols))
+            cols += extra
+            blocks += list((rng.uniform(-1, 1, (len(extra), LM, LM)) + 1j * rng.uniform(-1, 1, (len(extra), LM, LM))) / LM)
+        o = np.argsort(cols)
+        ci += [cols[i] for i in o]
+        A += [blocks[i] for i in o]
+        rp.append(len(ci))
+    return T.Problem(np.array(rp), np.array(ci, dtype=np.int32), np.array(A), pr.rowPtrX, pr.colIndX, pr.rowPtrB, pr.colIndB, pr.B, None, pr.tolerance, 0)
+
+
+@pytest.mark.parametrize("LM,LN,prec,family", [(4, 8, "z", "k_spmm_m4"), (4, 8, "c", "k_spmm_s4w"), (4, 4, "c", "k_spmm_small4"), (4, 5, "z", "k_spmm_small4")])
+def test_apply_operator_four_row_families_on_long_rows(oracle, LM, LN, prec, family):
+    """X := A*X through each 4-row family on a mid-size ragged plan with rows past the LDS index patch, element by element within the rounding
+    bound of a complex sum of n = (longest row) x LM products, 2 sqrt(2) (n + 2) eps |A| |X|, against the oracle's product"""
+    pr = _long_rows(LM, LN, seed=60 + LN)
+    assert pr.nnzbX >= 2000 and int(np.diff(pr.rowPtrA).max()) > 140
+    rng = np.random.default_rng(LN)
+    X = rng.uniform(-1, 1, (pr.nnzbX, LM, LN)) + 1j * rng.uniform(-1, 1, (pr.nnzbX, LM, LN))
+    real = np.float64 if prec == "z" else np.float32
+    an = oracle.analyse(pr)
+    want = oracle.from_native(oracle.spmm(prec, LM, LN, an["starts"], an["pairs"], oracle.a_native(pr.A, real), oracle.to_native(X, real)))
+    env = np.abs(oracle.from_native(oracle.spmm(prec, LM, LN, an["starts"], an["pairs"], oracle.a_native(np.abs(pr.A) + 0j, real),
+                                                oracle.to_native(np.abs(X) + 0j, real))))
+    with T.Solver() as s:
+        s.create_plan(pr)
+        s.set_buffer(nbytes=s.buffer_size(LM, LN, prec))
+        assert s.multiply_kernel() == family
+        s.set_matrix("A", pr.A)
+        s.set_matrix("X", X)
+        s.apply_operator()
+        got = s.get_matrix()
+    n = int(np.diff(pr.rowPtrA).max()) * LM
+    eps = 2.0 ** -53 if prec == "z" else 2.0 ** -24
+    assert np.abs(want).max() > 1
+    assert np.all(np.abs(got - want) <= 2 * np.sqrt(2) * (n + 2) * eps * env * 1.01), np.abs(got - want).max()
 
 
 def test_apply_operator_with_column_batches(oracle):

@@ -11,14 +11,20 @@ import numpy as np
 import pytest
 
 import tfqmrgpu_amd as T
-from conftest import ROOT, load_problem, torchrun
+from _env_worker import problem
+from conftest import ROOT, torchrun
+from plan_paths import FOLD_MAX, plan_paths
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("world,name,prec,tol", [(2, "fd_16x16_small", "z", 1e-9), (3, "stencil_8x8", "z", 1e-9),
                                                  (2, "fd_16x16_2d", "c", 1e-4),
-                                                 (2, "fd_16x16_2d", "m", 1e-9)])     # mixed precision: the refinement's residual rides the same max-reduction
+                                                 (2, "fd_16x16_2d", "m", 1e-9),     # mixed precision: the refinement's residual rides the same max-reduction
+                                                 # 8 x 64 z, a dense column of 300 chunks (5 segments) and one of 29: one rank alone has 329 chunks
+                                                 # (<= 384, the folding size), each of two ranks runs unfolded -- the long column is summed in the
+                                                 # same order either way
+                                                 (2, "stencil:20:15:8:64:2:5:5:-,3", "z", 1e-9)])
 def test_ranks_sharing_one_gpu(tmp_path, world, name, prec, tol):
     out = str(tmp_path / "sharded.npz")
     env = dict(os.environ, OMP_NUM_THREADS="2", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -27,7 +33,10 @@ def test_ranks_sharing_one_gpu(tmp_path, world, name, prec, tol):
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     g = np.load(out)
-    pr = load_problem(name)
+    pr = problem(name)
+    if name.startswith("stencil:"):
+        ch, seg, folds = plan_paths(pr, prec)
+        assert ch == [300, 29] and seg == [5, 1] and sum(ch) <= FOLD_MAX and not folds
     with T.Solver() as s:                       # single rank, same settings
         s.create_plan(pr)
         s.set_buffer(nbytes=s.buffer_size(pr.LM, pr.LN, prec))

@@ -3,7 +3,9 @@
 // (b) for small systems in the TAIL of the kernel that produces their input: the work group that finishes a block column last
 // (per-column arrival counter) runs the column's update, the one that finishes the last column runs the decision -- six launches
 // less per iteration slot where the slot is all launch latency ("small systems").  The arithmetic and the order
-// of every sum are the same in both forms: results do not depend on the form, nor on which work group happens to be last.
+// of every sum are the same in both forms: results do not depend on the form, nor on which work group happens to be last.  (A column
+// of several segments -- column_total below -- is summed in shares; the folded form has no shares, so a plan with such a column never
+// folds: tfq_plan.cpp, Plan::foldOk.)
 //
 // What is computed follows the reference: tfqmrgpu_linalg.hxx:50-75 (dec35), :116-151 (dec34), :195-229 (decT),
 // tfqmrgpu_core.hxx:239-260, 274-298 (the stopping logic).
@@ -91,7 +93,10 @@ __device__ inline bool fold_arrive(uint32_t* counter, uint32_t expected, int* la
 // in DevPlan::colPart, and the LAST one to arrive (the column's arrival counter, fold_arrive) adds the S shares IN ORDER and runs the
 // column's update.  The order of every sum is fixed by (n, LN) alone: results do not depend on which work group is last, nor on the
 // number of ranks (a column's chunks are the same on any rank).  Short columns -- every golden fixture -- are summed by one work group exactly
-// as before.  seg < 0: one work group for the whole column whatever its length (the folded path).
+// as before.  seg < 0: the folded path, one work group for the whole column -- only ever called for columns of ONE segment (S = 1, the same sum as
+// above): plans with a longer column do not fold (tfq_plan.cpp, Plan::foldOk), whatever the fold limit, so that the order stays fixed by (n, LN).
+// (Summing the S shares in the folded tail instead -- one work group, share after share -- raised the registers of the fused multiplies that
+// compile the tail in: k_spmm_ilv16 +6 SGPRs, k_spmm_ilv16f +9 VGPRs; out of line, the call cost up to 254 VGPRs and scratch.)
 // A segment is what one work group sums in ONE round of loads (256 / LN lane groups x 16 records in flight: 256 records for LN = 16, 128 for 32); columns
 // of at most four such rounds stay with one work group -- the arrival costs a few microseconds (P2's columns of 705 records, three rounds: 11 us per
 // column kernel either way), BASELINE config 3's, 4's and 5's columns of 1024-4096 records are cut (17-37 -> 10-17 us, profiles/r04_vector_kernels.txt).
@@ -102,7 +107,7 @@ __device__ inline size_t col_part_slot(uint32_t c0, uint32_t col, uint32_t seg) 
 template <int LN, int NPL>
 __device__ inline bool column_total(DevPlan const& d, double const* part, uint32_t col, int seg, double* s, int* lastFlag, double (&res)[NPL]) {
     uint32_t const c0 = d.colChunkPtr[col], c1 = d.colChunkPtr[col + 1], n = c1 - c0;
-    uint32_t const S = (seg < 0) ? 1u : col_segments(n, LN);
+    uint32_t const S = (seg < 0) ? 1u : col_segments(n, LN);   // (seg < 0: a plan that folds has no longer column, see above)
     if (uint32_t(seg < 0 ? 0 : seg) >= S) return false;          // (the grid has as many segments as the longest column needs)
     if (1 == S) { if (seg < 0) column_sum<LN, NPL, true>(part, c0, c1, s, res); else column_sum<LN, NPL>(part, c0, c1, s, res); return true; }
     uint32_t const len = (n + S - 1) / S, b0 = c0 + uint32_t(seg) * len, b1 = min(c1, b0 + len);

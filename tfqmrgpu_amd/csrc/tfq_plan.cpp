@@ -352,7 +352,19 @@ tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
         }
     }
     size_t const nChunks = p.chunks.col.size();
-    if (nChunks <= size_t(lab_switch("TFQMRGPU_FOLD_MAX", kFoldMax))) { p.colBatch.clear(); p.chunks.orderB.clear(); }   // small plans fold their column operations into the multiplies' tails instead (below)
+    p.colSegMax = 1;                                  // long columns are summed by several work groups (tfq_colops.hpp: column_total)
+    for (uint32_t jb = 0; jb < p.nCols; ++jb)
+        p.colSegMax = std::max(p.colSegMax, col_segments(p.chunks.colPtr[jb + 1] - p.chunks.colPtr[jb], LN));
+    // Small systems fold the column operations into the producers' tails (tfq_colops.hpp): six launches less per iteration slot.
+    // "Small" = at most kFoldMax = 384 chunks, i.e. work groups per multiply: measured with one build and the switch (scripts/fold_crossover.py).
+    // r03, arrivals with fences: gains below 128 chunks, LOSES 10-14 % at 256 ... 288.  r04, fence-free arrivals (co_store / co_load): 22 chunks -9 %,
+    // 256-288 chunks -6 ... -9.5 %, 576 chunks +1.6 %, 1024 and more +6 ... +27 % (every work group waits for its own stores in front of the arrival):
+    // profiles/r04_small_systems.txt.  Lab builds: TFQMRGPU_FOLD_MAX chunks.
+    // A plan with a column of several segments never folds: the folded tail sums a column in one work group, the column kernels sum its segments
+    // first, and the two orders give different bits.  So the order of every column sum depends on (chunks of the column, LN) alone -- not on the
+    // fold limit, the number of ranks or a user-defined operator.  (The product meets such a plan only at LN = 64: a column of 257 ... 384 chunks.)
+    p.foldOk = (nChunks <= size_t(lab_switch("TFQMRGPU_FOLD_MAX", kFoldMax))) && 1 == p.colSegMax;
+    if (p.foldOk) { p.colBatch.clear(); p.chunks.orderB.clear(); }   // small plans fold their column operations into the multiplies' tails instead
 
     size_t at = 0;
     auto take = [&](Window& w, size_t bytes) { w.offset = at; w.bytes = bytes; at = align256(at + bytes); };
@@ -376,12 +388,7 @@ tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
     take(p.wPz, nChunks * 2 * LN * sizeof(double));
     take(p.wPd, nChunks * LN * sizeof(double));
     take(p.wColRec, size_t(p.nCols) * 2 * sizeof(double)); // per-column stopping-test record
-    {   // long columns are summed by several work groups (tfq_colops.hpp: column_total)
-        p.colSegMax = 1;
-        for (uint32_t jb = 0; jb < p.nCols; ++jb)
-            p.colSegMax = std::max(p.colSegMax, col_segments(p.chunks.colPtr[jb + 1] - p.chunks.colPtr[jb], LN));
-        take(p.wColPart, (nChunks / kColSlot + p.nCols + 2) * 3 * size_t(LN) * sizeof(double));
-    }
+    take(p.wColPart, (nChunks / kColSlot + p.nCols + 2) * 3 * size_t(LN) * sizeof(double));   // the segments' shares (colSegMax > 1)
     take(p.wChunkFirst, (nChunks + 1) * sizeof(uint32_t));
     take(p.wChunkCol, nChunks * sizeof(uint32_t));
     take(p.wOrder, nChunks * sizeof(uint32_t));
@@ -400,12 +407,6 @@ tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
     take(p.wRowI, size_t(p.nnzbX) * sizeof(uint32_t));
     take(p.wFold, (size_t(p.nCols) + 1) * sizeof(uint32_t));
     take(p.wSelf, 1024);
-    // Small systems fold the column operations into the producers' tails (tfq_colops.hpp): six launches less per iteration slot.
-    // "Small" = at most kFoldMax = 384 chunks, i.e. work groups per multiply: measured with one build and the switch (scripts/fold_crossover.py).
-    // r03, arrivals with fences: gains below 128 chunks, LOSES 10-14 % at 256 ... 288.  r04, fence-free arrivals (co_store / co_load): 22 chunks -9 %,
-    // 256-288 chunks -6 ... -9.5 %, 576 chunks +1.6 %, 1024 and more +6 ... +27 % (every work group waits for its own stores in front of the arrival):
-    // profiles/r04_small_systems.txt.  Lab builds: TFQMRGPU_FOLD_MAX chunks.
-    p.foldOk = (nChunks <= size_t(lab_switch("TFQMRGPU_FOLD_MAX", kFoldMax)));
     take(p.wA, size_t(p.nnzbA) * 2 * LM * LM * p.realBytes);
     if (mixed) {
         // Mixed precision: float vectors for the iteration (above), and in double the solution, B, A (the refinement's residual

@@ -114,7 +114,8 @@ def dense_random(mb=5, LM=4, LN=4, ncols=2, seed=7, shift=8.0):
 def stencil_2d(nx, ny, LM, LN, ncols, seed=1, radius=None, points=5):
     """Block 5-point (or 9/13-point) stencil on an nx x ny grid with random blocks, made block
     diagonally dominant; X dense in `ncols` block columns (or inside `radius` grid steps of the
-    source of each column); B = one random block per column.  Used for BASELINE configs 3-5."""
+    source of each column; a sequence: one radius per column, None = dense); B = one random block per column.
+    Used for BASELINE configs 3-5."""
     mb = nx * ny
     offs = [(0, 0), (1, 0), (-1, 0), (0, 1), (0, -1)]
     if points >= 9:
@@ -136,14 +137,16 @@ def stencil_2d(nx, ny, LM, LN, ncols, seed=1, radius=None, points=5):
     diag = np.nonzero(rows == ciA)[0]
     A[diag] += 2.0 * np.eye(LM)
     src = [(c * mb) // ncols + (mb // ncols) // 2 for c in range(ncols)]  # source row of each column
+    radii = list(radius) if isinstance(radius, (list, tuple)) else [radius] * ncols
+    assert len(radii) == ncols
     rpX, ciX = [0], []
     for r in range(mb):
         for c in range(ncols):
-            if radius is None:
+            if radii[c] is None:
                 ciX.append(c)
             else:
                 sx, sy = src[c] % nx, src[c] // nx
-                if (r % nx - sx) ** 2 + (r // nx - sy) ** 2 <= radius * radius:
+                if (r % nx - sx) ** 2 + (r // nx - sy) ** 2 <= radii[c] * radii[c]:
                     ciX.append(c)
         rpX.append(len(ciX))
     rpB, ciB = [0], []
