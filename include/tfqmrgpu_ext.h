@@ -102,7 +102,15 @@ tfqmrgpuStatus_t tfqmrgpuExt_getWorkVector(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
  * All pointers are DEVICE pointers.  Blocks are in the native layout RRRRIIII:
  * A[nnzbA][2][lm(k)][lm(i)] (transposed), X|Y[nnzb][2][lm][ln].
  * Same contract as the reference kernel gemmNxNf (tfqmrgpu_blockmult.hxx:9-93).
- * Four real products per complex one, as the reference (the three-product form is an option of a PLAN, section 6). */
+ * Four real products per complex one, as the reference (the three-product form is an option of a PLAN, section 6).
+ * precision: 'z' (or 'd') complex<double>; 'm' float data summed in double -- operands and Y are float, every sum is
+ * accumulated in double and rounded to float once, when Y is stored (the reference's gemmNxNf<float, ..., double>); every
+ * other letter complex<float> ('c', 'f').
+ * Shapes (lm x ln), the 21 of the reference's `bench multi`, in every precision: the solver's 15 (4x4, 4x5, 4x8, 4x32, 8x8,
+ * 8x9, 8x10, 8x32, 8x64, 16x16, 16x32, 16x64, 32x32, 32x64, 64x64) and 6x6, 12x12, 24x24, 48x48, 96x96, 128x128.  Any other
+ * shape returns TFQMRGPU_BLOCKSIZE_MISSING.  The further shapes belong to this product only: the block
+ * sizes of the solver (tfqmrgpu_bsrsv_bufferSize, tfqmrgpu_bsrsv_allowedBlockSizes) do not change, as in the reference
+ * (allowed_block_sizes.h). */
 tfqmrgpuStatus_t tfqmrgpuExt_multiply(tfqmrgpuHandle_t handle,
     char precision, int lm, int ln,
     uint32_t nnzbY, uint32_t const *starts_d, uint32_t const *pairs_d,
@@ -114,7 +122,8 @@ tfqmrgpuStatus_t tfqmrgpuExt_multiply(tfqmrgpuHandle_t handle,
  * back from the device, finds block columns (Y blocks that share X blocks) and row bands (by the A indices) and leaves an XCD-aware order
  * in device memory: mode 1 = neighbouring work groups share X and A blocks, the 8 XCDs split the block COLUMNS (every L2 sees all of A and an
  * eighth of X); mode 3 = the XCDs split the block ROWS (an eighth of A, all of X); mode 4 = 1 or 3, whichever keeps the larger operand split
- * (the recommended one); mode 2 = mode 1 with the work groups of most block products first; mode 0 or a shape whose kernel takes no order: *order = NULL,
+ * (the recommended one); mode 2 = mode 1 with the work groups of most block products first; mode 0 or a shape whose kernel takes no order (lm or ln
+ * not a multiple of 16): *order = NULL,
  * which multiplyOrdered treats as the caller's order.  Results are those of tfqmrgpuExt_multiply bit for bit (the same kernel computes
  * every Y block from the same pair list).  An order belongs to ONE listing (nnzbY, starts, pairs): release it with multiplyRelease. */
 tfqmrgpuStatus_t tfqmrgpuExt_multiplyPrepare(tfqmrgpuHandle_t handle, char precision, int lm, int ln,

@@ -4,7 +4,8 @@
 //
 //   bench_tfqmrgpu multi <planfile> [precision=f] [nrep=1] [nsamp=1] [lm=16] [ln=lm]
 //       plan file `#nnzb_for_Y_A_X= nY nA nX` + lines `iY iA iX beta` (bench_tfqmrgpu.cu:456-498), cos/sin fill
-//       (:274-287), host re-computation check maxdev <= 1e-4 (:349-420).  A `.gz` file is read with zlib.
+//       (:274-287), host re-computation check maxdev <= 1e-4 (:349-420).  A `.gz` file is read with zlib.  precision f | c, d | z, or m
+//       (float data summed in double, the reference's gemmNxNf<float, ..., double>: float arrays, `f` result lines, the f64 matrix peak).
 //   bench_tfqmrgpu tfQMR <problem.xml> [precision=z] [nrep=1] [MaxIter=2000]
 //       solves the <LinearProblem> (schema of tfqmrgpu_example_xml_reader.hxx:125-292) through createPlan ->
 //       bufferSize -> setBuffer -> setMatrix -> solve -> getInfo -> getMatrix and compares with the stored X if any
@@ -74,7 +75,9 @@ int bench_multi(int argc, char** argv) {
     int const lm = (argc > 6) ? std::atoi(argv[6]) : 16;
     int const ln = (argc > 7) ? std::atoi(argv[7]) : lm;
     bool const dbl = ('d' == fF || 'z' == fF);
-    char const prec = dbl ? 'z' : 'c';
+    // m: float data summed in double (the reference's gemmNxNf<float, ..., double>, bench_tfqmrgpu.cu:520-547): float arrays, the f64 matrix pipe
+    bool const mixed = ('m' == fF);
+    char const prec = dbl ? 'z' : mixed ? 'm' : 'c';
 
     std::string const text = slurp(path);
     std::istringstream in(text);
@@ -202,7 +205,7 @@ int bench_multi(int argc, char** argv) {
         std::vector<char> usedA(size_t(nA), 0); size_t nAref = 0;
         for (size_t q = 0; q < nPairs; ++q) if (!usedA[pairs[2 * q]]) { usedA[pairs[2 * q]] = 1; ++nAref; }
         double const bytes = double(nAref) * 2 * PA * rb + double(nX + nY) * 2 * PX * rb + 4.0 * (nY + 1) + 8.0 * nPairs;
-        double const t1 = tsum / (double(nsamp) * nrep), peak = dbl ? 78.6e12 : 157.3e12;
+        double const t1 = tsum / (double(nsamp) * nrep), peak = (dbl || mixed) ? 78.6e12 : 157.3e12;
         bool const hbm = bytes / 8.0e12 >= flop1 / peak;
         std::printf("# MI355X roofline: %.1f GB/s of compulsory bytes (%.3f of 8 TB/s HBM), %.2f T%clop/s (%.3f of the %.1f T%clop/s matrix peak): %s-bound, fraction %.3f\n",
                     bytes * 1e-9 / t1, bytes / t1 / 8.0e12, flop1 * 1e-12 / t1, ch, flop1 / t1 / peak, peak * 1e-12, ch,

@@ -1111,7 +1111,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_multiplyPrepare(tfqmrgpuHandle_t handle, char preci
     auto h = (Handle*)handle;
     if (!h || !starts_d || !pairs_d || !order) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     *order = nullptr;
-    if (!blockSizeAllowed(lm, ln)) return err(TFQMRGPU_BLOCKSIZE_MISSING, ln, lm);
+    if (!multiply_shape_allowed(precision, lm, ln)) return err(TFQMRGPU_BLOCKSIZE_MISSING, ln, lm);
     uint32_t const ch = multiply_blocks_per_work_group(precision, lm, ln);
     if (0 == ch || 0 == nnzbY || mode <= 0) return TFQMRGPU_STATUS_SUCCESS;      // nothing to prepare: a null order is the caller's order
     hipStream_t const s = (hipStream_t)h->stream;

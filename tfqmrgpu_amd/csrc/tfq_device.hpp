@@ -137,6 +137,7 @@ void launch_probe_decide(DevPlan const& d, int phase, hipStream_t s);
 tfqmrgpuStatus_t launch_multiply(char precision, int lm, int ln, uint32_t nnzbY,
     uint32_t const* starts, uint32_t const* pairs, void const* A, void const* X, void* Y, hipStream_t s, uint32_t const* yOrder = nullptr);
 uint32_t multiply_blocks_per_work_group(char precision, int lm, int ln);   // Y blocks per work group of that launch (0: this shape's kernel takes no prepared order)
+bool multiply_shape_allowed(char precision, int lm, int ln);              // the shapes of that product in that precision (tfqmrgpu_ext.h section 3)
 
 // layout conversion between the caller's block layout and the native one (tfq_layout.hip)
 // direction 0: user -> native (setMatrix), 1: native -> user (getMatrix); one batch of user blocks

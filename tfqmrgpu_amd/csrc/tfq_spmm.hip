@@ -260,45 +260,83 @@ __global__ __launch_bounds__(256) void k_spmm_n16(SpmmArgs a) {
     }
 }
 
-uint32_t multiply_blocks_per_work_group(char precision, int lm, int ln) {
-    bool const dbl = ('z' == (precision | 32)) || ('d' == (precision | 32));
+static MulPrec multiply_precision(char precision) {
+    char const p = char(precision | 32);
+    return ('z' == p || 'd' == p) ? MulPrec::z : ('m' == p) ? MulPrec::m : MulPrec::c;
+}
+
+// The kernel family of a stand-alone multiply (tfqmrgpuExt_multiply), the counterpart of spmm_select for plans and the one place that
+// decides which shapes the product takes in which precision.  plan: the family spmm_select picks (k_spmm_mfma, k_spmm_mfma8, k_spmm_s4w,
+// k_spmm_m4, k_spmm_small4 on the solver's shapes); wide: k_spmm_mfma on TFQ_MULTIPLY_SIZES; mfma_m: k_spmm_mfma_m (`m`, multiples of 16);
+// pad: k_spmm_pad (TFQ_PAD_SIZES; in `m` also the 4- and 8-row shapes).
+enum class MulKernel { missing, n16, plan, wide, mfma_m, pad };
+static MulKernel multiply_select(MulPrec p, int lm, int ln) {
     bool const mfma = (lm % 16 == 0 && ln % 16 == 0);
-    if (!mfma) return 0;                                   // (a prepared order is honoured by k_spmm_mfma only)
+    bool const solver = solver_shape(lm, ln), wide = wide_shape(lm, ln);
+    if (pad_shape(lm, ln)) return MulKernel::pad;
+    if (MulPrec::m == p) return !(solver || wide) ? MulKernel::missing : mfma ? MulKernel::mfma_m : MulKernel::pad;
+    if (wide) return MulKernel::wide;
+    if (!solver) return MulKernel::missing;
+    // float: the reference's plan file 44.3 -> 59.2 TFLOP/s (0.28 -> 0.38 of the matrix peak), a 16 x 16 c stencil 0.360 -> 0.249 ms (0.55); double: the LDS traffic doubles with the
+    // element size and the plan file LOSES 7 % (35.3 -> 32.9), P2 gains 3 %: float only (lab: TFQMRGPU_N16 bit 0 = float, bit 1 = double; profiles/r04_native_multiply.txt)
+    if (16 == lm && 16 == ln && (lab_switch("TFQMRGPU_N16", 1) & ((MulPrec::z == p) ? 2 : 1))) return MulKernel::n16;
+    return MulKernel::plan;
+}
+
+// units (strips of a Y block, k_spmm_mfma | k_spmm_mfma_m) per Y block; rb: bytes per accumulator element
+static int mfma_units(int lm, int ln, int rb) {
+    int const cs = mfma_col_split(rb, ln);
     int const mt = lm / 16;
-    int const ms = (mt % 2 == 0 && 2 * (ln / 16) * (dbl ? 8 : 4) <= 32) ? 2 : 1;   // RowTiles<>::MS
-    int const mu = mt / ms;
+    int const ms = (mt % 2 == 0 && 2 * (ln / (16 * cs)) * rb <= 32) ? 2 : 1;   // RowTiles<>::MS
+    return (mt / ms) * cs;
+}
+
+bool multiply_shape_allowed(char precision, int lm, int ln) {
+    return MulKernel::missing != multiply_select(multiply_precision(precision), lm, ln);
+}
+
+uint32_t multiply_blocks_per_work_group(char precision, int lm, int ln) {
+    bool const mfma = (lm % 16 == 0 && ln % 16 == 0);
+    if (!mfma) return 0;                                   // (a prepared order is honoured by k_spmm_mfma | k_spmm_mfma_m only)
+    int const mu = mfma_units(lm, ln, (MulPrec::c == multiply_precision(precision)) ? 4 : 8);
     return uint32_t((mu >= 4) ? 1 : 4 / mu);
 }
 
 tfqmrgpuStatus_t launch_multiply(char precision, int lm, int ln, uint32_t nnzbY,
     uint32_t const* starts, uint32_t const* pairs, void const* A, void const* X, void* Y, hipStream_t s, uint32_t const* yOrder)
 {
-    bool const dbl = ('z' == (precision | 32)) || ('d' == (precision | 32));
+    MulPrec const prec = multiply_precision(precision);
+    MulKernel const k = multiply_select(prec, lm, ln);
+    if (MulKernel::missing == k) return err(TFQMRGPU_BLOCKSIZE_MISSING, ln, lm);
+    bool const dbl = (MulPrec::z == prec);
     SpmmArgs a{};
     a.Y = Y; a.A = A; a.X = X; a.starts = starts; a.pairs = pairs; a.nY = nnzbY;
     a.chunkFirst = nullptr; a.gate = 0;
     a.yOrder = (lm % 16 == 0 && ln % 16 == 0) ? yOrder : nullptr;
-    // plain mode: enough work groups to fill 256 CUs several times, at least one strip per wave
-    bool const mfma = (lm % 16 == 0 && ln % 16 == 0);
-    int const mt = mfma ? lm / 16 : 1;
-    int const ms = (mt % 2 == 0 && 2 * (ln / 16) * (dbl ? 8 : 4) <= 32) ? 2 : 1;   // RowTiles<>::MS
-    int const mu = mt / ms;                               // strips per Y block
-    uint32_t ch = (mu >= 4) ? 1 : 4 / mu;                 // one strip per wave
-    if (!mfma) ch = (4 == lm) ? 64 : (lm * ln >= 256) ? 1 : 256 / (lm * ln); // k_spmm_small4: a few sub-blocks per thread group
-    if (8 == lm) ch = 4;                                  // k_spmm_mfma8 (kTile8): one Y block per wave and pass
-    if (4 == lm && dbl && 32 == ln) ch = 16;              // k_spmm_m4: 64 items, four per Y block (and the tile kernel's 16 before it)
-    a.CH = ch;
-    uint32_t nWG = (nnzbY + ch - 1) / ch;
-    // (lab: contiguous eighths of the caller's Y blocks per XCD instead of round-robin work groups)
-    if (mfma && nWG >= 64 && lab_switch("TFQMRGPU_PLAIN_XCD", 0)) { a.plainPer = (nWG + 7) / 8; nWG = 8 * a.plainPer; }
-    // float: the reference's plan file 44.3 -> 59.2 TFLOP/s (0.28 -> 0.38 of the matrix peak), a 16 x 16 c stencil 0.360 -> 0.249 ms (0.55); double: the LDS traffic doubles with the
-    // element size and the plan file LOSES 7 % (35.3 -> 32.9), P2 gains 3 %: float only (lab: TFQMRGPU_N16 bit 0 = float, bit 1 = double; profiles/r04_native_multiply.txt)
-    if (16 == lm && 16 == ln && (lab_switch("TFQMRGPU_N16", 1) & (dbl ? 2 : 1))) {
-        if (nWG) { if (dbl) k_spmm_n16<double><<<dim3(nWG), dim3(256), 0, s>>>(a); else k_spmm_n16<float><<<dim3(nWG), dim3(256), 0, s>>>(a); }
-        return (hipSuccess == hipGetLastError()) ? TFQMRGPU_STATUS_SUCCESS : TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
+    bool ok = true;
+    if (MulKernel::pad == k) ok = spmm_pad(prec, lm, ln, a, s);      // (its own work groups: one Y block per wave)
+    else {
+        // plain mode: enough work groups to fill 256 CUs several times, at least one strip per wave
+        bool const mfma = (lm % 16 == 0 && ln % 16 == 0);
+        int const mu = mfma ? mfma_units(lm, ln, (MulPrec::c == prec) ? 4 : 8) : 1;   // strips per Y block
+        uint32_t ch = (mu >= 4) ? 1 : 4 / mu;                 // one strip per wave
+        if (!mfma) ch = (4 == lm) ? 64 : (lm * ln >= 256) ? 1 : 256 / (lm * ln); // k_spmm_small4: a few sub-blocks per thread group
+        if (8 == lm) ch = 4;                                  // k_spmm_mfma8 (kTile8): one Y block per wave and pass
+        if (4 == lm && dbl && 32 == ln) ch = 16;              // k_spmm_m4: 64 items, four per Y block (and the tile kernel's 16 before it)
+        a.CH = ch;
+        uint32_t nWG = (nnzbY + ch - 1) / ch;
+        // (lab: contiguous eighths of the caller's Y blocks per XCD instead of round-robin work groups)
+        if (mfma && nWG >= 64 && lab_switch("TFQMRGPU_PLAIN_XCD", 0)) { a.plainPer = (nWG + 7) / 8; nWG = 8 * a.plainPer; }
+        switch (k) {
+        case MulKernel::n16:
+            if (nWG) { if (dbl) k_spmm_n16<double><<<dim3(nWG), dim3(256), 0, s>>>(a); else k_spmm_n16<float><<<dim3(nWG), dim3(256), 0, s>>>(a); }
+            break;
+        case MulKernel::mfma_m: ok = spmm_mfma_m(lm, ln, a, nWG, s); break;     // float data, double sums
+        case MulKernel::wide:   ok = spmm_mfma_wide(dbl, lm, ln, a, nWG, s); break;
+        default:                ok = spmm_go(dbl, lm, ln, EPI_NONE, a, nWG, s); break;
+        }
     }
-    if (!spmm_go(dbl, lm, ln, EPI_NONE, a, nWG, s))
-        return err(TFQMRGPU_BLOCKSIZE_MISSING, ln, lm);
+    if (!ok) return err(TFQMRGPU_BLOCKSIZE_MISSING, ln, lm);
     return (hipSuccess == hipGetLastError()) ? TFQMRGPU_STATUS_SUCCESS : TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
 }
 

@@ -14,7 +14,10 @@
 //  * tfq_spmm_ilv8.hip: k_spmm_ilv8 | k_spmm_ilv8b (8 x 8 complex<double>, a block = one access; b: column batches, config 5), k_spmm_ilv8w
 //    (8 x 32 | 64 | 9 | 10 complex<double>, row pairs), k_spmm_ilv8f (8 x 8 | 32 | 64 complex<float>, row quads, two products per tile);
 // on the reference's native order (every other shape, caller-owned arrays of tfqmrgpuExt_multiply, TFQMRGPU_ILV=0):
-//  * tfq_spmm_mfma.hip: k_spmm_mfma (LM and LN multiples of 16: a wave keeps a strip of a Y block in MFMA accumulators);
+//  * tfq_spmm_mfma.hip: k_spmm_mfma (LM and LN multiples of 16: a wave keeps a strip of a Y block in MFMA accumulators; in the stand-alone
+//    multiply also 48 | 96 | 128 square, TFQ_MULTIPLY_SIZES), k_spmm_mfma_m (tfqmrgpuExt_multiply in `m`: float data, double accumulators);
+//  * tfq_spmm_pad.hip: k_spmm_pad (tfqmrgpuExt_multiply on 6 | 12 | 24 square, and `m` on the 4- and 8-row shapes: operands through a
+//    zero-padded LDS image into 16 x 16 MFMA tiles);
 //  * tfq_spmm_ilv8.hip: k_spmm_mfma8 (LM == 8, and 4 x 32 z: [Re A; Im A] x [Re X | Im X] fills one 16 x 16 tile per 8 block columns);
 //  * tfq_spmm_rows4.hip: k_spmm_m4 (4 x 4 | 8 | 32 in double, v_mfma_f64_4x4x4_4b_f64), k_spmm_s4w (4 x 8 | 32 in float, 4 x 4 without
 //    epilogue: two | four neighbouring columns per lane), k_spmm_small4 (the other 4-row shapes: one lane per element, operands through LDS);
@@ -351,6 +354,28 @@ template <bool OK, typename F> inline void variant(bool v, F&& f) {
     X(R, 4, 4) X(R, 4, 5) X(R, 4, 8) X(R, 4, 32) X(R, 8, 8) X(R, 8, 9) X(R, 8, 10) X(R, 8, 32) X(R, 8, 64) \
     X(R, 16, 16) X(R, 16, 32) X(R, 16, 64) X(R, 32, 32) X(R, 32, 64) X(R, 64, 64)
 
+// the further shapes of the stand-alone multiply (tfqmrgpuExt_multiply, the reference's `bench multi`): the plain product only, on
+// k_spmm_mfma in `c` and `z` and on k_spmm_mfma_m in `m`; no solver family is instantiated for them and the solver's list
+// (tfq_plan.cpp: kAllowedBlockSizes) does not change
+#define TFQ_MULTIPLY_SIZES(X, R) X(R, 48, 48) X(R, 96, 96) X(R, 128, 128)
+// ... and those that do not fill 16 x 16 tiles, on k_spmm_pad: in every precision, and the 4- and 8-row shapes of TFQ_SIZES in `m`
+#define TFQ_PAD_SIZES(X, R) X(R, 6, 6) X(R, 12, 12) X(R, 24, 24)
+#define TFQ_PAD_M_SIZES(X, R) X(R, 4, 4) X(R, 4, 5) X(R, 4, 8) X(R, 4, 32) X(R, 8, 8) X(R, 8, 9) X(R, 8, 10) X(R, 8, 32) X(R, 8, 64)
+#define TFQ_SIZE_IS(R, LM, LN) || (lm == LM && ln == LN)
+constexpr bool solver_shape(int lm, int ln) { return false TFQ_SIZES(TFQ_SIZE_IS, 0); }            // one of TFQ_SIZES
+constexpr bool wide_shape(int lm, int ln) { return false TFQ_MULTIPLY_SIZES(TFQ_SIZE_IS, 0); }     // one of TFQ_MULTIPLY_SIZES
+constexpr bool pad_shape(int lm, int ln) { return false TFQ_PAD_SIZES(TFQ_SIZE_IS, 0); }           // one of TFQ_PAD_SIZES
+#undef TFQ_SIZE_IS
+
+// The precisions of the stand-alone multiply (the reference's `bench multi`): `z` | `d` complex<double>, `m` float data summed in double,
+// every other letter complex<float>
+enum class MulPrec { c, z, m };
+
+// Waves per 16-row strip of a Y block in k_spmm_mfma | k_spmm_mfma_m (rb: bytes per accumulator element): two, each with LN / 2 columns,
+// where the double accumulators of a whole strip and two operand slices would not fit the 256 VGPRs of two waves per SIMD
+// (128 columns: 128 VGPRs of accumulators)
+constexpr int mfma_col_split(int rb, int ln) { return (8 == rb && ln >= 128) ? 2 : 1; }
+
 // Launches Family<R, LM, LN, EPI>::go(k, a, nWG, s) for the precision, shape and epilogue of a launch (nothing when nWG == 0);
 // false: the shape is not one of TFQ_SIZES
 template <template <typename, int, int, int> class Family, typename R, int LM, int LN>
@@ -375,6 +400,12 @@ bool spmm_switch(SpmmKernel k, bool dbl, int lm, int ln, int epi, SpmmArgs const
 // The launchers of the family files: launch kernel family k (spmm_select's choice for this launch) on nWG work groups; false: the
 // shape is not one of TFQ_SIZES
 bool spmm_mfma(SpmmKernel k, bool dbl, int lm, int ln, int epi, SpmmArgs const& a, uint32_t nWG, hipStream_t s);    // mfma
+// the stand-alone multiply (plain mode, no epilogue): k_spmm_mfma on TFQ_MULTIPLY_SIZES, and k_spmm_mfma_m (precision `m`) on every shape of
+// TFQ_SIZES and TFQ_MULTIPLY_SIZES with LM and LN multiples of 16; false: not such a shape
+bool spmm_mfma_wide(bool dbl, int lm, int ln, SpmmArgs const& a, uint32_t nWG, hipStream_t s);
+bool spmm_mfma_m(int lm, int ln, SpmmArgs const& a, uint32_t nWG, hipStream_t s);
+// k_spmm_pad on TFQ_PAD_SIZES (and TFQ_PAD_M_SIZES in `m`), a.nY Y blocks; false: not such a shape
+bool spmm_pad(MulPrec p, int lm, int ln, SpmmArgs const& a, hipStream_t s);
 bool spmm_ilv16(SpmmKernel k, bool dbl, int lm, int ln, int epi, SpmmArgs const& a, uint32_t nWG, hipStream_t s);   // ilv16, ilv16f, ilvf
 bool spmm_ilv8(SpmmKernel k, bool dbl, int lm, int ln, int epi, SpmmArgs const& a, uint32_t nWG, hipStream_t s);    // ilv8b, ilv8, ilv8f, ilv8w, mfma8
 bool spmm_rows4(SpmmKernel k, bool dbl, int lm, int ln, int epi, SpmmArgs const& a, uint32_t nWG, hipStream_t s);   // s4w, m4, small4

@@ -13,8 +13,10 @@ namespace tfq {
 // column (nt/VW) * 16 VW + lc * VW + nt % VW (not nt * 16 + lc).  X operands and every epilogue vector then move
 // as 16-byte accesses, 256 contiguous bytes per row and lane group (the memory pipe retires one wave-wide access
 // per 16 clocks whatever its width, scripts/ta_rate.hip).  Which 16 columns share a tile is free.
+// VW: the largest power of two with VW * sizeof(R) <= 16 that divides NT (3 | 6 tiles: one | two columns per access).
+constexpr int col_vw(int nt, int rb) { int v = 16 / rb; while (nt % v) v /= 2; return v; }
 template <typename R, int NT> struct ColMap {
-    static constexpr int VW = (NT * sizeof(R) <= 16) ? NT : int(16 / sizeof(R));   // columns per access
+    static constexpr int VW = col_vw(NT, int(sizeof(R)));                            // columns per access
     static constexpr int NG = NT / VW;                                             // accesses per row
     __device__ static inline int col(int lc, int nt) { return (nt / VW) * 16 * VW + lc * VW + nt % VW; }
 };
@@ -70,6 +72,25 @@ struct Slice {
             }
         }
     }
+    // the precision `m`: float operands widened to double in registers (v_cvt_f64_f32; the product of two floats is exact in double),
+    // double accumulators, the four real products in the order of mma below
+    __device__ inline void mma_f64(d4 (&cre)[MS][NT], d4 (&cim)[MS][NT]) const {
+        static_assert(std::is_same<R, float>::value, "float operands");
+#pragma unroll
+        for (int s = 0; s < KSL; ++s)
+#pragma unroll
+            for (int ms = 0; ms < MS; ++ms) {
+                double const a_r = ar[s][ms], a_i = ai[s][ms], na_i = -a_i;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    double const x_r = xr[s][nt], x_i = xi[s][nt];
+                    cre[ms][nt] = Acc<double>::mma(a_r, x_r, cre[ms][nt]);
+                    cim[ms][nt] = Acc<double>::mma(a_r, x_i, cim[ms][nt]);
+                    cre[ms][nt] = Acc<double>::mma(na_i, x_i, cre[ms][nt]);
+                    cim[ms][nt] = Acc<double>::mma(a_i, x_r, cim[ms][nt]);
+                }
+            }
+    }
     template <typename T4>
     __device__ inline void mma(T4 (&cre)[MS][NT], T4 (&cim)[MS][NT]) const {
 #pragma unroll
@@ -96,7 +117,9 @@ template <typename R, int LM, int LN, int EPI, bool PRE, bool M3, bool HASH, boo
 __global__ __launch_bounds__(256, 2) void k_spmm_mfma(SpmmArgs a) {   // at least 2 waves per SIMD: 256 VGPRs at most
     if (gate_closed(a)) return;
     static_assert(LM % 16 == 0 && LN % 16 == 0, "MFMA tiles are 16 x 16");
-    constexpr int P = LM * LN, MT = LM / 16, NT = LN / 16;
+    constexpr int CS = mfma_col_split(sizeof(R), LN);   // waves per strip, LN / CS columns each
+    static_assert(CS == 1 || EPI == EPI_NONE, "the epilogues take whole rows");
+    constexpr int P = LM * LN, MT = LM / 16, NT = LN / (16 * CS);
     constexpr int MS = RowTiles<R, MT, NT>::MS;      // row tiles per wave
     constexpr int MU = MT / MS;                      // strips per Y block
     constexpr int KSL = (MS * NT >= 4) ? 2 : 4;      // k-steps per slice: bounds the registers of the prefetch
@@ -128,12 +151,13 @@ __global__ __launch_bounds__(256, 2) void k_spmm_mfma(SpmmArgs a) {   // at leas
     }
     double part[NPL > 0 ? NPL : 1][NT] = {};
 
-    uint32_t const nUnits = (last - first) * MU;     // unit = strip of MS * 16 rows of one Y block
+    uint32_t const nUnits = (last - first) * MU * CS;   // unit = strip of MS * 16 rows (and LN / CS columns) of one Y block
     using CU32o = __attribute__((address_space(4))) uint32_t const*;
     CU32o const yOrder = (CU32o)(uintptr_t)a.yOrder;
     for (uint32_t u = wave; u < nUnits; u += 4) {
-        uint32_t const y = a.yOrder ? yOrder[first + u / MU] : first + u / MU;   // (plain mode with a prepared order: which Y block this position computes)
-        int const i0 = int(u % MU) * 16 * MS;
+        uint32_t const y = a.yOrder ? yOrder[first + u / (MU * CS)] : first + u / (MU * CS);   // (plain mode with a prepared order: which Y block this position computes)
+        int const i0 = int((u / CS) % MU) * 16 * MS;
+        int const cb = int(u % CS) * (LN / CS);      // first block column of this unit
         uint64_t const key = HASH ? shadow_key(uint32_t(a.origCol[col]), a.rowI[y]) : 0;
         T4 cre[MS][NT], cim[MS][NT], cp3[M3 ? MS : 1][M3 ? NT : 1];   // M3: P1, P2, P3
 #pragma unroll
@@ -152,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void k_spmm_mfma(SpmmArgs a) {   // at leas
         uint32_t const q0 = cstarts[y];
         uint32_t const nT = (cstarts[y + 1] - q0) * SPP;   // slices of this strip
         R const* const A0 = (R const*)a.A + i0 + lc * MS;
-        R const* const X0 = (R const*)a.X + c0;
+        R const* const X0 = (R const*)a.X + cb + c0;
         auto fetch = [&](Slice<R, MS, NT, KSL>& o, uint32_t t) {
             uint32_t const q = q0 + t / SPP;
             int const k0 = int(t % SPP) * (4 * KSL);
@@ -210,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void k_spmm_mfma(SpmmArgs a) {   // at leas
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int g = 0; g < NG; ++g) {       // accesses of at most 16 bytes per lane
-                    int const e = row_of(ms, r) * LN + c0 + g * 16 * VW;
+                    int const e = row_of(ms, r) * LN + cb + c0 + g * 16 * VW;
                     size_t const off = size_t(y) * 2 * P + e;
                     R yr[VW], yi[VW];
 #pragma unroll
@@ -272,7 +296,9 @@ template <typename R, int LM, int LN, int EPI> struct MfmaFamily {
             // unconditional (clamped) operand prefetch where a strip has at least 8 slices per block product (LM >= 32)
             constexpr bool canClamp = (LM >= 32);
             static int const use_clamp = lab_switch("TFQMRGPU_CLAMP", 1);
-            variant<true>(m3, [&](auto M3) { variant<canHash>(a.hashV3, [&](auto H) { variant<pre>(use_pre, [&](auto PRE) { variant<canClamp>(use_clamp, [&](auto CLAMP) {
+            // (the shapes of the stand-alone multiply alone, TFQ_MULTIPLY_SIZES, have the four-product form only)
+            constexpr bool canM3 = solver_shape(LM, LN);
+            variant<canM3>(m3, [&](auto M3) { variant<canHash>(a.hashV3, [&](auto H) { variant<pre>(use_pre, [&](auto PRE) { variant<canClamp>(use_clamp, [&](auto CLAMP) {
                 k_spmm_mfma<R, LM, LN, EPI, PRE, M3, H, CLAMP><<<dim3(nWG), dim3(256), 0, s>>>(a); }); }); }); });
         }
     }
@@ -280,6 +306,117 @@ template <typename R, int LM, int LN, int EPI> struct MfmaFamily {
 
 bool spmm_mfma(SpmmKernel k, bool dbl, int lm, int ln, int epi, SpmmArgs const& a, uint32_t nWG, hipStream_t s) {
     return spmm_switch<MfmaFamily>(k, dbl, lm, ln, epi, a, nWG, s);
+}
+
+bool spmm_mfma_wide(bool dbl, int lm, int ln, SpmmArgs const& a, uint32_t nWG, hipStream_t s) {
+#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: if (nWG) MfmaFamily<R, LM, LN, EPI_NONE>::go(SpmmKernel::mfma, a, nWG, s); return true;
+    if (dbl) { switch (lm * 1000 + ln) { TFQ_MULTIPLY_SIZES(TFQ_CASE, double) default: return false; } }
+    else     { switch (lm * 1000 + ln) { TFQ_MULTIPLY_SIZES(TFQ_CASE, float)  default: return false; } }
+#undef TFQ_CASE
+}
+
+// ---------------------------------------------------------------------------------------------------
+// k_spmm_mfma_m: the precision `m` of the stand-alone multiply, the reference's gemmNxNf<float, LM, LN, NA, double> (float data, sums in
+// double, tfqmrgpu_blockmult.hxx:28,62-77,88).  k_spmm_mfma's plain mode with float operands and double accumulators: the operands move
+// as in the `c` instance (ColMap<float>: 16-byte column accesses), are widened in registers (Slice::mma_f64) and summed by
+// v_mfma_f64_16x16x4_f64 in the order of the `z` instance; each Y element is rounded to float once, when it is stored.  Row tiles per wave
+// and column split as `z` (the accumulators are double), so that a prepared order (tfqmrgpuExt_multiplyPrepare) counts the same units.
+template <int LM, int LN, bool CLAMP>
+__global__ __launch_bounds__(256, 2) void k_spmm_mfma_m(SpmmArgs a) {   // at least 2 waves per SIMD: 256 VGPRs at most
+    static_assert(LM % 16 == 0 && LN % 16 == 0, "MFMA tiles are 16 x 16");
+    using R = float;
+    constexpr int CS = mfma_col_split(8, LN);
+    constexpr int P = LM * LN, MT = LM / 16, NT = LN / (16 * CS);
+    constexpr int MS = RowTiles<double, MT, NT>::MS;
+    constexpr int MU = MT / MS;
+    constexpr int KSL = (MS * NT >= 4) ? 2 : 4;
+    constexpr int SPP = LM / (4 * KSL);
+    constexpr int VW = ColMap<R, NT>::VW, NG = ColMap<R, NT>::NG;
+    constexpr bool STREAM = EpiOps<R, EPI_NONE, VW>::STREAM;
+    using T4 = Acc<double>::T;
+    int const lane = threadIdx.x & 63;
+    int const wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int const lr = lane >> 4, lc = lane & 15;
+    int const c0 = lc * VW;
+    uint32_t const chunk = a.plainPer ? (blockIdx.x & 7u) * a.plainPer + (blockIdx.x >> 3) : blockIdx.x;
+    uint32_t const first = min(chunk * a.CH, a.nY), last = min(first + a.CH, a.nY);
+    uint32_t const nUnits = (last - first) * MU * CS;
+    using CU32 = __attribute__((address_space(4))) uint32_t const*;
+    CU32 const yOrder = (CU32)(uintptr_t)a.yOrder;
+    CU32 const cstarts = (CU32)(uintptr_t)a.starts; CU32 const cpairs = (CU32)(uintptr_t)a.pairs;
+    for (uint32_t u = wave; u < nUnits; u += 4) {
+        uint32_t const y = a.yOrder ? yOrder[first + u / (MU * CS)] : first + u / (MU * CS);
+        int const i0 = int((u / CS) % MU) * 16 * MS;
+        int const cb = int(u % CS) * (LN / CS);
+        T4 cre[MS][NT], cim[MS][NT];
+#pragma unroll
+        for (int ms = 0; ms < MS; ++ms)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) { cre[ms][nt] = T4{0, 0, 0, 0}; cim[ms][nt] = T4{0, 0, 0, 0}; }
+        uint32_t const q0 = cstarts[y];
+        uint32_t const nT = (cstarts[y + 1] - q0) * SPP;
+        R const* const A0 = (R const*)a.A + i0 + lc * MS;
+        R const* const X0 = (R const*)a.X + cb + c0;
+        auto fetch = [&](Slice<R, MS, NT, KSL>& o, uint32_t t) {
+            uint32_t const q = q0 + t / SPP;
+            int const k0 = int(t % SPP) * (4 * KSL);
+            o.template load<LM, LN>(A0 + size_t(cpairs[2 * size_t(q)]) * 2 * LM * LM,
+                                    X0 + size_t(cpairs[2 * size_t(q) + 1]) * 2 * P, k0, lr);
+        };
+        constexpr int NSET = 2;                      // the software pipeline of k_spmm_mfma
+        Slice<R, MS, NT, KSL> o[NSET];
+        if constexpr (CLAMP) {
+            if (nT > 0) {
+#pragma unroll
+                for (int i = 0; i < NSET; ++i) fetch(o[i], (uint32_t(i) < nT) ? uint32_t(i) : nT - 1);
+            }
+        } else {
+            if (nT > 0) fetch(o[0], 0);
+            if (nT > 1) fetch(o[1], 1);
+        }
+        uint32_t t = 0;
+        for (; t + NSET <= nT; t += NSET) {
+#pragma unroll
+            for (int i = 0; i < NSET; ++i) {
+                o[i].mma_f64(cre, cim);
+                uint32_t const tn = t + NSET + i;
+                if constexpr (CLAMP) fetch(o[i], (tn < nT) ? tn : nT - 1);
+                else if (tn < nT) fetch(o[i], tn);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NSET - 1; ++i) if (t + i < nT) o[i].mma_f64(cre, cim);
+
+#pragma unroll
+        for (int ms = 0; ms < MS; ++ms)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int g = 0; g < NG; ++g) {
+                    size_t const off = size_t(y) * 2 * P + (i0 + Acc<double>::row(lane, r) * MS + ms) * LN + cb + c0 + g * 16 * VW;
+                    R yr[VW], yi[VW];
+#pragma unroll
+                    for (int n = 0; n < VW; ++n) { yr[n] = R(cre[ms][g * VW + n][r]); yi[n] = R(cim[ms][g * VW + n][r]); }   // the one rounding
+                    vstore_stream<STREAM, R, VW>((R*)a.Y + off, yr); vstore_stream<STREAM, R, VW>((R*)a.Y + off + P, yi);
+                }
+    }
+}
+
+template <int LM, int LN> bool mfma_m_go(SpmmArgs const& a, uint32_t nWG, hipStream_t s) {
+    if constexpr (takes_mfma(true, LM, LN)) {
+        // the clamped prefetch of k_spmm_mfma where a strip has many slices, except 96 x 96: six column tiles of double accumulators and the
+        // widened operands of two slices need 256 VGPRs and 44 bytes of scratch there (218 VGPRs without the clamp)
+        constexpr bool canClamp = (LM >= 32 && LN != 96);
+        static int const use_clamp = lab_switch("TFQMRGPU_CLAMP", 1);
+        if (nWG) variant<canClamp>(use_clamp, [&](auto CLAMP) { k_spmm_mfma_m<LM, LN, CLAMP><<<dim3(nWG), dim3(256), 0, s>>>(a); });
+        return true;
+    } else return false;
+}
+
+bool spmm_mfma_m(int lm, int ln, SpmmArgs const& a, uint32_t nWG, hipStream_t s) {
+#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: return mfma_m_go<LM, LN>(a, nWG, s);
+    switch (lm * 1000 + ln) { TFQ_SIZES(TFQ_CASE, float) TFQ_MULTIPLY_SIZES(TFQ_CASE, float) default: return false; }
+#undef TFQ_CASE
 }
 
 } // namespace tfq
