@@ -209,6 +209,52 @@ typedef tfqmrgpuStatus_t (*tfqmrgpuOperator_t)(void *ctx, void *Y_d, void const 
     tfqmrgpuStream_t stream, double *flops);
 tfqmrgpuStatus_t tfqmrgpuExt_setOperator(tfqmrgpuBsrsvPlan_t plan, tfqmrgpuOperator_t multiply, void *ctx);
 
+/* ---- (7) preconditioner ------------------------------------------------------------------ */
+/* The reference has the hook and never filled it (has_preconditioner() returns false, tfqmrgpu_blocksparse.hxx:68,79;
+ * tfqmrgpu_core.hxx:37,57).  Here: block Jacobi applied from the RIGHT.  With M = blockdiag(A) the solver iterates on
+ * (A M^-1) Y = B and returns X = M^-1 Y.  A M^-1 has the block pattern of A (block (i,j) becomes A_ij M_jj^-1) and M^-1 Y the
+ * pattern of Y (block (i,c) becomes M_ii^-1 Y_ic), so the truncation of every product to the pattern of X
+ * commutes with it: the truncated problem that is solved is exactly the caller's.  The residual B - (A M^-1) Y equals B - A X:
+ * `threshold`, the bound history and getInfo's residuum_reached keep their meaning.  It costs nothing per iteration.
+ *
+ * setPreconditioner: kind NONE (the default) or BLOCK_JACOBI; any other kind returns TFQMRGPU_UNDOCUMENTED_ERROR.  Call it after
+ *   bufferSize; it takes effect at the next solve.  A plan that never calls it, or sets NONE, behaves bit for bit as without this
+ *   section: same buffer size, same launches, same results.
+ * setMatrix('A') marks the preconditioner stale.  The first solve after it inverts the diagonal blocks (Gauss-Jordan with row
+ *   exchanges, double arithmetic in every precision) and scales A IN PLACE in the buffer; later solves of the same A (new B) reuse
+ *   both.  M^-1 lives in device memory that the library owns, allocated at the first preconditioned solve and released by destroyPlan;
+ *   bufferSize and the buffer layout do not change.
+ * Switching the kind after A has been scaled needs a fresh setMatrix('A'): until then solve returns TFQMRGPU_UNDOCUMENTED_ERROR
+ *   with the key character 'A' (status = 14 + 1000 * line + 10^7 * 'A') instead of solving with a half-scaled operator.  The same
+ *   status when A has never been set.
+ * A block row without a diagonal block in the pattern of A, or whose diagonal block is singular (a pivot that is zero or not
+ *   finite; pivots are chosen by max(|Re|, |Im|)) or whose inverse is not finite in the precision it is stored in, gets M_ii = 1;
+ *   the solve runs all the same.  M^-1 never holds anything but finite numbers.
+ * getMatrix('X') and tfqmrgpuExt_getWorkVector(.., 1, ..) return X, not Y: the back transform runs at the end of solve, on the
+ *   solver's stream, also when the solve ends at maxIterations or in a breakdown.  The other work vectors (4 ... 9) are those of the
+ *   scaled system.  tfqmrgpuExt_applyOperator on such a plan multiplies with what is in the buffer: A M^-1 once a solve (or
+ *   getPreconditioner) has scaled A, the caller's A before.  The caller's A itself is not kept: whoever reads the A window of the
+ *   buffer directly finds A M^-1 there (getMatrix hands out X only, as in the reference).  setBuffer starts afresh: the new buffer
+ *   holds no A, so setMatrix('A') has to follow it and is inverted and scaled at the next solve; bufferSize does the same.
+ * Precisions 'z', 'c' and 'm'.  'm': both copies of A (double and float) are scaled, M^-1 is kept in double and the back transform
+ *   is applied once, in double, to the refined solution.
+ * A plan with a user-defined operator (section 5) refuses: solve returns TFQMRGPU_NO_IMPLEMENTATION, on several ranks through the
+ *   vote in front of the solve, so that all ranks leave together.
+ *   With kind NONE such a plan solves whatever state the A in the buffer is in: the operator never reads it.
+ * Several ranks (section 4): every rank holds all of A and computes the same M^-1; the back transform is local to a rank's block
+ *   columns.  X does not depend on the number of ranks.
+ * getInfo: iterations and residual as always; flops_performed includes the back transform, 8 LM LM LN nnzbX; the set-up is not
+ *   counted (it belongs to setMatrix('A')).
+ * getPreconditioner: M^-1 as the solver uses it, to host memory, [mb][2][LM][LM] (Re plane, Im plane, row-major), in the plan's
+ *   precision ('m': double), and the number of block rows whose M_ii is the unit matrix.  Either pointer may be NULL.  Needs kind
+ *   BLOCK_JACOBI (else TFQMRGPU_UNDOCUMENTED_ERROR); called between setMatrix('A') and the first solve it performs the set-up
+ *   itself, so that the solve finds it done. */
+enum { TFQMRGPU_PRECOND_NONE = 0, TFQMRGPU_PRECOND_BLOCK_JACOBI = 1 };
+tfqmrgpuStatus_t tfqmrgpuExt_setPreconditioner(tfqmrgpuBsrsvPlan_t plan, int kind);
+tfqmrgpuStatus_t tfqmrgpuExt_getPreconditioner(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+                                               void *Minv /* host, [mb][2][LM][LM], plan precision ('m': double) */,
+                                               int32_t *nIdentity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ LAB_LIB_PATH = os.path.join(_HERE, "lib", "libtfQMRgpu_lab.so")   # the same sou
 
 LAYOUT_RRRRIIII, LAYOUT_RRIIRRII, LAYOUT_RIRIRIRI = 0x0F, 0x33, 0x55
 SHADOW_HASH, SHADOW_GLIBC_RAND = 0, 1
+PRECOND_NONE, PRECOND_BLOCK_JACOBI = 0, 1
 CODE_LINE, CODE_CHAR = 1000, 10000 * 1000
 
 EXPORTED_SYMBOLS = [  # include/tfqmrgpu.h
@@ -38,6 +39,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_freeShard", "tfqmrgpuExt_commUniqueId", "tfqmrgpuExt_commInit",
     "tfqmrgpuExt_commDestroy", "tfqmrgpuExt_setReduceCallback", "tfqmrgpuExt_setOperator",
     "tfqmrgpuExt_getRefinementHistory", "tfqmrgpuExt_setThreeProductMultiply",
+    "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -135,6 +137,8 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_setOperator.argtypes = [P, OPERATOR_CB, P]
     lib.tfqmrgpuExt_getRefinementHistory.argtypes = [P, P, P, C.c_int32]
     lib.tfqmrgpuExt_setThreeProductMultiply.argtypes = [P, I]
+    lib.tfqmrgpuExt_setPreconditioner.argtypes = [P, I]
+    lib.tfqmrgpuExt_getPreconditioner.argtypes = [P, P, P, C.POINTER(C.c_int32)]
     return lib
 
 
@@ -342,6 +346,18 @@ class Solver:
     def set_three_product_multiply(self, on=True):
         _check(lib.tfqmrgpuExt_setThreeProductMultiply(self.plan, int(on)), "tfqmrgpuExt_setThreeProductMultiply")
 
+    def set_preconditioner(self, kind=PRECOND_BLOCK_JACOBI):
+        """tfqmrgpu_ext.h section 7: PRECOND_NONE or PRECOND_BLOCK_JACOBI (applied from the right); call after buffer_size"""
+        _check(lib.tfqmrgpuExt_setPreconditioner(self.plan, int(kind)), "tfqmrgpuExt_setPreconditioner")
+
+    def get_preconditioner(self, values=True):
+        """(M^-1 as complex [mb, LM, LM] -- None with values=False --, number of block rows whose M_ii is the unit matrix); between
+        set_matrix('A') and the first solve this call performs the set-up (inversion and scaling of A) itself"""
+        n = C.c_int32(0)
+        m = np.zeros((self.problem.mb, 2, self.LM, self.LM), dtype=np.float32 if self.precision == "c" else np.float64) if values else None
+        _check(lib.tfqmrgpuExt_getPreconditioner(self.handle, self.plan, _ptr(m) if values else None, C.byref(n)), "tfqmrgpuExt_getPreconditioner")
+        return (m[:, 0].astype(np.float64) + 1j * m[:, 1]) if values else None, int(n.value)
+
     def bound_history(self):
         n = lib.tfqmrgpuExt_getBoundHistory(self.plan, None, 0)
         h = np.zeros(max(n, 0), dtype=np.float64)
@@ -407,8 +423,9 @@ def hash_shadow_vector(pr):
 
 
 def solve_problem(pr, precision="z", threshold=None, max_iterations=2000, transA="n", shadow_mode=SHADOW_HASH, stream=None,
-                  data_precision=None, three_products=False):
-    """createPlan .. getMatrix in one go; returns (status, X[nnzbX, LM, LN] complex, info dict)."""
+                  data_precision=None, three_products=False, preconditioner=PRECOND_NONE):
+    """createPlan .. getMatrix in one go; returns (status, X[nnzbX, LM, LN] complex, info dict).
+    preconditioner=PRECOND_BLOCK_JACOBI: info["n_identity"] = block rows whose M_ii is the unit matrix."""
     with Solver(stream) as s:
         s.create_plan(pr)
         nbytes = s.buffer_size(pr.LM, pr.LN, precision)
@@ -416,12 +433,16 @@ def solve_problem(pr, precision="z", threshold=None, max_iterations=2000, transA
             s.data_precision = data_precision
         if three_products:
             s.set_three_product_multiply(True)
+        if preconditioner != PRECOND_NONE:
+            s.set_preconditioner(preconditioner)
         s.set_shadow_mode(shadow_mode)
         s.set_buffer(nbytes=nbytes)
         s.set_matrix("A", pr.A, transA)
         s.set_matrix("B", pr.B, "n")
         status = s.solve(pr.tolerance if threshold is None else threshold, max_iterations)
         info = s.get_info()
+        if preconditioner != PRECOND_NONE:
+            info["n_identity"] = s.get_preconditioner(values=False)[1]
         info["bound_history"] = s.bound_history()
         info["refinement_history"] = s.refinement_history()
         info["buffer_bytes"] = nbytes

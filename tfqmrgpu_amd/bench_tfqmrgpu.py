@@ -7,9 +7,11 @@ arguments and result lines, running on this library through its C-ABI:
       (bench_tfqmrgpu.cu:456-498), cos/sin fill (:274-287), host re-computation check maxdev <= 1e-4 (:349-420)
   python -m tfqmrgpu_amd.bench_tfqmrgpu tfQMR <problem.xml> [precision=z] [nrep=1] [MaxIter=2000]
       solves the <LinearProblem> through the staged API with trans 'n' (row-major XML blocks, see DESIGN.md on the
-      reference's 't'), compares with the stored X if the file has one (:178-205)
+      reference's 't'), compares with the stored X if the file has one (:178-205); BENCH_PRECOND=1 in the environment switches the
+      block-Jacobi right preconditioner on (not in the reference; without it the output is unchanged)
 """
 import gzip
+import os
 import sys
 import time
 
@@ -123,6 +125,9 @@ def tfqmr(argv):
         if prec == "m":
             s.data_precision = "c"
         print("# use %.6f GByte GPU memory" % (nbytes * 1e-9))
+        if int(os.environ.get("BENCH_PRECOND", "0") or 0) > 0:   # not in the reference: the block-Jacobi right preconditioner (tfqmrgpu_ext.h section 7)
+            s.set_preconditioner(T.PRECOND_BLOCK_JACOBI)
+            print("# block-Jacobi right preconditioner: on (set-up at the first solve, inside the timed region)")
         s.set_buffer(nbytes=nbytes)
         s.set_matrix("A", pr.A, "n")
         s.set_matrix("B", pr.B, "n")

@@ -14,6 +14,7 @@
 #include "tfq_order.hpp"
 #include "tfq_vec.hpp"
 #include "tfq_switch.hpp"
+#include "tfq_precond.hpp"
 
 using namespace tfq;
 
@@ -471,6 +472,71 @@ struct FlopModel {
     double solve(Ctl const& c) const { return fNrm + c.iteration * (2 * fMult + 2 * fDot + 2 * fNrm + 10 * fAxp) + c.nprobes * (fMult + fNrm); }
 };
 
+// ---- block-Jacobi right preconditioner (tfqmrgpu_ext.h section 7; kernels: tfq_precond.hip) ------------------------------------------
+// With M = blockdiag(A) the iteration runs on (A M^-1) Y = B: A M^-1 has the pattern of A and takes its place in the buffer, once per
+// setMatrix('A'); X = M^-1 Y has the pattern of Y and is formed in place at the end of a solve.  No iteration kernel knows about it.
+struct PrecondMem { char* minv; uint32_t* diag; uint32_t* colA; uint32_t* counter; size_t minvBytes, bytes; };
+static PrecondMem precond_mem(Plan const& p) {
+    size_t const real = ('c' == p.precision) ? 4 : 8;       // M^-1 in the plan's precision, double for 'm'
+    PrecondMem m{};
+    m.minvBytes = size_t(p.nRows) * 2 * p.LM * p.LM * real;
+    char* q = p.precond;
+    m.minv = q;              q += align256(m.minvBytes);
+    m.diag = (uint32_t*)q;   q += align256(size_t(p.nRows) * 4);
+    m.colA = (uint32_t*)q;   q += align256(size_t(p.nnzbA) * 4);
+    m.counter = (uint32_t*)q; q += 256;
+    m.bytes = size_t(q - p.precond);
+    return m;
+}
+
+// what a solve needs before its first iteration: nothing when the preconditioner is off; otherwise M^-1 and the scaled A, made here
+// when the A in the buffer is still the caller's (the first solve after setMatrix('A')) and reused by every later solve of that A
+static tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p) {
+    if (TFQMRGPU_PRECOND_NONE == p.precondKind && TFQMRGPU_PRECOND_NONE == p.precondInA) return TFQMRGPU_STATUS_SUCCESS;
+    if (p.opFn) {   // a user-defined operator has no blocks to scale -- and never reads the A in the buffer, scaled or not
+        return (TFQMRGPU_PRECOND_NONE != p.precondKind) ? TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION) : TFQMRGPU_STATUS_SUCCESS;
+    }
+    if (p.precondInA == p.precondKind) return TFQMRGPU_STATUS_SUCCESS;
+    // the kind has changed since A was scaled: only a fresh setMatrix('A') brings the caller's A back
+    if (TFQMRGPU_PRECOND_NONE != p.precondInA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+    if (!p.buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (!p.haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+    hipStream_t const s = (hipStream_t)h.stream;
+    if (!p.precond) {
+        size_t const bytes = precond_mem(p).bytes;          // (offsets only: p.precond is null)
+        TFQ_HIP(hipMalloc((void**)&p.precond, bytes), TFQMRGPU_STATUS_ALLOCATION_FAILED)
+        auto const m = precond_mem(p);
+        TFQ_HIP(hipMemcpyAsync(m.diag, p.diagOfRow.data(), p.diagOfRow.size() * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        if (p.nnzbA) TFQ_HIP(hipMemcpyAsync(m.colA, p.colOfA.data(), p.colOfA.size() * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    }
+    auto const m = precond_mem(p);
+    bool const mixed = ('m' == p.precision), wDbl = ('c' != p.precision);
+    DevPlan const d = mixed ? resolveZ(p) : resolve(p);      // mixed: M^-1 comes from the double copy of A
+    TFQ_HIP(hipMemsetAsync(m.counter, 0, 4, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    launch_precond_invert(d.dbl, wDbl, d.A, m.diag, m.minv, m.counter, p.nRows, p.LM, d.ilv, s);
+    // A_ij := A_ij M_jj^-1; the blocks are stored transposed, so this is block := (M_jj^-1)^T block
+    launch_precond_apply(d.dbl, wDbl, true, d.A, p.nnzbA, m.colA, m.minv, p.LM, p.LM, d.ilv, s);
+    if (mixed) launch_precond_apply(false, true, true, p.buffer + p.wA.offset, p.nnzbA, m.colA, m.minv, p.LM, p.LM, p.ilv, s);   // the float copy of the inner solves
+    uint32_t n = 0;
+    TFQ_HIP(hipMemcpyAsync(&n, m.counter, 4, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    p.precondIdentity = int32_t(n);
+    p.precondInA = p.precondKind;
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// X := M^-1 Y at the end of a solve, on the solver's stream ('m': once, in double, on the refined solution)
+static tfqmrgpuStatus_t precond_back(Handle& h, Plan& p) {
+    if (TFQMRGPU_PRECOND_BLOCK_JACOBI != p.precondInA) return TFQMRGPU_STATUS_SUCCESS;
+    auto const m = precond_mem(p);
+    DevPlan const d = ('m' == p.precision) ? resolveZ(p) : resolve(p);
+    launch_precond_apply(d.dbl, 'c' != p.precision, false, d.x, p.nnzbX, d.rowI, m.minv, p.LM, p.LN, d.ilv, (hipStream_t)h.stream);
+    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    p.flops_performed += 8. * p.LM * p.LM * p.LN * p.nnzbX;
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
 // Mixed precision 'm' (reference: dormant, tfqmrgpu.cu:42 "load float, multiply-accumulate double, store float"; documented as
 // "start with float and converge double", tfqmrgpu.h:72).  Iterative refinement: x, B, A in double; per cycle r = b - A x in double,
 // A d = r solved by the complex<float> tfQMR (its kernels unchanged; the right-hand side is the X-shaped R), x += d in double.  The
@@ -498,6 +564,7 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt) {
     };
     if (!p.buffer)  return leave_marked(TFQ_ERR(TFQMRGPU_POINTER_INVALID));
     if (p.opFn)     return leave_marked(TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION));  // user-defined operators: 'z' and 'c' only
+    if (auto const st = precond_prepare(h, p)) return leave_marked(st);
     DevPlan const d = resolve(p), dz = resolveZ(p);
     FlopModel const fm(p);
     RefineArgs a{};
@@ -597,6 +664,7 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt) {
         launch_refine_update(a, s);
         p.flops_performed += 2. * p.nnzbX * p.LM * p.LN;
     }
+    if (auto const st = precond_back(h, p)) return st;   // (every rank gets here: errors that one rank alone could see have left above, behind a collective)
     TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
     p.flops_performed_all += p.flops_performed;
     p.residuum_reached = std::sqrt(std::max(res2, 1.4e-76 * 1.4e-76));
@@ -613,12 +681,14 @@ static tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt) {
     tfqmrgpuStatus_t early = TFQMRGPU_STATUS_SUCCESS;
     if (!p.buffer) early = TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     else if ('z' != p.precision && 'c' != p.precision) early = err(TFQMRGPU_PRECISION_MISSMATCH, __LINE__ % 10000, p.precision);
+    if (!early) early = precond_prepare(h, p);   // (off: returns at once; a refusal travels through the ranks' vote like the others)
     SolveOutcome o;
     if (auto const st = run_tfqmr(h, p, early ? DevPlan{} : resolve(p), tol, maxIt, early, 1., o)) return st;
     Ctl const& last = o.last;
     FlopModel const fm(p);
     p.flops_performed = fm.solve(last);
     if (p.opFn) p.flops_performed += o.userFlops - (2. * last.iteration + last.nprobes) * fm.fMult;  // the operator's own count
+    if (auto const st = precond_back(h, p)) return st;   // X := M^-1 Y, also when the solve ended at maxIterations or in a breakdown
     p.flops_performed_all += p.flops_performed;
     p.residuum_reached = std::sqrt(last.residual2_reached);
     p.iterations_needed = (1 == last.state) ? last.iterations_needed : maxIt;
@@ -718,6 +788,17 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_createPlan(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
                      bsrRowPtrB, nnzbB, bsrColIndB, indexOffset, echo);
     } catch (std::bad_alloc const&) { st = TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     if (st) { delete p; return st; }   // (the reference leaks the plan on its error paths)
+    try {   // for the block-Jacobi preconditioner (tfqmrgpu_ext.h section 7): where the diagonal blocks of A are, and the block column of every block
+        p->diagOfRow.assign(size_t(mb), ~0u);
+        p->colOfA.resize(size_t(nnzbA));
+        for (int r = 0; r < mb; ++r) {
+            for (int32_t q = bsrRowPtrA[r] - indexOffset; q < bsrRowPtrA[r + 1] - indexOffset; ++q) {
+                auto const col = uint32_t(bsrColIndA[q] - indexOffset);
+                p->colOfA[q] = col;
+                if (col == uint32_t(r) && ~0u == p->diagOfRow[r]) p->diagOfRow[r] = uint32_t(q);
+            }
+        }
+    } catch (std::bad_alloc const&) { delete p; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     *plan = (tfqmrgpuBsrsvPlan_t)p;
     return TFQMRGPU_STATUS_SUCCESS;
 }
@@ -728,6 +809,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_destroyPlan(tfqmrgpuHandle_t handle, tfqmrgpuBsr
     if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     if (p->ring) { (void)hipHostFree(p->ring); for (auto e : p->ringEvent) (void)hipEventDestroy((hipEvent_t)e); }
     if (p->opScratch) (void)hipFree(p->opScratch);
+    if (p->precond) (void)hipFree(p->precond);
     p->magic = 0;
     delete p;
     return TFQMRGPU_STATUS_SUCCESS;
@@ -757,6 +839,8 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     try { st = layoutBuffer(*p, LM, LN, prec); }
     catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     if (p->opScratch) { (void)hipFree(p->opScratch); p->opScratch = nullptr; }   // sized for the previous block shape
+    if (p->precond) { (void)hipFree(p->precond); p->precond = nullptr; }         // likewise
+    p->precondInA = TFQMRGPU_PRECOND_NONE; p->haveA = false;                     // (the A of the new layout has not been set)
     p->precision = prec;
     p->buffer = nullptr;
     *pBufferSizeInBytes = p->bufferBytes;
@@ -771,6 +855,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);        // bufferSize has not been called
     hipStream_t const s = (hipStream_t)h->stream;
     p->buffer = (char*)pBuffer;
+    p->precondInA = TFQMRGPU_PRECOND_NONE; p->haveA = false;   // this buffer holds no A yet, scaled or not (tfqmrgpu_ext.h section 7)
     auto at = [&](Window const& w) { return (void*)(p->buffer + w.offset); };
     auto up = [&](Window const& w, void const* src, size_t bytes) { return upload(at(w), src, bytes, s); };
     tfqmrgpuStatus_t st;
@@ -872,6 +957,7 @@ static tfqmrgpuStatus_t set_or_get(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t 
     auto const st = transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, nnzb, nR, nC, layout, trans, conj, nullptr,
                                     (mixed && 0 == which && !is_get) ? &floatA : nullptr);
     if (!st && 1 == which) p->haveB = true;
+    if (0 == which && !is_get) { p->haveA = !st; p->precondInA = TFQMRGPU_PRECOND_NONE; }   // a new A: not scaled, the preconditioner of the last one is stale
     return st;
 }
 
@@ -1207,6 +1293,29 @@ tfqmrgpuStatus_t tfqmrgpuExt_setOperator(tfqmrgpuBsrsvPlan_t plan, tfqmrgpuOpera
     auto p = asPlan(plan);
     if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     p->opFn = (void*)multiply; p->opCtx = ctx;
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_setPreconditioner(tfqmrgpuBsrsvPlan_t plan, int kind) {
+    auto p = asPlan(plan);
+    if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (TFQMRGPU_PRECOND_NONE != kind && TFQMRGPU_PRECOND_BLOCK_JACOBI != kind) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
+    p->precondKind = kind;
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_getPreconditioner(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, void* Minv, int32_t* nIdentity) {
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (TFQMRGPU_PRECOND_BLOCK_JACOBI != p->precondKind) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
+    if (auto const st = precond_prepare(*h, *p)) return st;   // (the first solve after setMatrix('A') would do the same)
+    if (Minv) {
+        auto const m = precond_mem(*p);
+        hipStream_t const s = (hipStream_t)h->stream;
+        TFQ_HIP(hipMemcpyAsync(Minv, m.minv, m.minvBytes, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    }
+    if (nIdentity) *nIdentity = p->precondIdentity;
     return TFQMRGPU_STATUS_SUCCESS;
 }
 

@@ -118,6 +118,14 @@ struct Plan {
     // [xu | yu | i2u | colindx in the caller's block order]
     void* opFn = nullptr; void* opCtx = nullptr;
     char* opScratch = nullptr;
+    // block-Jacobi right preconditioner (tfqmrgpu_ext.h section 7)
+    std::vector<uint32_t> diagOfRow;   // [nRows] the diagonal block of each block row of A, ~0u: the pattern has none
+    std::vector<uint32_t> colOfA;      // [nnzbA] block column of each block of A
+    int precondKind = TFQMRGPU_PRECOND_NONE;     // what the caller asked for
+    int precondInA = TFQMRGPU_PRECOND_NONE;      // what the A in the buffer has been scaled with (NONE: it is the caller's A)
+    bool haveA = false;
+    int32_t precondIdentity = 0;       // block rows whose M_ii is the unit matrix (no diagonal block, or a singular one)
+    char* precond = nullptr;           // library-owned device memory [M^-1 | diagOfRow | colOfA | counter], allocated at the first preconditioned solve
 
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;
