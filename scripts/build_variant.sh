@@ -7,7 +7,11 @@ set -e
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)
 csrc=$root/tfqmrgpu_amd/csrc
-srcs="$csrc/tfq_spmm.hip $csrc/tfq_spmm_mfma.hip $csrc/tfq_spmm_ilv16.hip $csrc/tfq_spmm_ilv8.hip $csrc/tfq_spmm_rows4.hip"
+# the source lists are the Makefile's: tfq_spmm*.hip is the multiply, everything else is linked from the regular (or lab) objects
+srcs=""; others=""
+for f in $(make -s -C $csrc print-HIPSRC print-CXXSRC); do
+    case $f in tfq_spmm*.hip) srcs="$srcs $csrc/$f";; *) others="$others ${f%.*}";; esac
+done
 [ -n "$SPMM_SRC" ] && srcs=$SPMM_SRC
 # timing-only variants (-DTFQ_PROBE=..., -DTFQ_LAB_CLOCK, -DTFQ_LAB_STAMPS, -DTFQ_B8_DEPTH=...) exist only in the lab copy of the multiply, one monolithic
 # source (r04: the product sources carry none of them)
@@ -26,7 +30,7 @@ for src in $srcs; do
 done
 for p in $pids; do wait $p; done
 objs=""
-for o in tfq_api tfq_vec tfq_layout tfq_plan tfq_shard tfq_error tfq_order; do objs="$objs $objdir/$o.o"; done
+for o in $others; do objs="$objs $objdir/$o.o"; done
 objs="$objs $root/tfqmrgpu_amd/lib/obj/tfq_fortran.o"
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $root/scripts/bin/libtfQMRgpu_$name.so $vdir/*.o $objs -Wl,-soname,libtfQMRgpu.so.1 -ldl
 rm -rf $vdir

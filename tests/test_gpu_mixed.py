@@ -1,5 +1,5 @@
 """Mixed precision 'm' (reference: dormant, tfqmrgpu.cu:42, tfqmrgpu.h:72 "start with float and converge double").
-The product runs complex<float> tfQMR solves inside an iterative refinement in double (tfq_api.hip: run_mixed); the oracle has no
+The product runs complex<float> tfQMR solves inside an iterative refinement in double (tfq_solve.cpp: run_mixed); the oracle has no
 such mode, so the checks are against the oracle's complex<double> solution of the same system and against A x = b itself:
   * the solve converges to the DOUBLE threshold (1e-9), far past the float floor (4.6e-5 on the FD fixture);
   * X is within 1e-6 max|X| of the oracle's 'z' solution (observed: 1e-10 ... 1e-8);

@@ -37,8 +37,29 @@ CASES = [("fd_16x16_small", "z"), ("fd_16x16_small", "c"), ("julia_kat", "z"), (
          ("dense_random_rect", "z"), ("st32x32", "c")]    # st32x32: the quad-interleaved 32 x 32 complex<float> plan (k_spmm_ilvf)
 
 
+PROFILE_CASE = "fd_16x16_small"
+
+
 def _problem(name):
     return PR.stencil_2d(6, 6, 32, 32, 2, seed=3) if name == "st32x32" else load_problem(name)
+
+
+def _builtin_as_operator(torch, s, pr, prec, view, seen):
+    """a callback that computes the same block-sparse product with tfqmrgpuExt_multiply on the caller's block order;
+    seen: gets one record of what the first call was handed"""
+    An = _native_A(torch, pr, prec)
+    dS = torch.from_numpy(view["starts"].view(np.int32)).cuda()
+    dP = torch.from_numpy(view["pairs"].view(np.int32)).cuda()
+    colindx = view["colindx"].copy()
+
+    def multiply(y, x, cols, nnzbX, nCols, lm, ln, precision, stream):
+        if not seen:                       # what the reference hands to action_t::multiply
+            got = torch.as_tensor(_DevArray(cols, (nnzbX,), "<u2"), device="cuda").cpu().numpy()
+            seen.append((np.array_equal(got, colindx), nnzbX, nCols, lm, ln, precision))
+        T._check(T.lib.tfqmrgpuExt_multiply(s.handle, precision.encode(), lm, ln, nnzbX, dS.data_ptr(), dP.data_ptr(),
+                                            An.data_ptr(), x, y), "tfqmrgpuExt_multiply")
+        return view["nPairs"] * 8.0 * lm * lm * ln
+    return multiply
 
 
 @pytest.mark.parametrize("name,prec", CASES)
@@ -55,21 +76,8 @@ def test_operator_that_repeats_the_builtin_multiply(torch_cuda, name, prec):
         s.set_buffer(nbytes=s.buffer_size(pr.LM, pr.LN, prec))
         s.set_matrix("A", 0 * pr.A)            # the values of the built-in operator are not used
         s.set_matrix("B", pr.B)
-        An = _native_A(torch, pr, prec)
-        dS = torch.from_numpy(view["starts"].view(np.int32)).cuda()
-        dP = torch.from_numpy(view["pairs"].view(np.int32)).cuda()
-        colindx = view["colindx"].copy()
         seen = []
-
-        def multiply(y, x, cols, nnzbX, nCols, lm, ln, precision, stream):
-            if not seen:                       # what the reference hands to action_t::multiply
-                got = torch.as_tensor(_DevArray(cols, (nnzbX,), "<u2"), device="cuda").cpu().numpy()
-                seen.append((np.array_equal(got, colindx), nnzbX, nCols, lm, ln, precision))
-            T._check(T.lib.tfqmrgpuExt_multiply(s.handle, precision.encode(), lm, ln, nnzbX, dS.data_ptr(), dP.data_ptr(),
-                                                An.data_ptr(), x, y), "tfqmrgpuExt_multiply")
-            return view["nPairs"] * 8.0 * lm * lm * ln
-
-        s.set_operator(multiply)
+        s.set_operator(_builtin_as_operator(torch, s, pr, prec, view, seen))
         st = s.solve(tol, 2000)
         info, X = s.get_info(), s.get_matrix()
         assert seen == [(True, pr.nnzbX, view["nCols"], pr.LM, pr.LN, prec)]
@@ -84,6 +92,32 @@ def test_operator_that_repeats_the_builtin_multiply(torch_cuda, name, prec):
         s.set_matrix("A", pr.A)
         assert s.solve(tol, 2000) == 0
         assert s.get_info()["iterations"] == info0["iterations"] and np.array_equal(s.get_matrix(), X0)
+
+
+def test_profile_counts_the_probes_of_an_operator_solve_like_the_builtin_ones(torch_cuda):
+    """tfqmrgpuExt_setProfiling under a user-defined operator: every class has one working launch per iteration, the probe class one
+    per probe that ran -- the same numbers as the same solve with the built-in multiply"""
+    torch = torch_cuda
+    pr = _problem(PROFILE_CASE)
+    with T.Solver() as s:
+        s.create_plan(pr)
+        view = s.plan_view()
+        s.set_buffer(nbytes=s.buffer_size(pr.LM, pr.LN, "z"))
+        s.set_matrix("A", pr.A)
+        s.set_matrix("B", pr.B)
+        s.set_profiling(1)
+        assert s.solve(pr.tolerance, 2000) == 0
+        it0, builtin = s.get_info()["iterations"], s.profile()
+        s.set_operator(_builtin_as_operator(torch, s, pr, "z", view, []))
+        assert s.solve(pr.tolerance, 2000) == 0
+        it1, through = s.get_info()["iterations"], s.profile()
+    print("iterations", it0, it1, "probes", builtin["probe"][0], through["probe"][0])
+    assert it0 == it1
+    assert builtin["probe"][0] < it0            # otherwise "one per probe" and "one per iteration" could not be told apart
+    for k in T.Solver.PROFILE_CLASSES:
+        if k != "probe":
+            assert builtin[k][0] == through[k][0] == it0, k
+    assert builtin["probe"][0] == through["probe"][0]
 
 
 def test_matrix_free_operator(torch_cuda):

@@ -413,6 +413,26 @@ def test_reduce_paths_single_rank(torch_cuda):
         assert T.lib.tfqmrgpuExt_commDestroy(s.handle) == 0
 
 
+def test_profile_with_a_reduce_callback(torch_cuda):
+    # the several-ranks form of the iteration slot (decide | reduce | decide) under profiling: the events change no result,
+    # and every class is launched once per iteration
+    pr = load_problem("fd_16x16_small")
+    with T.Solver() as s:
+        s.create_plan(pr)
+        s.set_buffer(nbytes=s.buffer_size(16, 16, "z"))
+        s.set_matrix("A", pr.A)
+        s.set_matrix("B", pr.B)
+        keep = T.REDUCE_CB(lambda ctx, values, n: None)
+        assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, keep, None) == 0
+        assert s.solve(pr.tolerance, 2000) == 0
+        it, X = s.get_info()["iterations"], s.get_matrix()
+        s.set_profiling(1)
+        assert s.solve(pr.tolerance, 2000) == 0
+        assert s.get_info()["iterations"] == it and np.array_equal(s.get_matrix(), X)
+        for k, (n, ms) in s.profile().items():
+            assert n == it or k == "probe", k
+
+
 def test_large_problem_properties(torch_cuda, oracle):
     # size-independent checks at a size the oracle cannot solve in seconds: the solution must satisfy
     # A*X == B on the pattern (checked with the device multiply, itself checked above), and the

@@ -72,6 +72,7 @@ struct DevPlan {
 };
 
 DevPlan resolve(Plan const& p);
+DevPlan resolveZ(Plan const& p) __attribute__((visibility("hidden")));   // 'm': the double-precision side as a plan of its own (tfq_api.hip)
 
 // mixed precision 'm': the double-precision side of the plan (x, B, A, the product A x) next to the float plan `d` of the inner solves
 struct RefineArgs {
@@ -128,7 +129,7 @@ __host__ __device__ inline int plane_offset(int ilv, int r, int s, int nC) { ret
 
 enum { EPI_NONE = 0, EPI_XPAY_DOT = 1, EPI_AXPY_NRM_DOT = 2, EPI_RESIDUAL = 3 };
 
-// ---- launchers (tfq_kernels*.hip); all asynchronous on `s` ---------------------------------------
+// ---- launchers (tfq_vec.hip, tfq_spmm*.hip, tfq_layout.hip); all asynchronous on `s` ---------------------------------------
 void launch_decide(DevPlan const& d, int phase, hipStream_t s); // phase 0: all, 1: reduce columns only, 2: update ctl only
 void launch_probe_decide(DevPlan const& d, int phase, hipStream_t s);
 

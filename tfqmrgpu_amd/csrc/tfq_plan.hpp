@@ -75,7 +75,7 @@ struct Plan {
 
     // ---- fixed by bufferSize -----------------------------------------------------------------
     int LM = 0, LN = 0;
-    char precision = 0;                // 'c', 'z' or 'm' (mixed: float inner iterations, double refinement; tfq_api.hip: run_mixed)
+    char precision = 0;                // 'c', 'z' or 'm' (mixed: float inner iterations, double refinement; tfq_solve.cpp: run_mixed)
     size_t realBytes = 0;              // 4 or 8 (the storage precision of the iteration vectors: 4 for 'm')
     size_t S = 0;                      // bytes of one X-shaped vector
     size_t bufferBytes = 0;
@@ -88,7 +88,7 @@ struct Plan {
     Window wRho, wAlfa, wBeta, wC67, wEta, wC67a, wEta2; // [nCols][2][LN] real
     Window wZ, wD, wTau, wVar, wInvBn2;        // double scalars per right-hand side
     Window wStatus;                            // int8 [nCols][LN]
-    Window wCtl;                               // device control block (see tfq_solver)
+    Window wCtl;                               // device control block (tfq_device.hpp: Ctl)
     Window wPz, wPd;                           // per-chunk partial sums (double)
     Window wColRec;                            // per-column stopping-test record [nCols][2] double
     Window wColPart; uint32_t colSegMax = 1;   // shares of the segment work groups of long columns (tfq_colops.hpp: column_total), segments of the longest column
