@@ -106,12 +106,7 @@ template <bool STREAM, typename T> __device__ inline void st_stream(T* p, T v) {
 
 template <int EPI> struct EpiPlanes { static constexpr int N = (EPI == EPI_XPAY_DOT) ? 2 : (EPI == EPI_AXPY_NRM_DOT) ? 3 : (EPI == EPI_RESIDUAL) ? 1 : 0; };
 
-// Every epilogue writes its complex updates and reductions as EXPLICIT fused multiply-adds, the same pattern in every kernel: what the
-// compiler contracts on its own changes with the code around an expression (a refactoring of the operand loads moved the last bits of
-// the 4-row shapes, amplified to 6e-6 in the bound history of a 32-iteration solve), and the instances of one kernel that read or
-// recompute the shadow vector must round alike (tests/test_gpu_hash_mode.py compares them bit by bit).
-__device__ inline double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ inline float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// (the explicit fused multiply-adds of every epilogue: tfq_device.hpp: fma_)
 // v4 := v9 + s (v8 + s v4)   (u = old v4, x = v8, y = v9 = A v6; tfqmrgpu_core.hxx:196-202)
 template <typename R> __device__ inline void epi_xpay2(R& nr, R& ni, R yr, R yi, R ur, R ui, R xr, R xi, R sr, R si) {
     R const tr = fma_(-si, ui, fma_(sr, ur, xr)), ti = fma_(sr, ui, fma_(si, ur, xi));

@@ -141,7 +141,7 @@ static tfqmrgpuStatus_t transfer_blocks(Plan& p, hipStream_t s, int direction, b
 }
 
 static tfqmrgpuStatus_t upload(void* dst, void const* src, size_t bytes, hipStream_t s) {
-    if (0 == bytes) return TFQMRGPU_STATUS_SUCCESS;
+    if (0 == bytes || !src) return TFQMRGPU_STATUS_SUCCESS;
     TFQ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
     return TFQMRGPU_STATUS_SUCCESS;
 }
@@ -298,30 +298,11 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     p->buffer = (char*)pBuffer;
     p->precondInA = TFQMRGPU_PRECOND_NONE; p->haveA = false;   // this buffer holds no A yet, scaled or not (tfqmrgpu_ext.h section 7)
     auto at = [&](Window const& w) { return (void*)(p->buffer + w.offset); };
-    auto up = [&](Window const& w, void const* src, size_t bytes) { return upload(at(w), src, bytes, s); };
-    tfqmrgpuStatus_t st;
-    auto const& c = p->chunks;
-    std::vector<int32_t> orig(p->original_bsrColIndX);
-    for (auto& o : orig) o -= p->indexOffset;
-    if ((st = up(p->wChunkFirst, c.first.data(), c.first.size() * 4))) return st;
-    if ((st = up(p->wChunkCol, c.col.data(), c.col.size() * 4))) return st;
-    if ((st = up(p->wOrder, c.order.data(), c.order.size() * 4))) return st;
-    if ((st = up(p->wColChunkPtr, c.colPtr.data(), c.colPtr.size() * 4))) return st;
-    if ((st = up(p->wColStart, p->colStart.data(), p->colStart.size() * 4))) return st;
-    if ((st = up(p->wOrigCol, orig.data(), orig.size() * 4))) return st;
-    if (!p->colBatch.empty() && (st = up(p->wColBatch, p->colBatch.data(), p->colBatch.size()))) return st;
-    if (!p->colBatch.empty() && (st = up(p->wOrderB, c.orderB.data(), c.orderB.size() * 4))) return st;
-    if ((st = up(p->wBofX, p->bOfX.data(), p->bOfX.size() * 4))) return st;
-    if ((st = up(p->wStarts, p->starts_i.data(), p->starts_i.size() * 4))) return st;
-    if ((st = up(p->wPairs, p->pairs_i.data(), p->pairs_i.size() * 4))) return st;
-    if ((st = up(p->wSubset, p->subset_i.data(), p->subset_i.size() * 4))) return st;
-    if ((st = up(p->wBColPtr, p->bColPtr.data(), p->bColPtr.size() * 4))) return st;
-    if ((st = up(p->wBList, p->bList.data(), p->bList.size() * 4))) return st;
-    if ((st = up(p->wU2I, p->u2i.data(), p->u2i.size() * 4))) return st;
-    if ((st = up(p->wRowI, p->rowI.data(), p->rowI.size() * 4))) return st;
+    for (auto const& l : indexLists(*p))   // (tfq_plan.cpp: the windows were sized from the same list)
+        if (auto const st = upload(at(*l.window), l.data, l.bytes, s)) return st;
     TFQ_HIP(hipMemsetAsync(at(p->wCtl), 0, p->wCtl.bytes, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
     TFQ_HIP(hipMemsetAsync(at(p->wFold), 0, p->wFold.bytes, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)     // host vectors above go out of scope
+    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)     // the plan's lists may change (bufferSize) once this call returns
     DevPlan const d = resolve(*p);
     {   // the device-resident copy that the folded column operations read (pointers and sizes only: nothing in it changes with a solve)
         static_assert(sizeof(DevPlan) <= 1024, "window wSelf");
@@ -335,7 +316,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
         GlibcRand rng(1);
         float const denom = 1. / 2147483647;                            // tfqmrgpu_linalg.hxx:799-801
         for (size_t i = 0; i < n; ++i) v3[i] = rng.next() * denom;
-        st = transfer_blocks(*p, s, 0, false, Target{d.v3, false, p->ilv}, v3.data(), d.u2i, p->nnzbX, p->LM, p->LN, TFQMRGPU_LAYOUT_RRRRIIII, false, false);
+        auto const st = transfer_blocks(*p, s, 0, false, Target{d.v3, false, p->ilv}, v3.data(), d.u2i, p->nnzbX, p->LM, p->LN, TFQMRGPU_LAYOUT_RRRRIIII, false, false);
         if (st) return st;
         p->v3IsHash = false; p->selfStale = true;
     } else {

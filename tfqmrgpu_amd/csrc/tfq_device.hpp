@@ -114,6 +114,13 @@ __host__ __device__ inline float shadow_pick(uint64_t h, int oddRow, int plane) 
 __host__ __device__ inline float shadow_value(uint64_t key, int plane, uint32_t r, uint32_t c, uint32_t LN) {
     return shadow_pick(shadow_quad(key, r >> 1, c, LN), int(r & 1), plane);
 }
+
+// Every kernel writes its complex updates and reductions as EXPLICIT fused multiply-adds, one fixed pattern: what the compiler contracts on its own
+// changes with the code around an expression (a refactoring of the operand loads moved the last bits of the 4-row shapes, amplified to 6e-6 in the
+// bound history of a 32-iteration solve); results must not move when a kernel is refactored, and the instances of one kernel that read or recompute
+// the shadow vector must round alike (tests/test_gpu_hash_mode.py compares them bit by bit).
+__device__ inline double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ inline float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 #endif
 
 // ---- element order inside one plane (Re or Im) of a block -------------------------------------------------------------

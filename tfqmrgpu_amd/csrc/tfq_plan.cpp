@@ -7,6 +7,8 @@
 // the row) and the "first match wins" rule of its linear search (bsr.hxx:27-39).
 // The search itself is done with one sorted (column, position) list per block row, so the
 // cost is O(nPairs log) instead of the reference's O(nnzbX * nnz/rowA * nnz/rowX).
+// layoutBuffer() is its steps in order: elementOrder, columnBatches, cutChunks, launchOrder (dealToXcds), foldDecision, carveWindows;
+// indexLists() names the index windows and the host lists behind them once, for carveWindows and for setBuffer (tfq_api.hip).
 #include "tfq_plan.hpp"
 #include "tfq_switch.hpp"
 
@@ -18,9 +20,9 @@
 
 namespace tfq {
 
-int const kAllowedBlockSizes[15][2] = {
-    { 4, 4}, { 4, 5}, { 4, 8}, { 4,32}, { 8, 8}, { 8, 9}, { 8,10}, { 8,32}, { 8,64},
-    {16,16}, {16,32}, {16,64}, {32,32}, {32,64}, {64,64}};
+#define TFQ_PAIR(R, LM, LN) {LM, LN},
+int const kAllowedBlockSizes[15][2] = { TFQ_SIZES(TFQ_PAIR, 0) };
+#undef TFQ_PAIR
 
 bool blockSizeAllowed(int lm, int ln) {
     for (auto const& s : kAllowedBlockSizes) if (s[0] == lm && s[1] == ln) return true;
@@ -151,9 +153,11 @@ tfqmrgpuStatus_t analyse(Plan& p, int mb,
     p.colindx.resize(nnzbX);
     p.col32.resize(nnzbX);
     p.original_bsrColIndX.assign(nb, 0);
+    p.origCol.assign(nb, 0);
     for (int q = 0; q < nnzbX; ++q) {
         auto const jb = uint32_t(std::lower_bound(distinct.begin(), distinct.end(), colIndX[q]) - distinct.begin());
         p.original_bsrColIndX[jb] = colIndX[q];
+        p.origCol[jb] = colIndX[q] - off;
         p.colindx[q] = uint16_t(jb);   // the reference's colIndex_t is 16 bit (tfqmrgpu.hxx:59)
         p.col32[q] = jb;
     }
@@ -231,130 +235,121 @@ tfqmrgpuStatus_t analyse(Plan& p, int mb,
 // tfqmrgpu_blocksparse.hxx:46-51 (X first, 256-byte granules, tfqmrgpu_util.hxx:56-82); the
 // layout here is this library's own: no 2^ceil(log2 nnzbX) reduction scratch (zvv/dvv), instead
 // one small partial-sum record per chunk.
-tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
-    // 'm' (mixed precision): the iteration runs on a complex<float> plan; x, B, A are kept in double next to it (below)
-    bool const mixed = ('m' == precision);
-    char const iterPrec = mixed ? 'c' : precision;
-    p.LM = LM; p.LN = LN; p.precision = precision;
-    p.realBytes = ('z' == iterPrec) ? 8 : 4;
-    size_t const blockElems = size_t(2) * LM * LN;
-    p.S = size_t(p.nnzbX) * blockElems * p.realBytes;
-    // groups of rows interleaved (16-byte accesses for one column) where a multiply kernel is written for it: 16 x 16 and 8 x 8
-    // complex<double> (pairs), 16 x 16, 16 x 32 and 32 x 32 complex<float> (quads).  A lab build (-DTFQ_LAB) can keep the native order
-    // with TFQMRGPU_ILV=0 (A/B runs), =16: only 16 x 16 z, =2: only the double shapes, =3: all but the float shapes beyond 16 x 16
+namespace {
+
+// Element order inside the blocks: groups of rows interleaved (16-byte accesses for one column) where a multiply kernel is written for it: 16 x 16 and 8 x 8
+// complex<double> (pairs), 16 x 16, 16 x 32 and 32 x 32 complex<float> (quads).  A lab build (-DTFQ_LAB) can keep the native order
+// with TFQMRGPU_ILV=0 (A/B runs), =16: only 16 x 16 z, =2: only the double shapes, =3: all but the float shapes beyond 16 x 16
+int elementOrder(int LM, int LN, char prec) {
     int const ilvEnv = lab_switch("TFQMRGPU_ILV", 1);
-    auto const ilvOf = [&](char prec) {
-        int ilv = 0;
-        if (ilvEnv && 'z' == prec && ((16 == LM && 16 == LN) || (8 == LM && 8 == LN && ilvEnv != 16))) ilv = 2;
-        if ((1 == ilvEnv || 2 == ilvEnv) && 'z' == prec && 8 == LM && (32 == LN || 64 == LN)) ilv = 2;      // k_spmm_ilv8w (r03)
-        if (1 == ilvEnv && 'z' == prec && 8 == LM && (9 == LN || 10 == LN) && lab_switch("TFQMRGPU_ILV89", 1)) ilv = 2;   // k_spmm_ilv8w with a ragged second column group (r04)
-        if ((1 == ilvEnv || 3 == ilvEnv) && 'c' == prec && 16 == LM && 16 == LN) ilv = 4;
-        if (1 == ilvEnv && 'c' == prec && (16 == LM || 32 == LM) && 32 == LN) ilv = 4;   // 16 x 32, 32 x 32 (k_spmm_ilvf)
-        if (1 == ilvEnv && 'c' == prec && 8 == LM && (8 == LN || 32 == LN || 64 == LN)) ilv = 4;   // k_spmm_ilv8f (r03)
-        if (1 == ilvEnv && 'c' == prec && LM >= 16 && 64 == LN && lab_switch("TFQMRGPU_ILV64", 1)) ilv = 4;   // k_spmm_ilvf on column halves (r03)
-        return ilv;
-    };
-    p.ilv = ilvOf(iterPrec);
-    p.ilvZ = mixed ? ilvOf('z') : 0;
+    int ilv = 0;
+    if (ilvEnv && 'z' == prec && ((16 == LM && 16 == LN) || (8 == LM && 8 == LN && ilvEnv != 16))) ilv = 2;
+    if ((1 == ilvEnv || 2 == ilvEnv) && 'z' == prec && 8 == LM && (32 == LN || 64 == LN)) ilv = 2;      // k_spmm_ilv8w (r03)
+    if (1 == ilvEnv && 'z' == prec && 8 == LM && (9 == LN || 10 == LN) && lab_switch("TFQMRGPU_ILV89", 1)) ilv = 2;   // k_spmm_ilv8w with a ragged second column group (r04)
+    if ((1 == ilvEnv || 3 == ilvEnv) && 'c' == prec && 16 == LM && 16 == LN) ilv = 4;
+    if (1 == ilvEnv && 'c' == prec && (16 == LM || 32 == LM) && 32 == LN) ilv = 4;   // 16 x 32, 32 x 32 (k_spmm_ilvf)
+    if (1 == ilvEnv && 'c' == prec && 8 == LM && (8 == LN || 32 == LN || 64 == LN)) ilv = 4;   // k_spmm_ilv8f (r03)
+    if (1 == ilvEnv && 'c' == prec && LM >= 16 && 64 == LN && lab_switch("TFQMRGPU_ILV64", 1)) ilv = 4;   // k_spmm_ilvf on column halves (r03)
+    return ilv;
+}
 
-    // Column batches (k_spmm_ilv8b, 8 x 8 complex<double>): runs of up to kColBatchMax neighbouring block columns whose row patterns are identical -- same
-    // block rows in the same order, hence the same chunk cuts and the same A blocks per row -- are multiplied together, one A fetch for the block products of all of them.  Dense right-hand-side columns (BASELINE config 5) qualify; columns truncated around different centres do not.  Lab: TFQMRGPU_BATCH=1 off.
+// Column batches (k_spmm_ilv8b, 8 x 8 complex<double>): runs of up to kColBatchMax neighbouring block columns whose row patterns are identical -- same
+// block rows in the same order, hence the same chunk cuts and the same A blocks per row -- are multiplied together, one A fetch for the block products of all of them.  Dense right-hand-side columns (BASELINE config 5) qualify; columns truncated around different centres do not.  Lab: TFQMRGPU_BATCH=1 off.
+void columnBatches(Plan& p, char iterPrec) {
     p.colBatch.clear();
-    if ('z' == iterPrec && 8 == LM && 8 == LN && 2 == p.ilv) {
-        int const maxB = std::min(kColBatchMax, std::max(1, lab_switch("TFQMRGPU_BATCH", kColBatchMax)));
-        p.colBatch.assign(p.nCols, uint8_t(1 << 4));
-        bool any = false;
-        for (uint32_t c = 0; c < p.nCols; ) {
-            uint32_t const n0 = p.colStart[c + 1] - p.colStart[c];
-            uint32_t nb = 1;
-            while (int(nb) < maxB && c + nb < p.nCols && p.colStart[c + nb + 1] - p.colStart[c + nb] == n0 && n0 > 0 &&
-                   std::equal(p.rowI.begin() + p.colStart[c], p.rowI.begin() + p.colStart[c + 1], p.rowI.begin() + p.colStart[c + nb])) ++nb;
-            for (uint32_t k = 0; k < nb; ++k) p.colBatch[c + k] = uint8_t((nb << 4) | k);
-            any = any || nb > 1;
-            c += nb;
-        }
-        if (!any) p.colBatch.clear();
+    if (!('z' == iterPrec && 8 == p.LM && 8 == p.LN && 2 == p.ilv)) return;
+    int const maxB = std::min(kColBatchMax, std::max(1, lab_switch("TFQMRGPU_BATCH", kColBatchMax)));
+    p.colBatch.assign(p.nCols, uint8_t(1 << 4));
+    bool any = false;
+    for (uint32_t c = 0; c < p.nCols; ) {
+        uint32_t const n0 = p.colStart[c + 1] - p.colStart[c];
+        uint32_t nb = 1;
+        while (int(nb) < maxB && c + nb < p.nCols && p.colStart[c + nb + 1] - p.colStart[c + nb] == n0 && n0 > 0 &&
+               std::equal(p.rowI.begin() + p.colStart[c], p.rowI.begin() + p.colStart[c + 1], p.rowI.begin() + p.colStart[c + nb])) ++nb;
+        for (uint32_t k = 0; k < nb; ++k) p.colBatch[c + k] = uint8_t((nb << 4) | k);
+        any = any || nb > 1;
+        c += nb;
     }
+    if (!any) p.colBatch.clear();
+}
 
-    // chunks: runs of CH blocks inside one column, sized so that a chunk of one vector is 8..16 KiB and the
-    // grid has a few thousand work groups when the problem is large enough
-    {
-        size_t const blockBytes = blockElems * p.realBytes;
-        size_t target = p.S / 4096;
-        size_t maxKiB = 16;   // P2: 64 -> 16 KiB takes the vector kernels from 4.2 to 17 rounds of work groups (tail 16 % -> 1 %): iteration 2.80 -> 2.69 ms
-        maxKiB = size_t(std::max(8, lab_switch("TFQMRGPU_CHUNK_KIB", 16)));
-        target = std::min<size_t>(std::max<size_t>(target, 8 * 1024), maxKiB * 1024);
-        uint32_t CH = uint32_t(std::max<size_t>(1, target / blockBytes));
-        // every wave of a work group wants a unit of work: the MFMA multiply cuts a block into strips of 16 or
-        // 32 rows (RowTiles in tfq_spmm_mfma.hip), one strip per wave and pass
-        if (LM % 16 == 0 && LN % 16 == 0) {
-            int const mt = LM / 16, ms = (mt % 2 == 0 && 2 * (LN / 16) * p.realBytes <= 32) ? 2 : 1;
-            uint32_t const perBlock = uint32_t(mt / ms);
-            CH = std::max(CH, (4 + perBlock - 1) / perBlock);
-        }
-        auto& c = p.chunks;
-        c.first.clear(); c.col.clear(); c.colPtr.assign(size_t(p.nCols) + 1, 0);
-        std::vector<uint32_t> bandOf;                        // band of CH block rows in which a chunk starts
-        for (uint32_t jb = 0; jb < p.nCols; ++jb) {
-            c.colPtr[jb] = uint32_t(c.col.size());
-            for (uint32_t b = p.colStart[jb]; b < p.colStart[jb + 1]; b += CH) {
-                c.first.push_back(b); c.col.push_back(jb); bandOf.push_back(p.rowI[b] / CH);
-            }
-        }
-        c.colPtr[p.nCols] = uint32_t(c.col.size());
-        c.first.push_back(p.nnzbX);
-
-        // Launch order of the multiply.  Work groups are dealt round-robin to the 8 XCDs (observed; used for
-        // speed only, never for correctness), each XCD has its own 4 MiB L2.  Chunks are sorted by
-        // (group of G block columns, band of block rows, column) and the sorted list is cut into 8
-        // contiguous parts, one per XCD: inside an XCD consecutive work groups walk down the row bands of G
-        // columns together, so the A blocks of a band are re-read from that L2 (measured on P2: fused
-        // multiply 0.92 -> 0.82 ms; larger G loses the X blocks shared by neighbouring bands).
-        // (Tried and dropped in round 1: one chunk per WAVE with the 4 waves of a work group on 4 columns
-        //  of the same band -- 20 % slower; with all A traffic removed artificially the kernel only
-        //  reaches 0.77 ms, so A re-reads are not what bounds it any more.)
-        auto envu = [](char const* name, uint32_t dflt) { return uint32_t(lab_switch(name, int(dflt))); };
-        uint32_t const n = uint32_t(c.col.size());
-        uint32_t const mode = envu("TFQMRGPU_ORDER", 1), G = std::max(1u, envu("TFQMRGPU_ORDER_G", 4));   // 8 until the epilogue streams went non-temporal / the shadow vector stopped being read: now 4 (P2 iteration 2.649 -> 2.626 ms, 8x8 z 2.819 -> 2.792, 2: 2.655)
-        uint32_t const BM = std::max(1u, envu("TFQMRGPU_ORDER_BANDMULT", 1));   // bands of BM*CH block rows
-        std::vector<uint32_t> sorted(n);
-        std::iota(sorted.begin(), sorted.end(), 0u);
-        c.order = sorted;
-        if (mode && n >= 64) {
-            std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) {
-                uint32_t const ga = c.col[a] / G, gb = c.col[b] / G;
-                if (ga != gb) return ga < gb;
-                if (bandOf[a] / BM != bandOf[b] / BM) return bandOf[a] / BM < bandOf[b] / BM;
-                return c.col[a] < c.col[b];
-            });
-            uint32_t const q = n / 8, r = n % 8;
-            std::vector<uint32_t> begin(9, 0);
-            for (uint32_t x = 0; x < 8; ++x) begin[x + 1] = begin[x] + q + (x < r ? 1 : 0);
-            uint32_t w = 0;
-            for (uint32_t i = 0; i <= q; ++i)
-                for (uint32_t x = 0; x < 8; ++x)
-                    if (begin[x] + i < begin[x + 1]) c.order[w++] = sorted[begin[x] + i];
-        }
-        c.orderB.clear();
-        if (!p.colBatch.empty()) {   // the same order over the chunks of the batches' first columns only: every work group of that launch has work
-            std::vector<uint32_t> lead;
-            for (uint32_t ch : sorted) if (0 == (p.colBatch[c.col[ch]] & 15)) lead.push_back(ch);
-            uint32_t const nl = uint32_t(lead.size()), q = nl / 8, r = nl % 8;
-            c.orderB = lead;
-            if (mode && n >= 64) {
-                std::vector<uint32_t> begin(9, 0);
-                for (uint32_t x = 0; x < 8; ++x) begin[x + 1] = begin[x] + q + (x < r ? 1 : 0);
-                uint32_t w = 0;
-                for (uint32_t i = 0; i <= q; ++i)
-                    for (uint32_t x = 0; x < 8; ++x)
-                        if (begin[x] + i < begin[x + 1]) c.orderB[w++] = lead[begin[x] + i];
-            }
+// chunks: runs of CH blocks inside one column, sized so that a chunk of one vector is 8..16 KiB and the
+// grid has a few thousand work groups when the problem is large enough.  Returns the band of CH block rows in which each chunk starts.
+std::vector<uint32_t> cutChunks(Plan& p) {
+    size_t const blockBytes = size_t(2) * p.LM * p.LN * p.realBytes;
+    // P2: 64 -> 16 KiB takes the vector kernels from 4.2 to 17 rounds of work groups (tail 16 % -> 1 %): iteration 2.80 -> 2.69 ms
+    size_t const maxKiB = size_t(std::max(8, lab_switch("TFQMRGPU_CHUNK_KIB", 16)));
+    size_t const target = std::min<size_t>(std::max<size_t>(p.S / 4096, 8 * 1024), maxKiB * 1024);
+    uint32_t CH = uint32_t(std::max<size_t>(1, target / blockBytes));
+    // every wave of a work group wants a unit of work: the MFMA multiply cuts a block into strips of 16 or
+    // 32 rows (tfq_plan.hpp: mfma_units), one strip per wave and pass
+    if (p.LM % 16 == 0 && p.LN % 16 == 0) {
+        uint32_t const perBlock = uint32_t(mfma_units(p.LM, p.LN, int(p.realBytes)));
+        CH = std::max(CH, (4 + perBlock - 1) / perBlock);
+    }
+    auto& c = p.chunks;
+    c.first.clear(); c.col.clear(); c.colPtr.assign(size_t(p.nCols) + 1, 0);
+    std::vector<uint32_t> bandOf;
+    for (uint32_t jb = 0; jb < p.nCols; ++jb) {
+        c.colPtr[jb] = uint32_t(c.col.size());
+        for (uint32_t b = p.colStart[jb]; b < p.colStart[jb + 1]; b += CH) {
+            c.first.push_back(b); c.col.push_back(jb); bandOf.push_back(p.rowI[b] / CH);
         }
     }
-    size_t const nChunks = p.chunks.col.size();
+    c.colPtr[p.nCols] = uint32_t(c.col.size());
+    c.first.push_back(p.nnzbX);
+    return bandOf;
+}
+
+// a sorted chunk list cut into 8 contiguous parts, one per XCD, in the order in which the work groups of a launch reach the XCDs (round-robin)
+std::vector<uint32_t> dealToXcds(std::vector<uint32_t> const& sorted) {
+    uint32_t const n = uint32_t(sorted.size()), q = n / 8, r = n % 8;
+    std::vector<uint32_t> begin(9, 0), dealt(n);
+    for (uint32_t x = 0; x < 8; ++x) begin[x + 1] = begin[x] + q + (x < r ? 1 : 0);
+    uint32_t w = 0;
+    for (uint32_t i = 0; i <= q; ++i)
+        for (uint32_t x = 0; x < 8; ++x)
+            if (begin[x] + i < begin[x + 1]) dealt[w++] = sorted[begin[x] + i];
+    return dealt;
+}
+
+// Launch order of the multiply.  Work groups are dealt round-robin to the 8 XCDs (observed; used for
+// speed only, never for correctness), each XCD has its own 4 MiB L2.  Chunks are sorted by
+// (group of G block columns, band of block rows, column) and the sorted list is cut into 8
+// contiguous parts, one per XCD: inside an XCD consecutive work groups walk down the row bands of G
+// columns together, so the A blocks of a band are re-read from that L2 (measured on P2: fused
+// multiply 0.92 -> 0.82 ms; larger G loses the X blocks shared by neighbouring bands).
+// (Tried and dropped in round 1: one chunk per WAVE with the 4 waves of a work group on 4 columns
+//  of the same band -- 20 % slower; with all A traffic removed artificially the kernel only
+//  reaches 0.77 ms, so A re-reads are not what bounds it any more.)
+void launchOrder(Plan& p, std::vector<uint32_t> const& bandOf) {
+    auto& c = p.chunks;
+    auto envu = [](char const* name, uint32_t dflt) { return uint32_t(lab_switch(name, int(dflt))); };
+    uint32_t const n = uint32_t(c.col.size());
+    uint32_t const mode = envu("TFQMRGPU_ORDER", 1), G = std::max(1u, envu("TFQMRGPU_ORDER_G", 4));   // 8 until the epilogue streams went non-temporal / the shadow vector stopped being read: now 4 (P2 iteration 2.649 -> 2.626 ms, 8x8 z 2.819 -> 2.792, 2: 2.655)
+    uint32_t const BM = std::max(1u, envu("TFQMRGPU_ORDER_BANDMULT", 1));   // bands of BM*CH block rows
+    bool const deal = mode && n >= 64;
+    std::vector<uint32_t> sorted(n);
+    std::iota(sorted.begin(), sorted.end(), 0u);
+    if (deal) std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) {
+        uint32_t const ga = c.col[a] / G, gb = c.col[b] / G;
+        if (ga != gb) return ga < gb;
+        if (bandOf[a] / BM != bandOf[b] / BM) return bandOf[a] / BM < bandOf[b] / BM;
+        return c.col[a] < c.col[b];
+    });
+    c.order = deal ? dealToXcds(sorted) : sorted;
+    c.orderB.clear();
+    if (!p.colBatch.empty()) {   // the same order over the chunks of the batches' first columns only: every work group of that launch has work
+        std::vector<uint32_t> lead;
+        for (uint32_t ch : sorted) if (0 == (p.colBatch[c.col[ch]] & 15)) lead.push_back(ch);
+        c.orderB = deal ? dealToXcds(lead) : lead;
+    }
+}
+
+void foldDecision(Plan& p) {
     p.colSegMax = 1;                                  // long columns are summed by several work groups (tfq_colops.hpp: column_total)
     for (uint32_t jb = 0; jb < p.nCols; ++jb)
-        p.colSegMax = std::max(p.colSegMax, col_segments(p.chunks.colPtr[jb + 1] - p.chunks.colPtr[jb], LN));
+        p.colSegMax = std::max(p.colSegMax, col_segments(p.chunks.colPtr[jb + 1] - p.chunks.colPtr[jb], p.LN));
     // Small systems fold the column operations into the producers' tails (tfq_colops.hpp): six launches less per iteration slot.
     // "Small" = at most kFoldMax = 384 chunks, i.e. work groups per multiply: measured with one build and the switch (scripts/fold_crossover.py).
     // r03, arrivals with fences: gains below 128 chunks, LOSES 10-14 % at 256 ... 288.  r04, fence-free arrivals (co_store / co_load): 22 chunks -9 %,
@@ -363,9 +358,15 @@ tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
     // A plan with a column of several segments never folds: the folded tail sums a column in one work group, the column kernels sum its segments
     // first, and the two orders give different bits.  So the order of every column sum depends on (chunks of the column, LN) alone -- not on the
     // fold limit, the number of ranks or a user-defined operator.  (The product meets such a plan only at LN = 64: a column of 257 ... 384 chunks.)
-    p.foldOk = (nChunks <= size_t(lab_switch("TFQMRGPU_FOLD_MAX", kFoldMax))) && 1 == p.colSegMax;
+    p.foldOk = (p.chunks.col.size() <= size_t(lab_switch("TFQMRGPU_FOLD_MAX", kFoldMax))) && 1 == p.colSegMax;
     if (p.foldOk) { p.colBatch.clear(); p.chunks.orderB.clear(); }   // small plans fold their column operations into the multiplies' tails instead
+}
 
+// The order of the take calls is the order of the buffer: X first, A last before the 'm' block.
+void carveWindows(Plan& p) {
+    bool const mixed = ('m' == p.precision);
+    int const LM = p.LM, LN = p.LN;
+    size_t const blockElems = size_t(2) * LM * LN, nChunks = p.chunks.col.size();
     size_t at = 0;
     auto take = [&](Window& w, size_t bytes) { w.offset = at; w.bytes = bytes; at = align256(at + bytes); };
     // (r03: X-shaped vectors that lie exactly 2^k bytes apart -- config 4: 2 GiB, config 5: 512 MiB -- do NOT alias on the memory channels:
@@ -378,33 +379,15 @@ tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
     size_t const cs = size_t(p.nCols) * 2 * LN * p.realBytes;
     take(p.wRho, cs); take(p.wAlfa, cs); take(p.wBeta, cs); take(p.wC67, cs); take(p.wEta, cs);
     take(p.wC67a, cs); take(p.wEta2, cs);
-    take(p.wZ,   size_t(p.nCols) * 2 * LN * sizeof(double));
-    take(p.wD,   size_t(p.nCols) * LN * sizeof(double));
-    take(p.wTau, size_t(p.nCols) * LN * sizeof(double));
-    take(p.wVar, size_t(p.nCols) * LN * sizeof(double));
-    take(p.wInvBn2, size_t(p.nCols) * LN * sizeof(double));
+    size_t const cd = size_t(p.nCols) * LN * sizeof(double);
+    take(p.wZ, 2 * cd); take(p.wD, cd); take(p.wTau, cd); take(p.wVar, cd); take(p.wInvBn2, cd);
     take(p.wStatus, size_t(p.nCols) * LN);
     take(p.wCtl, 4096);
     take(p.wPz, nChunks * 2 * LN * sizeof(double));
     take(p.wPd, nChunks * LN * sizeof(double));
     take(p.wColRec, size_t(p.nCols) * 2 * sizeof(double)); // per-column stopping-test record
     take(p.wColPart, (nChunks / kColSlot + p.nCols + 2) * 3 * size_t(LN) * sizeof(double));   // the segments' shares (colSegMax > 1)
-    take(p.wChunkFirst, (nChunks + 1) * sizeof(uint32_t));
-    take(p.wChunkCol, nChunks * sizeof(uint32_t));
-    take(p.wOrder, nChunks * sizeof(uint32_t));
-    take(p.wColChunkPtr, (size_t(p.nCols) + 1) * sizeof(uint32_t));
-    take(p.wColStart, (size_t(p.nCols) + 1) * sizeof(uint32_t));
-    take(p.wOrigCol, size_t(p.nCols) * sizeof(int32_t));
-    take(p.wColBatch, size_t(p.nCols));
-    take(p.wOrderB, p.chunks.orderB.size() * sizeof(uint32_t));
-    take(p.wBofX, size_t(p.nnzbX) * sizeof(uint32_t));         // B block on each X block or ~0
-    take(p.wStarts, p.starts_i.size() * sizeof(uint32_t));
-    take(p.wPairs, p.pairs_i.size() * sizeof(uint32_t));
-    take(p.wSubset, size_t(p.nnzbB) * sizeof(uint32_t));
-    take(p.wBColPtr, (size_t(p.nCols) + 1) * sizeof(uint32_t));
-    take(p.wBList, size_t(p.nnzbB) * sizeof(uint32_t));
-    take(p.wU2I, size_t(p.nnzbX) * sizeof(uint32_t));
-    take(p.wRowI, size_t(p.nnzbX) * sizeof(uint32_t));
+    for (auto const& l : indexLists(p)) take(*l.window, l.bytes);
     take(p.wFold, (size_t(p.nCols) + 1) * sizeof(uint32_t));
     take(p.wSelf, 1024);
     take(p.wA, size_t(p.nnzbA) * 2 * LM * LM * p.realBytes);
@@ -417,10 +400,41 @@ tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
         take(p.wR, p.S);
         take(p.wBz, size_t(p.nnzbB) * blockElems * sizeof(double));
         take(p.wAz, size_t(p.nnzbA) * 2 * LM * LM * sizeof(double));
-        take(p.wBn2z, size_t(p.nCols) * LN * sizeof(double));
+        take(p.wBn2z, cd);
         take(p.wRefine, 256);
     }
     p.bufferBytes = at + 256;
+}
+
+} // namespace
+
+std::vector<IndexList> indexLists(Plan& p) {
+    auto const& c = p.chunks;
+    auto list = [](Window& w, auto const& v) { return IndexList{&w, v.data(), v.size() * sizeof(v[0])}; };
+    return {
+        list(p.wChunkFirst, c.first), list(p.wChunkCol, c.col), list(p.wOrder, c.order), list(p.wColChunkPtr, c.colPtr),
+        list(p.wColStart, p.colStart), list(p.wOrigCol, p.origCol),
+        // the one window that is not sized by its list: a byte per block column also where the plan has no batches (colBatch is empty and
+        // nothing is uploaded), so that every window behind it keeps its offset whether the columns batch or not
+        IndexList{&p.wColBatch, p.colBatch.empty() ? nullptr : p.colBatch.data(), p.nCols},
+        list(p.wOrderB, c.orderB), list(p.wBofX, p.bOfX), list(p.wStarts, p.starts_i), list(p.wPairs, p.pairs_i),
+        list(p.wSubset, p.subset_i), list(p.wBColPtr, p.bColPtr), list(p.wBList, p.bList), list(p.wU2I, p.u2i), list(p.wRowI, p.rowI),
+    };
+}
+
+tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision) {
+    // 'm' (mixed precision): the iteration runs on a complex<float> plan; x, B, A are kept in double next to it (carveWindows)
+    bool const mixed = ('m' == precision);
+    char const iterPrec = mixed ? 'c' : precision;
+    p.LM = LM; p.LN = LN; p.precision = precision;
+    p.realBytes = ('z' == iterPrec) ? 8 : 4;
+    p.S = size_t(p.nnzbX) * 2 * LM * LN * p.realBytes;
+    p.ilv = elementOrder(LM, LN, iterPrec);
+    p.ilvZ = mixed ? elementOrder(LM, LN, 'z') : 0;
+    columnBatches(p, iterPrec);
+    launchOrder(p, cutChunks(p));
+    foldDecision(p);
+    carveWindows(p);
     return TFQMRGPU_STATUS_SUCCESS;
 }
 

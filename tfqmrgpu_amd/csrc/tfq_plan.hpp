@@ -1,6 +1,6 @@
 // Host-side plan of one bsrsv problem: the reference-visible analysis results
 // (bit-exact with real-space/tfQMRgpu createPlan, tfqmrgpu.cu:136-351) plus the
-// MI355X-specific device layout derived from them.
+// MI355X-specific device layout derived from them; and the shape list and shape rules that the plan and the kernels share.
 #pragma once
 #include <cstdint>
 #include <cstddef>
@@ -25,6 +25,25 @@ inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 constexpr uint32_t col_seg_len(int LN) { return uint32_t(256 / LN) * 16u; }
 constexpr uint32_t col_segments(uint32_t n, int LN) { return (n <= 4 * col_seg_len(LN)) ? 1u : (n + col_seg_len(LN) - 1) / col_seg_len(LN); }
 constexpr uint32_t kColSlot = 64;      // granule of the slot numbering of colPart (tfq_colops.hpp: col_part_slot; <= the shortest segment: LN = 64)
+
+// The 15 (LM, LN) pairs of the solver, in the order of the reference's table (allowed_block_sizes.h:4-18): kAllowedBlockSizes is generated
+// from it, and so are the instances of tfq_vec.hip and of the multiply's family launchers (tfq_spmm.hpp)
+#define TFQ_SIZES(X, R) \
+    X(R, 4, 4) X(R, 4, 5) X(R, 4, 8) X(R, 4, 32) X(R, 8, 8) X(R, 8, 9) X(R, 8, 10) X(R, 8, 32) X(R, 8, 64) \
+    X(R, 16, 16) X(R, 16, 32) X(R, 16, 64) X(R, 32, 32) X(R, 32, 64) X(R, 64, 64)
+
+// Waves per 16-row strip of a Y block in k_spmm_mfma | k_spmm_mfma_m (rb: bytes per accumulator element): two, each with LN / 2 columns,
+// where the double accumulators of a whole strip and two operand slices would not fit the 256 VGPRs of two waves per SIMD
+// (128 columns: 128 VGPRs of accumulators)
+constexpr int mfma_col_split(int rb, int ln) { return (8 == rb && ln >= 128) ? 2 : 1; }
+// Row tiles (16 rows each) per wave of these kernels, for mt row tiles per block and nt column tiles per wave: two where the block has them
+// and the accumulators (2 * nt complex tiles) stay within 64 VGPRs
+constexpr int mfma_row_tiles(int mt, int nt, int rb) { return (mt % 2 == 0 && 2 * nt * rb <= 32) ? 2 : 1; }
+// Units of work (strips of a Y block, one per wave and pass) per Y block: the plan cuts its chunks by it, the stand-alone multiply its work groups
+constexpr int mfma_units(int lm, int ln, int rb) {
+    int const cs = mfma_col_split(rb, ln), mt = lm / 16;
+    return (mt / mfma_row_tiles(mt, ln / (16 * cs), rb)) * cs;
+}
 
 struct Window { size_t offset = 0, bytes = 0; };
 
@@ -71,6 +90,7 @@ struct Plan {
     std::vector<uint32_t> bColPtr, bList; // B blocks grouped by compressed column
     std::vector<uint32_t> bOfX;        // [nnzbX] internal order: B block sitting on this X block, or ~0
     std::vector<uint32_t> rowI;        // [nnzbX] block row, internal order
+    std::vector<int32_t>  origCol;     // [nCols] original_bsrColIndX without the index offset (what the device keeps, DevPlan::origCol)
     ChunkTable chunks;
 
     // ---- fixed by bufferSize -----------------------------------------------------------------
@@ -157,7 +177,12 @@ tfqmrgpuStatus_t analyse(Plan& p, int mb,
 // derive chunk tables + buffer windows for (LM, LN, precision); tfq_plan.cpp
 tfqmrgpuStatus_t layoutBuffer(Plan& p, int LM, int LN, char precision);
 
-// the 15 compiled (ldA, ldB) pairs of the reference (allowed_block_sizes.h:4-18)
+// The index lists of a laid-out plan that setBuffer uploads, in the order of their windows in the buffer: layoutBuffer sizes the windows from
+// this list and setBuffer walks it, so that a window and its upload cannot disagree.  data == nullptr: nothing to upload
+struct IndexList { Window* window; void const* data; size_t bytes; };
+std::vector<IndexList> indexLists(Plan& p);
+
+// the 15 compiled (ldA, ldB) pairs of the reference (TFQ_SIZES)
 extern int const kAllowedBlockSizes[15][2];
 bool blockSizeAllowed(int lm, int ln);
 

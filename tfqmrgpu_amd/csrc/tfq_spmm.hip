@@ -283,23 +283,22 @@ static MulKernel multiply_select(MulPrec p, int lm, int ln) {
     return MulKernel::plan;
 }
 
-// units (strips of a Y block, k_spmm_mfma | k_spmm_mfma_m) per Y block; rb: bytes per accumulator element
-static int mfma_units(int lm, int ln, int rb) {
-    int const cs = mfma_col_split(rb, ln);
-    int const mt = lm / 16;
-    int const ms = (mt % 2 == 0 && 2 * (ln / (16 * cs)) * rb <= 32) ? 2 : 1;   // RowTiles<>::MS
-    return (mt / ms) * cs;
-}
-
 bool multiply_shape_allowed(char precision, int lm, int ln) {
     return MulKernel::missing != multiply_select(multiply_precision(precision), lm, ln);
 }
 
-uint32_t multiply_blocks_per_work_group(char precision, int lm, int ln) {
-    bool const mfma = (lm % 16 == 0 && ln % 16 == 0);
-    if (!mfma) return 0;                                   // (a prepared order is honoured by k_spmm_mfma | k_spmm_mfma_m only)
-    int const mu = mfma_units(lm, ln, (MulPrec::c == multiply_precision(precision)) ? 4 : 8);
-    return uint32_t((mu >= 4) ? 1 : 4 / mu);
+// Y blocks per work group of the stand-alone multiply in plain mode (SpmmArgs::CH), for every family but k_spmm_pad (its own work groups:
+// one Y block per wave): enough work groups to fill 256 CUs several times, at least one unit of work per wave
+static uint32_t multiply_chunk(MulPrec p, int lm, int ln) {
+    int const mu = mfma_units(lm, ln, (MulPrec::c == p) ? 4 : 8);   // strips per Y block
+    if (lm % 16 == 0 && ln % 16 == 0) return uint32_t((mu >= 4) ? 1 : 4 / mu);   // k_spmm_mfma | k_spmm_mfma_m | k_spmm_n16: one strip per wave
+    if (8 == lm) return 4;                                  // k_spmm_mfma8 (kTile8): one Y block per wave and pass
+    if (MulPrec::z == p && 32 == ln) return 16;             // 4 x 32 z, k_spmm_m4: 64 items, four per Y block (and the tile kernel's 16 before it)
+    return 64;                                              // the other 4-row shapes (k_spmm_small4: a few sub-blocks per thread group)
+}
+
+uint32_t multiply_blocks_per_work_group(char precision, int lm, int ln) {   // (a prepared order is honoured by k_spmm_mfma | k_spmm_mfma_m | k_spmm_n16 only)
+    return (lm % 16 || ln % 16) ? 0 : multiply_chunk(multiply_precision(precision), lm, ln);
 }
 
 tfqmrgpuStatus_t launch_multiply(char precision, int lm, int ln, uint32_t nnzbY,
@@ -312,18 +311,12 @@ tfqmrgpuStatus_t launch_multiply(char precision, int lm, int ln, uint32_t nnzbY,
     SpmmArgs a{};
     a.Y = Y; a.A = A; a.X = X; a.starts = starts; a.pairs = pairs; a.nY = nnzbY;
     a.chunkFirst = nullptr; a.gate = 0;
-    a.yOrder = (lm % 16 == 0 && ln % 16 == 0) ? yOrder : nullptr;
+    bool const mfma = (lm % 16 == 0 && ln % 16 == 0);
+    a.yOrder = mfma ? yOrder : nullptr;
     bool ok = true;
     if (MulKernel::pad == k) ok = spmm_pad(prec, lm, ln, a, s);      // (its own work groups: one Y block per wave)
     else {
-        // plain mode: enough work groups to fill 256 CUs several times, at least one strip per wave
-        bool const mfma = (lm % 16 == 0 && ln % 16 == 0);
-        int const mu = mfma ? mfma_units(lm, ln, (MulPrec::c == prec) ? 4 : 8) : 1;   // strips per Y block
-        uint32_t ch = (mu >= 4) ? 1 : 4 / mu;                 // one strip per wave
-        if (!mfma) ch = (4 == lm) ? 64 : (lm * ln >= 256) ? 1 : 256 / (lm * ln); // k_spmm_small4: a few sub-blocks per thread group
-        if (8 == lm) ch = 4;                                  // k_spmm_mfma8 (kTile8): one Y block per wave and pass
-        if (4 == lm && dbl && 32 == ln) ch = 16;              // k_spmm_m4: 64 items, four per Y block (and the tile kernel's 16 before it)
-        a.CH = ch;
+        uint32_t const ch = a.CH = multiply_chunk(prec, lm, ln);
         uint32_t nWG = (nnzbY + ch - 1) / ch;
         // (lab: contiguous eighths of the caller's Y blocks per XCD instead of round-robin work groups)
         if (mfma && nWG >= 64 && lab_switch("TFQMRGPU_PLAIN_XCD", 0)) { a.plainPer = (nWG + 7) / 8; nWG = 8 * a.plainPer; }

@@ -71,12 +71,7 @@ template <bool STREAM, typename T> __device__ inline void st_stream(T* p, T v) {
 
 template <int EPI> struct EpiPlanes { static constexpr int N = (EPI == EPI_XPAY_DOT) ? 2 : (EPI == EPI_AXPY_NRM_DOT) ? 3 : (EPI == EPI_RESIDUAL) ? 1 : 0; };
 
-// Every epilogue writes its complex updates and reductions as EXPLICIT fused multiply-adds, the same pattern in every kernel: what the
-// compiler contracts on its own changes with the code around an expression (a refactoring of the operand loads moved the last bits of
-// the 4-row shapes, amplified to 6e-6 in the bound history of a 32-iteration solve), and the instances of one kernel that read or
-// recompute the shadow vector must round alike (tests/test_gpu_hash_mode.py compares them bit by bit).
-__device__ inline double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ inline float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// Every epilogue writes its complex updates and reductions as explicit fused multiply-adds (tfq_device.hpp: fma_), the same pattern in every kernel.
 // v4 := v9 + s (v8 + s v4)   (u = old v4, x = v8, y = v9 = A v6; tfqmrgpu_core.hxx:196-202)
 template <typename R> __device__ inline void epi_xpay2(R& nr, R& ni, R yr, R yi, R ur, R ui, R xr, R xi, R sr, R si) {
     R const tr = fma_(-si, ui, fma_(sr, ur, xr)), ti = fma_(sr, ui, fma_(si, ur, xi));
@@ -349,14 +344,9 @@ template <bool OK, typename F> inline void variant(bool v, F&& f) {
     f(std::false_type{});
 }
 
-// the block shapes the library is compiled for
-#define TFQ_SIZES(X, R) \
-    X(R, 4, 4) X(R, 4, 5) X(R, 4, 8) X(R, 4, 32) X(R, 8, 8) X(R, 8, 9) X(R, 8, 10) X(R, 8, 32) X(R, 8, 64) \
-    X(R, 16, 16) X(R, 16, 32) X(R, 16, 64) X(R, 32, 32) X(R, 32, 64) X(R, 64, 64)
-
-// the further shapes of the stand-alone multiply (tfqmrgpuExt_multiply, the reference's `bench multi`): the plain product only, on
-// k_spmm_mfma in `c` and `z` and on k_spmm_mfma_m in `m`; no solver family is instantiated for them and the solver's list
-// (tfq_plan.cpp: kAllowedBlockSizes) does not change
+// The block shapes the library is compiled for: TFQ_SIZES (tfq_plan.hpp), the solver's.
+// The further shapes of the stand-alone multiply (tfqmrgpuExt_multiply, the reference's `bench multi`): the plain product only, on
+// k_spmm_mfma in `c` and `z` and on k_spmm_mfma_m in `m`; no solver family is instantiated for them and the solver's list does not change
 #define TFQ_MULTIPLY_SIZES(X, R) X(R, 48, 48) X(R, 96, 96) X(R, 128, 128)
 // ... and those that do not fill 16 x 16 tiles, on k_spmm_pad: in every precision, and the 4- and 8-row shapes of TFQ_SIZES in `m`
 #define TFQ_PAD_SIZES(X, R) X(R, 6, 6) X(R, 12, 12) X(R, 24, 24)
@@ -366,15 +356,13 @@ constexpr bool solver_shape(int lm, int ln) { return false TFQ_SIZES(TFQ_SIZE_IS
 constexpr bool wide_shape(int lm, int ln) { return false TFQ_MULTIPLY_SIZES(TFQ_SIZE_IS, 0); }     // one of TFQ_MULTIPLY_SIZES
 constexpr bool pad_shape(int lm, int ln) { return false TFQ_PAD_SIZES(TFQ_SIZE_IS, 0); }           // one of TFQ_PAD_SIZES
 #undef TFQ_SIZE_IS
+#define TFQ_SIZE_IN(R, LM, LN) && solver_shape(LM, LN)
+static_assert(true TFQ_PAD_M_SIZES(TFQ_SIZE_IN, 0), "TFQ_PAD_M_SIZES: shapes of TFQ_SIZES");
+#undef TFQ_SIZE_IN
 
 // The precisions of the stand-alone multiply (the reference's `bench multi`): `z` | `d` complex<double>, `m` float data summed in double,
 // every other letter complex<float>
 enum class MulPrec { c, z, m };
-
-// Waves per 16-row strip of a Y block in k_spmm_mfma | k_spmm_mfma_m (rb: bytes per accumulator element): two, each with LN / 2 columns,
-// where the double accumulators of a whole strip and two operand slices would not fit the 256 VGPRs of two waves per SIMD
-// (128 columns: 128 VGPRs of accumulators)
-constexpr int mfma_col_split(int rb, int ln) { return (8 == rb && ln >= 128) ? 2 : 1; }
 
 // Launches Family<R, LM, LN, EPI>::go(k, a, nWG, s) for the precision, shape and epilogue of a launch (nothing when nWG == 0);
 // false: the shape is not one of TFQ_SIZES

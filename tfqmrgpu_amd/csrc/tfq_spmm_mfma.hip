@@ -21,10 +21,8 @@ template <typename R, int NT> struct ColMap {
     __device__ static inline int col(int lc, int nt) { return (nt / VW) * 16 * VW + lc * VW + nt % VW; }
 };
 
-// row tiles per wave: two where the block has them and the accumulators (MS * NT complex tiles) stay within 64 VGPRs
-template <typename R, int MT, int NT> struct RowTiles {
-    static constexpr int MS = (MT % 2 == 0 && 2 * NT * sizeof(R) <= 32) ? 2 : 1;
-};
+// row tiles per wave (tfq_plan.hpp: the rule by which the plan cuts its chunks as well)
+template <typename R, int MT, int NT> struct RowTiles { static constexpr int MS = mfma_row_tiles(MT, NT, int(sizeof(R))); };
 
 // operands of one "slice" = KSL consecutive MFMA k-steps (4 k each) of one block product, for a strip of
 // MS * 16 block rows: the wave owns MS row tiles, tile ms of lane column lc holds block row i0 + lc * MS + ms, so

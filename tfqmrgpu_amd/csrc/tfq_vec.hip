@@ -82,10 +82,7 @@ struct Scal {
     }
 };
 
-// Explicit fused multiply-adds, one fixed pattern: what the compiler contracts on its own depends on the code around the expression
-// (tfq_spmm.hip has the story), and results must not move when a kernel is refactored.
-__device__ inline double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ inline float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// (explicit fused multiply-adds, one fixed pattern: tfq_device.hpp: fma_)
 // y := x + a*y  (tfqmrgpu_linalg.hxx:660-661)
 template <typename R> __device__ inline void xpay(R& yr, R& yi, R xr, R xi, R ar, R ai) {
     R const nr = fma_(-ai, yi, fma_(ar, yr, xr));
@@ -607,10 +604,6 @@ __global__ __launch_bounds__(256) void k_refine_update(RefineArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-#define TFQ_SIZES(X, R) \
-    X(R, 4, 4) X(R, 4, 5) X(R, 4, 8) X(R, 4, 32) X(R, 8, 8) X(R, 8, 9) X(R, 8, 10) X(R, 8, 32) X(R, 8, 64) \
-    X(R, 16, 16) X(R, 16, 32) X(R, 16, 64) X(R, 32, 32) X(R, 32, 64) X(R, 64, 64)
-
 template <typename R, int LM, int LN>
 static hipError_t vec_run(int op, DevPlan const& d, double tol, int maxIt, hipStream_t s) {
     dim3 const grid(d.nChunks), cols(d.nCols, d.colSegMax ? d.colSegMax : 1), cols1(d.nCols), blk(256);
