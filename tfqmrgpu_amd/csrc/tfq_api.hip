@@ -378,7 +378,6 @@ static tfqmrgpuStatus_t set_or_get(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t 
     uint32_t const* u2n = (2 == which) ? d.u2i : nullptr;
     auto const st = transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, nnzb, nR, nC, layout, trans, conj, nullptr,
                                     (mixed && 0 == which && !is_get) ? &floatA : nullptr);
-    if (!st && 1 == which) p->haveB = true;
     if (0 == which && !is_get) { p->haveA = !st; p->precondInA = TFQMRGPU_PRECOND_NONE; }   // a new A: not scaled, the preconditioner of the last one is stale
     return st;
 }

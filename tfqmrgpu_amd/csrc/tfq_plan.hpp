@@ -128,7 +128,6 @@ struct Plan {
     void* ringEvent[kDepth] = {};      // hipEvent_t behind each copy
     int shadowMode = TFQMRGPU_SHADOW_HASH;
     bool v3IsHash = false;             // the buffer's v3 holds the counter-based hash (set by setBuffer, cleared by a user-supplied vector)
-    bool haveB = false;
     bool threeProducts = false;        // tfqmrgpuExt_setThreeProductMultiply: Gauss' three real products per complex one in the double multiplies
     std::vector<double> cycleResidual; // 'm': relative residual (double arithmetic) in front of every inner solve and at the end
     std::vector<int32_t> cycleIterations; // 'm': float iterations of every inner solve

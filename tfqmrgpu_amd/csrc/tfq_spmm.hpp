@@ -24,7 +24,8 @@
 //  * tfq_spmm.hip: k_spmm_n16 (tfqmrgpuExt_multiply, 16 x 16), k_spmm_direct (one thread per output element; only as the epilogue of a
 //    user-defined operator).
 // This header: what the kernels of every family share (launch arguments, epilogue arithmetic, operand and stream helpers), the shapes each
-// family takes and the family launchers.
+// family takes and the family launchers.  tfq_spmm_ilv.hpp: what only the kernels on the interleaved orders share (work-group prologue, the
+// epilogue operands of a 16-byte piece, the plane exchange).
 #pragma once
 #include <cstdlib>
 #include <type_traits>

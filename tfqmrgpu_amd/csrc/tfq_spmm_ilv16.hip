@@ -1,5 +1,5 @@
 // The 16-row kernels on the plans' interleaved element orders: k_spmm_ilv16, k_spmm_ilv16f, k_spmm_ilvf (tfq_spmm.hpp)
-#include "tfq_spmm.hpp"
+#include "tfq_spmm_ilv.hpp"
 
 namespace tfq {
 
@@ -142,14 +142,12 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16(SpmmArgs a) {
                     double w0, w1;      // the logical elements (rows 2 (lr + 4 h) + e, column lc) are one quad of the shadow vector's hash
                     if constexpr (HASH) { w0 = shadow_pick(hqh, e, 0); w1 = shadow_pick(hqh, e, 1); }
                     else { w0 = wr[h][e]; w1 = wi[h][e]; }
-                    double const dr = nr[e], di = ni[e];
-                    part[0] = __builtin_fma(-di, w1, __builtin_fma(dr, w0, part[0]));
-                    part[1] = __builtin_fma(di, w0, __builtin_fma(dr, w1, part[1]));
-                    if constexpr (EPI == EPI_AXPY_NRM_DOT) part[2] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[2]));
+                    epi_dot(part[0], part[1], nr[e], ni[e], w0, w1);
+                    if constexpr (EPI == EPI_AXPY_NRM_DOT) epi_nrm(part[2], nr[e], ni[e]);
                 } else if constexpr (EPI == EPI_RESIDUAL) {     // |A x - b|^2, nothing stored (tfqmrgpu_core.hxx:265-269)
                     R const rr = yr[e] + R(-1) * br[e], ri = yi[e] + R(-1) * bi[e];
                     double const dr = rr, di = ri;
-                    part[0] += dr * dr + di * di;
+                    part[0] += dr * dr + di * di;   // (not epi_nrm: this kernel's sum leaves the contraction to the compiler)
                 }
             }
             if constexpr (EPI != EPI_RESIDUAL) {
@@ -232,12 +230,8 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16f(SpmmArgs a) {
         };
         uint32_t const q0 = starts[y], q1 = starts[y + 1];
         Ops o0, o1;
-        constexpr bool EPI_FIRST = true;   // epilogue operands requested in front of the first products' operands: -1 % (profiles/r02_ab_traversal.txt)
-        if constexpr (!EPI_FIRST) {
-            if (q0 < q1) fetch(o0, q0);
-            if (q0 + 1 < q1) fetch(o1, q0 + 1);
-        }
         size_t const yoff = size_t(y) * 2 * P + mine;          // rows 4 lr .. 4 lr + 3 of column lc
+        // the epilogue operands are requested in front of the first products' operands: -1 % (profiles/r02_ab_traversal.txt)
         f4v ur, ui, vr, vi, wr, wi;
         if constexpr (UPD) {
             if constexpr (EPI == EPI_XPAY_DOT && FIRST) { ur = f4v{0, 0, 0, 0}; ui = ur; vr = ur; vi = ur; }   // first iteration: old v4 = v8 = 0, not read
@@ -247,10 +241,8 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16f(SpmmArgs a) {
             }
             if constexpr (!HASH) { wr = __builtin_nontemporal_load((f4v const*)(a.v3 + yoff)); wi = __builtin_nontemporal_load((f4v const*)(a.v3 + yoff + P)); }
         }
-        if constexpr (EPI_FIRST) {
-            if (q0 < q1) fetch(o0, q0);
-            if (q0 + 1 < q1) fetch(o1, q0 + 1);
-        }
+        if (q0 < q1) fetch(o0, q0);
+        if (q0 + 1 < q1) fetch(o1, q0 + 1);
         uint32_t q = q0;
         for (; q + 2 <= q1; q += 2) {
             mma(o0);
@@ -285,14 +277,11 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16f(SpmmArgs a) {
                 double w0, w1;          // rows 4 lr + e of column lc: two quads of the shadow vector's hash
                 if constexpr (HASH) { w0 = shadow_pick(hq[e >> 1], e & 1, 0); w1 = shadow_pick(hq[e >> 1], e & 1, 1); }
                 else { w0 = wr[e]; w1 = wi[e]; }
-                double const dr = nr[e], di = ni[e];
-                part[0] = __builtin_fma(-di, w1, __builtin_fma(dr, w0, part[0]));
-                part[1] = __builtin_fma(di, w0, __builtin_fma(dr, w1, part[1]));
-                if constexpr (EPI == EPI_AXPY_NRM_DOT) part[2] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[2]));
+                epi_dot(part[0], part[1], nr[e], ni[e], w0, w1);
+                if constexpr (EPI == EPI_AXPY_NRM_DOT) epi_nrm(part[2], nr[e], ni[e]);
             } else if constexpr (EPI == EPI_RESIDUAL) {     // |A x - b|^2, nothing stored (tfqmrgpu_core.hxx:265-269)
                 R const rr = yr[e] + R(-1) * br[e], ri = yi[e] + R(-1) * bi[e];
-                double const dr = rr, di = ri;
-                part[0] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[0]));
+                epi_nrm(part[0], rr, ri);
             }
         }
         if constexpr (EPI != EPI_RESIDUAL) { __builtin_nontemporal_store(yr, (f4v*)((R*)a.Y + yoff)); __builtin_nontemporal_store(yi, (f4v*)((R*)a.Y + yoff + P)); }

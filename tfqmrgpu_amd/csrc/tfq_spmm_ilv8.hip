@@ -1,5 +1,5 @@
 // The 8-row kernels: k_spmm_ilv8, k_spmm_ilv8b, k_spmm_ilv8w, k_spmm_ilv8f on the interleaved orders, k_spmm_mfma8 (tfq_spmm.hpp)
-#include "tfq_spmm.hpp"
+#include "tfq_spmm_ilv.hpp"
 
 namespace tfq {
 
@@ -13,8 +13,6 @@ namespace tfq {
 // of Re Y (c = 0) or Im Y (c = 1) -- the Y block, each epilogue operand and each result are again ONE access per wave.
 // Per Y block: 2 loads per block product + 2 (3) epilogue loads + 2 stores, against 4 per product + 8 + 4 eight-byte accesses and
 // an LDS round trip in k_spmm_mfma8.
-__device__ inline double xor8(double v) { return __shfl_xor(v, 8); }
-__device__ inline d2v xor8(d2v v) { return d2v{__shfl_xor(v[0], 8), __shfl_xor(v[1], 8)}; }
 
 template <int EPI, bool HASH, bool FIRST = false>   // FIRST: the launch of the first iteration of a solve (SpmmArgs::first)
 __global__ __launch_bounds__(256) void k_spmm_ilv8(SpmmArgs a) {
@@ -23,15 +21,10 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8(SpmmArgs a) {
     constexpr int LN = 8, P = 64, NPL = EpiPlanes<EPI>::N;
     constexpr bool UPD = (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT);
     using T4 = d4;
-    int const lane = threadIdx.x & 63;
-    int const wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int const lr = lane >> 4, lc = lane & 15, cp = lc >> 3, j = lc & 7;
-    using CU32 = __attribute__((address_space(4))) uint32_t const*;
-    CU32 const pairs = (CU32)(uintptr_t)a.pairs; CU32 const starts = (CU32)(uintptr_t)a.starts;
-    uint32_t const chunk = a.order ? a.order[blockIdx.x] : blockIdx.x;
-    uint32_t const first = a.chunkFirst[chunk], last = a.chunkFirst[chunk + 1], col = a.chunkCol[chunk];
+    ChunkWG const g(a);
+    int const lr = g.lane >> 4, lc = g.lane & 15, cp = lc >> 3, j = lc & 7;
     R sr = 0, si = 0;
-    if constexpr (UPD) { sr = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + j]; si = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + j]; }
+    if constexpr (UPD) { sr = ((R const*)a.sc)[(size_t(g.col) * 2 + 0) * LN + j]; si = ((R const*)a.sc)[(size_t(g.col) * 2 + 1) * LN + j]; }
     double part[NPL > 0 ? NPL : 1] = {};
     __shared__ double s[4][NPL > 0 ? NPL : 1][LN];
 
@@ -40,34 +33,22 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8(SpmmArgs a) {
     R const* const X0 = (R const*)a.X + mine;
     struct Ops { d2v av, xv; };
     auto fetch = [&](Ops& o, uint32_t q) __attribute__((always_inline)) {
-        o.av = *(d2v const*)(A0 + size_t(pairs[2 * size_t(q)]) * 2 * P);
-        o.xv = *(d2v const*)(X0 + size_t(pairs[2 * size_t(q) + 1]) * 2 * P);
+        o.av = *(d2v const*)(A0 + size_t(g.pairs[2 * size_t(q)]) * 2 * P);
+        o.xv = *(d2v const*)(X0 + size_t(g.pairs[2 * size_t(q) + 1]) * 2 * P);
     };
-    for (uint32_t u = wave; u < last - first; u += 4) {
-        uint32_t const y = first + u;
-        uint64_t const key = HASH ? shadow_key(uint32_t(a.origCol[col]), a.rowI[y]) : 0;
+    for (uint32_t u = g.wave; u < g.last - g.first; u += 4) {
+        uint32_t const y = g.first + u;
+        uint64_t const key = HASH ? shadow_key(uint32_t(a.origCol[g.col]), a.rowI[y]) : 0;
         T4 acc = T4{0, 0, 0, 0};
-        uint32_t const q0 = starts[y], nq = starts[y + 1] - q0;
+        uint32_t const q0 = g.starts[y], nq = g.starts[y + 1] - q0;
         constexpr int DEPTH = 4;
         Ops o[DEPTH];
-        constexpr bool EPI_FIRST = true;   // epilogue operands requested in front of the first products' operands: -1 % (profiles/r02_ab_traversal.txt)
-        if constexpr (!EPI_FIRST) {
-#pragma unroll
-            for (int dd = 0; dd < DEPTH; ++dd) if (uint32_t(dd) < nq) fetch(o[dd], q0 + dd);
-        }
         size_t const yoff = size_t(y) * 2 * P + mine;
-        d2v uM = d2v{0, 0}, vM = d2v{0, 0}; f2v wM = f2v{0, 0};
-        if constexpr (UPD) {                       // the epilogue operands travel while the products are computed
-            if constexpr (!(EPI == EPI_XPAY_DOT && FIRST)) {   // (first iteration of a solve: old v4 = v8 = 0, not read)
-            uM = __builtin_nontemporal_load((d2v const*)((R const*)a.e0 + yoff));
-            if constexpr (EPI == EPI_XPAY_DOT) vM = __builtin_nontemporal_load((d2v const*)((R const*)a.e1 + yoff));
-            }
-            if constexpr (!HASH) wM = __builtin_nontemporal_load((f2v const*)(a.v3 + yoff));
-        }
-        if constexpr (EPI_FIRST) {
+        // the epilogue operands travel while the products are computed, requested in front of the first products' operands: -1 % (profiles/r02_ab_traversal.txt)
+        EpiPiece<d2v> eo;
+        eo.template load<EPI, FIRST, HASH>(a, yoff);
 #pragma unroll
-            for (int dd = 0; dd < DEPTH; ++dd) if (uint32_t(dd) < nq) fetch(o[dd], q0 + dd);
-        }
+        for (int dd = 0; dd < DEPTH; ++dd) if (uint32_t(dd) < nq) fetch(o[dd], q0 + dd);
         for (uint32_t base = 0; base < nq; base += DEPTH) {
 #pragma unroll
             for (int dd = 0; dd < DEPTH; ++dd) {
@@ -81,42 +62,32 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8(SpmmArgs a) {
         // lanes of plane 0 hold (Q00, Q10), lanes of plane 1 (Q01, Q11), rows 2 lr and 2 lr + 1: Re Y = Q00 - Q11, Im Y = Q01 + Q10
         d2v const qa = d2v{acc[0], acc[1]}, qb = xor8(d2v{acc[2], acc[3]});
         d2v const yM = cp ? d2v{qa[0] + qb[0], qa[1] + qb[1]} : d2v{qa[0] - qb[0], qa[1] - qb[1]};   // this lane's plane of Y
-        d2v const yO = xor8(yM);
-        d2v const yr = cp ? yO : yM, yi = cp ? yM : yO;
+        auto const [yr, yi] = planes(yM, xor8(yM), cp);
         if constexpr (UPD) {
-            d2v const uO = xor8(uM), ur = cp ? uO : uM, ui = cp ? uM : uO;
+            auto const [ur, ui] = planes(eo.u, xor8(eo.u), cp);
             d2v nr, ni;
-            d2v w0, w1;     // the shadow vector: Re and Im of the two elements
+            ReIm<d2v> w;    // the shadow vector: Re and Im of the two elements
             if constexpr (HASH) {
                 uint64_t const hq = shadow_quad(key, uint32_t(lr), uint32_t(j), LN);   // rows 2 lr, 2 lr + 1 of column j
 #pragma unroll
-                for (int e = 0; e < 2; ++e) { w0[e] = shadow_pick(hq, e, 0); w1[e] = shadow_pick(hq, e, 1); }
+                for (int e = 0; e < 2; ++e) { w.r[e] = shadow_pick(hq, e, 0); w.i[e] = shadow_pick(hq, e, 1); }
             } else {
-                f2v const wO = f2v{__shfl_xor(wM[0], 8), __shfl_xor(wM[1], 8)};
-                w0 = cp ? d2v{wO[0], wO[1]} : d2v{wM[0], wM[1]}; w1 = cp ? d2v{wM[0], wM[1]} : d2v{wO[0], wO[1]};
+                f2v const wM = eo.w, wO = xor8(wM);
+                d2v const wOd = d2v{wO[0], wO[1]}, wMd = d2v{wM[0], wM[1]};
+                w = planes(wMd, wOd, cp);
             }
             if constexpr (EPI == EPI_XPAY_DOT) {          // v9 := A v6; v4 := v8 + beta v4; v4 := v9 + beta v4 (tfqmrgpu_core.hxx:196-202)
-                d2v const vO = xor8(vM), vr = cp ? vO : vM, vi = cp ? vM : vO;
+                auto const [vr, vi] = planes(eo.v, xor8(eo.v), cp);
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    R const tr = __builtin_fma(-si, ui[e], __builtin_fma(sr, ur[e], vr[e]));
-                    R const ti = __builtin_fma(sr, ui[e], __builtin_fma(si, ur[e], vi[e]));
-                    nr[e] = __builtin_fma(-si, ti, __builtin_fma(sr, tr, yr[e]));
-                    ni[e] = __builtin_fma(sr, ti, __builtin_fma(si, tr, yi[e]));
-                }
+                for (int e = 0; e < 2; ++e) { R a, b; epi_xpay2(a, b, yr[e], yi[e], ur[e], ui[e], vr[e], vi[e], sr, si); nr[e] = a; ni[e] = b; }
             } else {                                      // v8 := A v6; v5 := alfa v8 + v5 (tfqmrgpu_core.hxx:224-228)
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    nr[e] = __builtin_fma(-si, yi[e], __builtin_fma(sr, yr[e], ur[e]));
-                    ni[e] = __builtin_fma(sr, yi[e], __builtin_fma(si, yr[e], ui[e]));
-                }
+                for (int e = 0; e < 2; ++e) { R a, b; epi_axpy(a, b, yr[e], yi[e], ur[e], ui[e], sr, si); nr[e] = a; ni[e] = b; }
             }
 #pragma unroll
             for (int e = 0; e < 2; ++e) {                 // every lane has both parts: the lanes of plane 0 are the ones that count
-                double const dr = nr[e], di = ni[e];
-                part[0] = __builtin_fma(-di, w1[e], __builtin_fma(dr, w0[e], part[0]));
-                part[1] = __builtin_fma(di, w0[e], __builtin_fma(dr, w1[e], part[1]));
-                if constexpr (EPI == EPI_AXPY_NRM_DOT) part[2] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[2]));
+                epi_dot(part[0], part[1], nr[e], ni[e], w.r[e], w.i[e]);
+                if constexpr (EPI == EPI_AXPY_NRM_DOT) epi_nrm(part[2], nr[e], ni[e]);
             }
             __builtin_nontemporal_store(yM, (d2v*)((R*)a.Y + yoff));
             __builtin_nontemporal_store(cp ? ni : nr, (d2v*)((R*)a.e0 + yoff));
@@ -124,12 +95,9 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8(SpmmArgs a) {
             uint32_t const bq = a.bOfX ? a.bOfX[y] : y;
             d2v bM = d2v{0, 0};
             if (bq != 0xffffffffu) bM = *(d2v const*)((R const*)a.B + size_t(bq) * 2 * P + mine);
-            d2v const bO = xor8(bM), br = cp ? bO : bM, bi = cp ? bM : bO;
+            auto const [br, bi] = planes(bM, xor8(bM), cp);
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                double const dr = yr[e] + R(-1) * br[e], di = yi[e] + R(-1) * bi[e];
-                part[0] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[0]));
-            }
+            for (int e = 0; e < 2; ++e) epi_nrm(part[0], yr[e] + R(-1) * br[e], yi[e] + R(-1) * bi[e]);
         } else {
             __builtin_nontemporal_store(yM, (d2v*)((R*)a.Y + yoff));
         }
@@ -141,15 +109,15 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8(SpmmArgs a) {
             double v = part[p];
             v += __shfl_xor(v, 16);
             v += __shfl_xor(v, 32);
-            if (lane < 8) s[wave][p][lane] = v;
+            if (g.lane < 8) s[g.wave][p][g.lane] = v;
         }
         __syncthreads();
         for (int e = threadIdx.x; e < NPL * LN; e += 256) {
             int const p = e / LN, jj = e % LN;
             double const sum = ((s[0][p][jj] + s[1][p][jj]) + s[2][p][jj]) + s[3][p][jj];
-            write_record<EPI>(a, chunk, LN, p, jj, sum);
+            write_record<EPI>(a, g.chunk, LN, p, jj, sum);
         }
-        if (a.foldPlan) spmm_fold<R, LN, EPI>(a, col);   // small systems: the column operation behind this multiply, in the last work group of the column
+        if (a.foldPlan) spmm_fold<R, LN, EPI>(a, g.col);   // small systems: the column operation behind this multiply, in the last work group of the column
     }
 }
 
@@ -166,14 +134,9 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
     constexpr int LN = 8, P = 64, NPL = EpiPlanes<EPI>::N;
     constexpr bool UPD = (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT);
     using T4 = d4;
-    int const lane = threadIdx.x & 63;
-    int const wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int const lr = lane >> 4, lc = lane & 15, cp = lc >> 3, j = lc & 7;
-    using CU32 = __attribute__((address_space(4))) uint32_t const*;
-    CU32 const pairs = (CU32)(uintptr_t)a.pairs; CU32 const starts = (CU32)(uintptr_t)a.starts;
-    uint32_t const chunk = a.order ? a.order[blockIdx.x] : blockIdx.x;
-    uint32_t const first = a.chunkFirst[chunk], last = a.chunkFirst[chunk + 1], col = a.chunkCol[chunk];
-    uint32_t const cb = a.colBatch[col];
+    ChunkWG const g(a);
+    int const lr = g.lane >> 4, lc = g.lane & 15, cp = lc >> 3, j = lc & 7;
+    uint32_t const cb = a.colBatch[g.col];
     if (cb & 15u) return;                       // (a later column of a batch: not in this launch's order, SpmmArgs::order = DevPlan::orderB)
     int const nb = int(cb >> 4);                // 1 ... NB columns
     uint32_t dBlk[NB], dChk[NB];                // how far the blocks / chunks of column col + k lie behind those of column col
@@ -182,8 +145,8 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
     for (int k = 0; k < NB; ++k) {
         dBlk[k] = 0; dChk[k] = 0; sr[k] = 0; si[k] = 0;
         if (k < nb) {
-            dBlk[k] = a.colStart[col + k] - a.colStart[col]; dChk[k] = a.colChunkPtr[col + k] - a.colChunkPtr[col];
-            if constexpr (UPD) { sr[k] = ((R const*)a.sc)[(size_t(col + k) * 2 + 0) * LN + j]; si[k] = ((R const*)a.sc)[(size_t(col + k) * 2 + 1) * LN + j]; }
+            dBlk[k] = a.colStart[g.col + k] - a.colStart[g.col]; dChk[k] = a.colChunkPtr[g.col + k] - a.colChunkPtr[g.col];
+            if constexpr (UPD) { sr[k] = ((R const*)a.sc)[(size_t(g.col + k) * 2 + 0) * LN + j]; si[k] = ((R const*)a.sc)[(size_t(g.col + k) * 2 + 1) * LN + j]; }
         }
     }
     double part[NB][NPL > 0 ? NPL : 1] = {};
@@ -194,17 +157,17 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
     R const* const X0 = (R const*)a.X + mine;
     struct Ops { d2v av; d2v xv[NB]; };
     auto fetch = [&](Ops& o, uint32_t q) __attribute__((always_inline)) {
-        o.av = *(d2v const*)(A0 + size_t(pairs[2 * size_t(q)]) * 2 * P);
-        uint32_t const xb = pairs[2 * size_t(q) + 1];
+        o.av = *(d2v const*)(A0 + size_t(g.pairs[2 * size_t(q)]) * 2 * P);
+        uint32_t const xb = g.pairs[2 * size_t(q) + 1];
 #pragma unroll
         for (int k = 0; k < NB; ++k) if (k < nb) o.xv[k] = *(d2v const*)(X0 + size_t(xb + dBlk[k]) * 2 * P);
     };
-    for (uint32_t u = wave; u < last - first; u += 4) {
-        uint32_t const y = first + u;
+    for (uint32_t u = g.wave; u < g.last - g.first; u += 4) {
+        uint32_t const y = g.first + u;
         T4 acc[NB];
 #pragma unroll
         for (int k = 0; k < NB; ++k) acc[k] = T4{0, 0, 0, 0};
-        uint32_t const q0 = starts[y], nq = starts[y + 1] - q0;
+        uint32_t const q0 = g.starts[y], nq = g.starts[y + 1] - q0;
         constexpr int DEPTH = 2;   // block products in flight (3 | 4 measured level or slower, profiles/r03_column_batches.txt)
         Ops o[DEPTH];
 #pragma unroll
@@ -225,34 +188,28 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
 #pragma unroll
         for (int k = 0; k < NB; ++k) if (k < nb) {
             size_t const yoff = size_t(y + dBlk[k]) * 2 * P + mine;
-            d2v uMk = d2v{0, 0}, vMk = d2v{0, 0}; f2v wMk = f2v{0, 0};
-            if constexpr (UPD) {   // (requested here, not in front of the products: measured better with two columns per wave)
-                if constexpr (!(EPI == EPI_XPAY_DOT && FIRST)) {   // (first iteration of a solve: old v4 = v8 = 0, not read)
-                    uMk = __builtin_nontemporal_load((d2v const*)((R const*)a.e0 + yoff));
-                    if constexpr (EPI == EPI_XPAY_DOT) vMk = __builtin_nontemporal_load((d2v const*)((R const*)a.e1 + yoff));
-                }
-                if constexpr (!HASH) wMk = __builtin_nontemporal_load((f2v const*)(a.v3 + yoff));
-            }
+            EpiPiece<d2v> eo;
+            eo.template load<EPI, FIRST, HASH>(a, yoff);   // (requested here, not in front of the products: measured better with two columns per wave)
             // lanes of plane 0 hold (Q00, Q10), lanes of plane 1 (Q01, Q11), rows 2 lr and 2 lr + 1: Re Y = Q00 - Q11, Im Y = Q01 + Q10
             d2v const qa = d2v{acc[k][0], acc[k][1]}, qb = xor8(d2v{acc[k][2], acc[k][3]});
             d2v const yM = cp ? d2v{qa[0] + qb[0], qa[1] + qb[1]} : d2v{qa[0] - qb[0], qa[1] - qb[1]};   // this lane's plane of Y
-            d2v const yO = xor8(yM);
-            d2v const yr = cp ? yO : yM, yi = cp ? yM : yO;
+            auto const [yr, yi] = planes(yM, xor8(yM), cp);
             if constexpr (UPD) {
-                d2v const uO = xor8(uMk), ur = cp ? uO : uMk, ui = cp ? uMk : uO;
+                auto const [ur, ui] = planes(eo.u, xor8(eo.u), cp);
                 d2v nr, ni;
-                d2v w0, w1;     // the shadow vector: Re and Im of the two elements
+                ReIm<d2v> w;    // the shadow vector: Re and Im of the two elements
                 if constexpr (HASH) {
-                    uint64_t const key = shadow_key(uint32_t(a.origCol[col + k]), a.rowI[y]);   // (the batch's columns have the same block rows)
+                    uint64_t const key = shadow_key(uint32_t(a.origCol[g.col + k]), a.rowI[y]);   // (the batch's columns have the same block rows)
                     uint64_t const hq = shadow_quad(key, uint32_t(lr), uint32_t(j), LN);       // rows 2 lr, 2 lr + 1 of column j
 #pragma unroll
-                    for (int e = 0; e < 2; ++e) { w0[e] = shadow_pick(hq, e, 0); w1[e] = shadow_pick(hq, e, 1); }
+                    for (int e = 0; e < 2; ++e) { w.r[e] = shadow_pick(hq, e, 0); w.i[e] = shadow_pick(hq, e, 1); }
                 } else {
-                    f2v const wO = f2v{__shfl_xor(wMk[0], 8), __shfl_xor(wMk[1], 8)};
-                    w0 = cp ? d2v{wO[0], wO[1]} : d2v{wMk[0], wMk[1]}; w1 = cp ? d2v{wMk[0], wMk[1]} : d2v{wO[0], wO[1]};
+                    f2v const wM = eo.w, wO = xor8(wM);
+                    d2v const wOd = d2v{wO[0], wO[1]}, wMd = d2v{wM[0], wM[1]};
+                    w = planes(wMd, wOd, cp);
                 }
                 if constexpr (EPI == EPI_XPAY_DOT) {          // v9 := A v6; v4 := v8 + beta v4; v4 := v9 + beta v4 (tfqmrgpu_core.hxx:196-202)
-                    d2v const vO = xor8(vMk), vr = cp ? vO : vMk, vi = cp ? vMk : vO;
+                    auto const [vr, vi] = planes(eo.v, xor8(eo.v), cp);
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
                         R const tr = __builtin_fma(-si[k], ui[e], __builtin_fma(sr[k], ur[e], vr[e]));
@@ -269,10 +226,8 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
                 }
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {                 // every lane has both parts: the lanes of plane 0 are the ones that count
-                    double const dr = nr[e], di = ni[e];
-                    part[k][0] = __builtin_fma(-di, w1[e], __builtin_fma(dr, w0[e], part[k][0]));
-                    part[k][1] = __builtin_fma(di, w0[e], __builtin_fma(dr, w1[e], part[k][1]));
-                    if constexpr (EPI == EPI_AXPY_NRM_DOT) part[k][2] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[k][2]));
+                    epi_dot(part[k][0], part[k][1], nr[e], ni[e], w.r[e], w.i[e]);
+                    if constexpr (EPI == EPI_AXPY_NRM_DOT) epi_nrm(part[k][2], nr[e], ni[e]);
                 }
                 __builtin_nontemporal_store(yM, (d2v*)((R*)a.Y + yoff));
                 __builtin_nontemporal_store(cp ? ni : nr, (d2v*)((R*)a.e0 + yoff));
@@ -280,12 +235,9 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
                 uint32_t const bq = a.bOfX ? a.bOfX[y + dBlk[k]] : y + dBlk[k];
                 d2v bM = d2v{0, 0};
                 if (bq != 0xffffffffu) bM = *(d2v const*)((R const*)a.B + size_t(bq) * 2 * P + mine);
-                d2v const bO = xor8(bM), br = cp ? bO : bM, bi = cp ? bM : bO;
+                auto const [br, bi] = planes(bM, xor8(bM), cp);
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    double const dr = yr[e] + R(-1) * br[e], di = yi[e] + R(-1) * bi[e];
-                    part[k][0] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[k][0]));
-                }
+                for (int e = 0; e < 2; ++e) epi_nrm(part[k][0], yr[e] + R(-1) * br[e], yi[e] + R(-1) * bi[e]);
             } else {
                 __builtin_nontemporal_store(yM, (d2v*)((R*)a.Y + yoff));
             }
@@ -300,7 +252,7 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
                 double v = part[k][p];
                 v += __shfl_xor(v, 16);
                 v += __shfl_xor(v, 32);
-                if (lane < 8) s[k][wave][p][lane] = v;
+                if (g.lane < 8) s[k][g.wave][p][g.lane] = v;
             }
         __syncthreads();
         for (int e = threadIdx.x; e < NB * NPL * LN; e += 256) {
@@ -310,7 +262,7 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
                 uint32_t dc = dChk[0];
 #pragma unroll
                 for (int kk = 1; kk < NB; ++kk) if (kk == k) dc = dChk[kk];
-                write_record<EPI>(a, chunk + dc, LN, p, jj, sum);
+                write_record<EPI>(a, g.chunk + dc, LN, p, jj, sum);
             }
         }
     }
@@ -335,13 +287,8 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
     constexpr int P = 8 * LN, PA = 64, NPL = EpiPlanes<EPI>::N;
     constexpr bool UPD = (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT);
     using T4 = d4;
-    int const lane = threadIdx.x & 63;
-    int const wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int const lr = lane >> 4, lc = lane & 15, cp = lc >> 3, j = lc & 7;
-    using CU32 = __attribute__((address_space(4))) uint32_t const*;
-    CU32 const pairs = (CU32)(uintptr_t)a.pairs; CU32 const starts = (CU32)(uintptr_t)a.starts;
-    uint32_t const chunk = a.order ? a.order[blockIdx.x] : blockIdx.x;
-    uint32_t const first = a.chunkFirst[chunk], last = a.chunkFirst[chunk + 1], col = a.chunkCol[chunk];
+    ChunkWG const g(a);
+    int const lr = g.lane >> 4, lc = g.lane & 15, cp = lc >> 3, j = lc & 7;
     double part[NPL > 0 ? NPL : 1][NT] = {};
     __shared__ double s[4][NPL > 0 ? NPL : 1][LN];
     if constexpr (NPL > 0) {   // (8 x 64: a wave meets both halves of the columns only if it has at least two units: clear what it may not write)
@@ -354,22 +301,22 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
     // units u = wave, wave + 4, ...: unit u is (Y block u / HALVES, half u % HALVES of its column groups); 4 is a multiple of HALVES,
     // so a wave keeps its half
     static_assert(4 % HALVES == 0, "a wave keeps its half of the column groups");
-    int const t0 = (wave % HALVES) * NT;                  // first column group of this wave's units
+    int const t0 = (g.wave % HALVES) * NT;                  // first column group of this wave's units
     // this lane's 16 bytes of column group t0 + t of an X-shaped block: plane cp, row pair lr, column 8 (t0 + t) + j
     auto mine = [&](int t) { return cp * P + (lr * LN + 8 * (t0 + t) + j) * 2; };
     auto live = [&](int t) { return !RAGGED || 8 * (t0 + t) + j < LN; };      // this lane's column of group t exists
     auto fetch = [&](Ops& o, uint32_t q) __attribute__((always_inline)) {
-        o.av = *(d2v const*)(A0 + size_t(pairs[2 * size_t(q)]) * 2 * PA);
-        R const* Xb = (R const*)a.X + size_t(pairs[2 * size_t(q) + 1]) * 2 * P;
+        o.av = *(d2v const*)(A0 + size_t(g.pairs[2 * size_t(q)]) * 2 * PA);
+        R const* Xb = (R const*)a.X + size_t(g.pairs[2 * size_t(q) + 1]) * 2 * P;
 #pragma unroll
         for (int t = 0; t < NT; ++t) o.xv[t] = live(t) ? *(d2v const*)(Xb + mine(t)) : d2v{0, 0};
     };
-    for (uint32_t u = wave; u < (last - first) * HALVES; u += 4) {
-        uint32_t const y = first + u / HALVES;
+    for (uint32_t u = g.wave; u < (g.last - g.first) * HALVES; u += 4) {
+        uint32_t const y = g.first + u / HALVES;
         T4 acc[NT];
 #pragma unroll
         for (int t = 0; t < NT; ++t) acc[t] = T4{0, 0, 0, 0};
-        uint32_t const q0 = starts[y], q1 = starts[y + 1];
+        uint32_t const q0 = g.starts[y], q1 = g.starts[y + 1];
         auto mma = [&](Ops const& o) __attribute__((always_inline)) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -416,11 +363,10 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
             // lanes of plane 0 hold (Q00, Q10), lanes of plane 1 (Q01, Q11), rows 2 lr and 2 lr + 1: Re Y = Q00 - Q11, Im Y = Q01 + Q10
             d2v const qa = d2v{acc[t][0], acc[t][1]}, qb = xor8(d2v{acc[t][2], acc[t][3]});
             d2v const yM = cp ? d2v{qa[0] + qb[0], qa[1] + qb[1]} : d2v{qa[0] - qb[0], qa[1] - qb[1]};   // this lane's plane of Y
-            d2v const yO = xor8(yM);
-            d2v const yr = cp ? yO : yM, yi = cp ? yM : yO;
+            auto const [yr, yi] = planes(yM, xor8(yM), cp);
             if constexpr (UPD) {
-                R const srt = on ? ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + 8 * (t0 + t) + j] : R(0);
-                R const sit = on ? ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + 8 * (t0 + t) + j] : R(0);
+                R const srt = on ? ((R const*)a.sc)[(size_t(g.col) * 2 + 0) * LN + 8 * (t0 + t) + j] : R(0);
+                R const sit = on ? ((R const*)a.sc)[(size_t(g.col) * 2 + 1) * LN + 8 * (t0 + t) + j] : R(0);
                 d2v uM = d2v{0, 0}, vM = d2v{0, 0}; f2v wM = f2v{0, 0};
                 if constexpr (PRE) { uM = uP[t]; vM = vP[t]; wM = wP[t]; }
                 else {
@@ -430,12 +376,13 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
                     }
                     if (on) wM = ld_stream<!RAGGED>((f2v const*)(a.v3 + yoff));
                 }
-                d2v const uO = xor8(uM), ur = cp ? uO : uM, ui = cp ? uM : uO;
-                f2v const wO = f2v{__shfl_xor(wM[0], 8), __shfl_xor(wM[1], 8)};
-                d2v const w0 = cp ? d2v{wO[0], wO[1]} : d2v{wM[0], wM[1]}, w1 = cp ? d2v{wM[0], wM[1]} : d2v{wO[0], wO[1]};
+                auto const [ur, ui] = planes(uM, xor8(uM), cp);
+                f2v const wO = xor8(wM);
+                d2v const wOd = d2v{wO[0], wO[1]}, wMd = d2v{wM[0], wM[1]};
+                auto const [w0, w1] = planes(wMd, wOd, cp);
                 d2v nr, ni;
                 if constexpr (EPI == EPI_XPAY_DOT) {          // v9 := A v6; v4 := v8 + beta v4; v4 := v9 + beta v4 (tfqmrgpu_core.hxx:196-202)
-                    d2v const vO = xor8(vM), vr = cp ? vO : vM, vi = cp ? vM : vO;
+                    auto const [vr, vi] = planes(vM, xor8(vM), cp);
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
                         R const tr = __builtin_fma(-sit, ui[e], __builtin_fma(srt, ur[e], vr[e]));
@@ -452,10 +399,8 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
                 }
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {                 // every lane has both parts: the lanes of plane 0 are the ones that count
-                    double const dr = nr[e], di = ni[e];
-                    part[0][t] = __builtin_fma(-di, w1[e], __builtin_fma(dr, w0[e], part[0][t]));
-                    part[1][t] = __builtin_fma(di, w0[e], __builtin_fma(dr, w1[e], part[1][t]));
-                    if constexpr (EPI == EPI_AXPY_NRM_DOT) part[2][t] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[2][t]));
+                    epi_dot(part[0][t], part[1][t], nr[e], ni[e], w0[e], w1[e]);
+                    if constexpr (EPI == EPI_AXPY_NRM_DOT) epi_nrm(part[2][t], nr[e], ni[e]);
                 }
                 if (on) {
                     st_stream<!RAGGED>((d2v*)((R*)a.Y + yoff), yM);
@@ -464,12 +409,9 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
             } else if constexpr (EPI == EPI_RESIDUAL) {       // |A x - b|^2, nothing stored (tfqmrgpu_core.hxx:265-269)
                 d2v bM = d2v{0, 0};
                 if (bq != 0xffffffffu && on) bM = *(d2v const*)((R const*)a.B + size_t(bq) * 2 * P + mine(t));
-                d2v const bO = xor8(bM), br = cp ? bO : bM, bi = cp ? bM : bO;
+                auto const [br, bi] = planes(bM, xor8(bM), cp);
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    double const dr = yr[e] + R(-1) * br[e], di = yi[e] + R(-1) * bi[e];
-                    part[0][t] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[0][t]));
-                }
+                for (int e = 0; e < 2; ++e) epi_nrm(part[0][t], yr[e] + R(-1) * br[e], yi[e] + R(-1) * bi[e]);
             } else {
                 if (on) st_stream<!RAGGED>((d2v*)((R*)a.Y + yoff), yM);
             }
@@ -484,15 +426,15 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
                 double v = part[p][t];
                 v += __shfl_xor(v, 16);
                 v += __shfl_xor(v, 32);
-                if (lane < 8 && (!RAGGED || 8 * (t0 + t) + lane < LN)) s[wave][p][8 * (t0 + t) + lane] = v;
+                if (g.lane < 8 && (!RAGGED || 8 * (t0 + t) + g.lane < LN)) s[g.wave][p][8 * (t0 + t) + g.lane] = v;
             }
         __syncthreads();
         for (int e = threadIdx.x; e < NPL * LN; e += 256) {
             int const p = e / LN, jj = e % LN;
             double const sum = ((s[0][p][jj] + s[1][p][jj]) + s[2][p][jj]) + s[3][p][jj];
-            write_record<EPI>(a, chunk, LN, p, jj, sum);
+            write_record<EPI>(a, g.chunk, LN, p, jj, sum);
         }
-        if (a.foldPlan) spmm_fold<R, LN, EPI>(a, col);   // small systems: the column operation behind this multiply, in the last work group of the column
+        if (a.foldPlan) spmm_fold<R, LN, EPI>(a, g.col);   // small systems: the column operation behind this multiply, in the last work group of the column
     }
 }
 
@@ -588,8 +530,7 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8f(SpmmArgs a) {
             f4v const o = f4v{__shfl_xor(v[0], 40), __shfl_xor(v[1], 40), __shfl_xor(v[2], 40), __shfl_xor(v[3], 40)};
             // owners: plane 0: Re Y = Q00 - Q11, plane 1: Im Y = Q01 + Q10
             f4v const yM = cp ? f4v{v[0] + o[0], v[1] + o[1], v[2] + o[2], v[3] + o[3]} : f4v{v[0] - o[0], v[1] - o[1], v[2] - o[2], v[3] - o[3]};
-            f4v const yO = f4v{__shfl_xor(yM[0], 8), __shfl_xor(yM[1], 8), __shfl_xor(yM[2], 8), __shfl_xor(yM[3], 8)};   // the other plane of the same elements
-            f4v const yr = cp ? yO : yM, yi = cp ? yM : yO;
+            auto const [yr, yi] = planes(yM, xor8(yM), cp);
             size_t const yoff = yb + mine(t);
             if constexpr (UPD) {
                 R const srt = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + 8 * (t0 + t) + j];
@@ -603,11 +544,11 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8f(SpmmArgs a) {
                     wM = __builtin_nontemporal_load((f4v const*)(a.v3 + yoff));
                 }
                 auto x8 = [](f4v z) { return f4v{__shfl_xor(z[0], 8), __shfl_xor(z[1], 8), __shfl_xor(z[2], 8), __shfl_xor(z[3], 8)}; };
-                f4v const uO = x8(uM), ur = cp ? uO : uM, ui = cp ? uM : uO;
-                f4v const wO = x8(wM), w0 = cp ? wO : wM, w1 = cp ? wM : wO;
+                auto const [ur, ui] = planes(uM, x8(uM), cp);
+                auto const [w0, w1] = planes(wM, x8(wM), cp);
                 f4v nr, ni;
                 if constexpr (EPI == EPI_XPAY_DOT) {          // v9 := A v6; v4 := v8 + beta v4; v4 := v9 + beta v4 (tfqmrgpu_core.hxx:196-202)
-                    f4v const vO = x8(vM), vr = cp ? vO : vM, vi = cp ? vM : vO;
+                    auto const [vr, vi] = planes(vM, x8(vM), cp);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         R const tr = __builtin_fmaf(-sit, ui[e], __builtin_fmaf(srt, ur[e], vr[e]));
@@ -625,10 +566,8 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8f(SpmmArgs a) {
                 if (owner) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {             // every owner lane has both parts: the lanes of plane 0 are the ones that count
-                        double const dr = nr[e], di = ni[e], x0 = w0[e], x1 = w1[e];
-                        part[0][t] = __builtin_fma(-di, x1, __builtin_fma(dr, x0, part[0][t]));
-                        part[1][t] = __builtin_fma(di, x0, __builtin_fma(dr, x1, part[1][t]));
-                        if constexpr (EPI == EPI_AXPY_NRM_DOT) part[2][t] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[2][t]));
+                        epi_dot(part[0][t], part[1][t], nr[e], ni[e], w0[e], w1[e]);
+                        if constexpr (EPI == EPI_AXPY_NRM_DOT) epi_nrm(part[2][t], nr[e], ni[e]);
                     }
                     __builtin_nontemporal_store(yM, (f4v*)((R*)a.Y + yoff));
                     __builtin_nontemporal_store(cp ? ni : nr, (f4v*)((R*)a.e0 + yoff));
@@ -642,8 +581,7 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8f(SpmmArgs a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         R const rr = yr[e] + R(-1) * br[e], ri = yi[e] + R(-1) * bi[e];
-                        double const dr = rr, di = ri;
-                        part[0][t] = __builtin_fma(di, di, __builtin_fma(dr, dr, part[0][t]));
+                        epi_nrm(part[0][t], rr, ri);
                     }
                 }
             } else {

@@ -370,6 +370,16 @@ __global__ __launch_bounds__(256) void k_decide(DevPlan d, int what, int phase) 
 
 // ---- start of a solve ---------------------------------------------------------------------------
 // tau := |b|^2 per RHS, 1/|b|^2, rho := 1, everything else 0 (tfqmrgpu_core.hxx:121-127,154-166)
+// the control block
+__device__ inline void reset_ctl(Ctl* c, double tol, int maxIterations, int stallStop) {
+    double const tol2 = tol * tol;
+    c->tol2 = tol2; c->target_bound2 = tol2 * 100 * 100; c->max_bound2 = 0; c->residual2_reached = 1e300; c->probe_bound2 = 0;
+    for (int i = 0; i < 6; ++i) c->red[i] = 0;
+    c->iteration = 0; c->maxIterations = maxIterations;
+    c->state = (maxIterations > 0) ? 0 : 3;
+    c->probe = 0; c->iterations_needed = maxIterations; c->nprobes = 0; c->xpend = 0; c->stallStop = stallStop;
+}
+// tau := |b|^2 per RHS, 1/|b|^2, rho := 1, everything else 0 (tfqmrgpu_core.hxx:121-127,154-166)
 template <typename R, int LM, int LN>
 __global__ __launch_bounds__(256) void k_init_col(DevPlan d, double tol, int maxIterations) {
     constexpr int P = LM * LN;
@@ -403,15 +413,7 @@ __global__ __launch_bounds__(256) void k_init_col(DevPlan d, double tol, int max
         d.foldCount[col] = 0;
         if (0 == col) d.foldCount[d.nCols] = 0;
     }
-    if (0 == col && 0 == t) {
-        Ctl* c = d.ctl;
-        double const tol2 = tol * tol;
-        c->tol2 = tol2; c->target_bound2 = tol2 * 100 * 100; c->max_bound2 = 0; c->residual2_reached = 1e300; c->probe_bound2 = 0;
-        for (int i = 0; i < 6; ++i) c->red[i] = 0;
-        c->iteration = 0; c->maxIterations = maxIterations;
-        c->state = (maxIterations > 0) ? 0 : 3;
-        c->probe = 0; c->iterations_needed = maxIterations; c->nprobes = 0; c->xpend = 0; c->stallStop = 0;
-    }
+    if (0 == col && 0 == t) reset_ctl(d.ctl, tol, maxIterations, 0);
 }
 
 // ---- mixed precision 'm': the refinement around the float solves ---------------------------------------------------
@@ -557,15 +559,7 @@ __global__ __launch_bounds__(256) void k_refine_init_col(RefineArgs a) {
         d.foldCount[col] = 0;
         if (0 == col) d.foldCount[d.nCols] = 0;
     }
-    if (0 == col && 0 == t) {
-        Ctl* c = d.ctl;
-        double const tol2 = a.innerTol * a.innerTol;
-        c->tol2 = tol2; c->target_bound2 = tol2 * 100 * 100; c->max_bound2 = 0; c->residual2_reached = 1e300; c->probe_bound2 = 0;
-        for (int i = 0; i < 6; ++i) c->red[i] = 0;
-        c->iteration = 0; c->maxIterations = a.innerMaxIt;
-        c->state = (a.innerMaxIt > 0) ? 0 : 3;
-        c->probe = 0; c->iterations_needed = a.innerMaxIt; c->nprobes = 0; c->xpend = 0; c->stallStop = 1;
-    }
+    if (0 == col && 0 == t) reset_ctl(d.ctl, a.innerTol, a.innerMaxIt, 1);   // (stallStop: the float iteration has a floor, Ctl::stallStop)
 }
 
 // max over the block columns -> refine[0], refine[1] (refine[2], "a rank failed", is the host's)
