@@ -616,6 +616,41 @@ def test_multiply_rows_with_more_products_than_the_index_patch_holds(torch_cuda,
     assert np.abs(dY.cpu().numpy() - want).max() <= eps * LM * 44, (size, prec)
 
 
+@pytest.mark.parametrize("prec,size", [("z", (4, 4)), ("z", (4, 8)), ("z", (4, 32)), ("z", (4, 5)), ("c", (4, 5)), ("c", (4, 4)), ("c", (4, 32))])
+def test_multiply_rows_with_exactly_the_products_the_index_patch_holds(torch_cuda, oracle, prec, size):
+    """Two work groups of the plain mode on the limit of the LDS index patch (tfq_spmm.hpp: IndexPatch): the rows of the first hold exactly kPairs
+    products (the patch, up to its last slot), the second has the same pair lists row for row and one product more in its last row (kPairs + 1: indices
+    from global memory).  Both against the oracle, and every row of the second but its last equals its counterpart bit for bit: same sums, same order"""
+    torch = torch_cuda
+    LM, LN = size
+    rows = 16 if (prec, size) == ("z", (4, 32)) else 64   # Y blocks per work group (tfq_spmm.hip: multiply_chunk)
+    k_pairs = 1024 if prec == "z" and LN % 4 == 0 else 2048   # k_spmm_m4: 1024; k_spmm_small4 (4 x 5) and k_spmm_s4w (4 x 4 | 32 c): 2048
+    per = k_pairs // rows                                  # products per row: 16 | 64 (k_spmm_m4), 32; one more in the first row, one fewer in the last
+    rng = np.random.default_rng(LM * 1000 + LN)
+    nY, nA = 2 * rows, 31
+    first = rng.integers(0, [nA, nY], (rows * per, 2))     # (A block, X block) of every product of the first work group
+    count = np.full(rows, per); count[0] += 1; count[-1] -= 1   # kPairs in all; the last row ends on the last slot with a length (15 | 31 | 63) that is
+                                                           # no multiple of a batch (4 | 6 | 8 products), so its last batch reads past the row: the clamped slot
+    extra = [int(rng.integers(0, nA)), int(rng.integers(0, nY))]
+    pairs = np.concatenate([first.ravel(), first.ravel(), extra]).astype(np.uint32)
+    starts = np.concatenate([[0], np.cumsum(np.concatenate([count, count[:-1], [count[-1] + 1]]))]).astype(np.uint32)
+    assert starts[rows] - starts[0] == k_pairs and starts[2 * rows] - starts[rows] == k_pairs + 1
+    real = np.float64 if prec == "z" else np.float32
+    A = rng.uniform(-1, 1, (nA, 2, LM, LM)).astype(real)
+    X = rng.uniform(-1, 1, (nY, 2, LM, LN)).astype(real)
+    want = oracle.spmm(prec, LM, LN, starts, pairs, A, X)
+    dA, dX = torch.from_numpy(A).cuda(), torch.from_numpy(X).cuda()
+    dS, dP = torch.from_numpy(starts.view(np.int32)).cuda(), torch.from_numpy(pairs.view(np.int32)).cuda()
+    dY = torch.full((nY, 2, LM, LN), 7.0, dtype=dA.dtype, device="cuda")
+    with T.Solver() as s:
+        assert T.lib.tfqmrgpuExt_multiply(s.handle, prec.encode(), LM, LN, nY, dS.data_ptr(), dP.data_ptr(), dA.data_ptr(), dX.data_ptr(), dY.data_ptr()) == 0
+        torch.cuda.synchronize()
+    got = dY.cpu().numpy()
+    eps = 1e-13 if prec == "z" else 2e-5
+    assert np.abs(got - want).max() <= eps * LM * (per + 1), (size, prec)
+    assert np.array_equal(got[rows:2 * rows - 1], got[:rows - 1]), (size, prec)
+
+
 @pytest.mark.parametrize("prec", ["z", "c"])
 @pytest.mark.parametrize("shape", [(16, 16), (8, 8), (4, 5), (4, 4), (4, 8), (4, 32), (8, 9), (8, 10), (8, 32), (8, 64), (16, 32), (32, 32), (16, 64), (32, 64), (64, 64)])   # all 15 shapes
 def test_apply_operator_on_plan_data(oracle, prec, shape):

@@ -28,8 +28,8 @@ __global__ __launch_bounds__(256) void k_spmm_direct(SpmmArgs a) {
     int const j = e0 % LN;                           // 256 % LN == 0 whenever NACC > 1
     R sr = 0, si = 0;
     if constexpr (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT) {
-        sr = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + j];
-        si = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + j];
+        sr = epi_scalar<R>(a, col, LN, 0, j);
+        si = epi_scalar<R>(a, col, LN, 1, j);
     }
     double part[NPL > 0 ? NPL : 1] = {};
 
@@ -59,8 +59,7 @@ __global__ __launch_bounds__(256) void k_spmm_direct(SpmmArgs a) {
                 yr[n] += cr; yi[n] += ci;
             }
         }
-        uint32_t bq = 0xffffffffu;
-        if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
+        uint32_t const bq = rhs_block<EPI>(a, y);
 #pragma unroll
         for (int n = 0; n < NACC; ++n) {
             int const e = e0 + n * 256;

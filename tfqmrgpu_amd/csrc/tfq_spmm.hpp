@@ -26,6 +26,11 @@
 // This header: what the kernels of every family share (launch arguments, epilogue arithmetic, operand and stream helpers), the shapes each
 // family takes and the family launchers.  tfq_spmm_ilv.hpp: what only the kernels on the interleaved orders share (work-group prologue, the
 // epilogue operands of a 16-byte piece, the plane exchange).
+// Three pieces below follow the rule of tfq_spmm_ilv.hpp -- a kernel uses one only where every instance keeps its assembly with it
+// (scripts/isa_compare.sh against the parent commit), elsewhere the block stays written out in the kernel:
+//   epi_scalar             k_spmm_small4, k_spmm_m4, k_spmm_s4w, k_spmm_ilv16, k_spmm_ilv16f, k_spmm_ilv8, k_spmm_mfma, k_spmm_direct
+//   rhs_block              k_spmm_small4, k_spmm_m4, k_spmm_s4w, k_spmm_ilv16, k_spmm_ilv16f, k_spmm_ilv8b, k_spmm_ilv8w, k_spmm_ilv8f, k_spmm_direct
+//   IndexPatch             k_spmm_small4, k_spmm_m4, k_spmm_s4w (limits, row ranges, clamped pair read; the staging loops written out)
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -175,6 +180,39 @@ __device__ inline bool gate_closed(SpmmArgs const& a) {
     if (a.ctl->state != 0) return true;
     return (a.gate == 2 && a.ctl->probe == 0);
 }
+
+// The scalar of an updating epilogue for right-hand side j of block column col: its real (im = 0) or imaginary (im = 1) part
+template <typename R> __device__ __forceinline__ R epi_scalar(SpmmArgs const& a, uint32_t col, int LN, int im, int j) {
+    return ((R const*)a.sc)[(size_t(col) * 2 + im) * LN + j];
+}
+
+// EPI_RESIDUAL: the block of B that belongs to Y block y (every other epilogue: none)
+template <int EPI> __device__ __forceinline__ uint32_t rhs_block(SpmmArgs const& a, uint32_t y) {
+    if constexpr (EPI == EPI_RESIDUAL) return a.bOfX ? a.bOfX[y] : y;
+    return 0xffffffffu;
+}
+
+// The index patch of the 4-row kernels: the row ranges and index pairs of a whole chunk, fetched into LDS once, so that a batch of products waits
+// for one memory latency.  This struct holds the limits and the reads; the kernel declares the two arrays (Starts, Pairs), hands them to the reads
+// and, where inLds, fills them -- starts[i] = a.starts[first + i] for i <= nRows, pairs[i] = a.pairs[2 * qBase + i] for i < 2 * (qEnd - qBase) -- with a
+// barrier behind.  (Those two loops stay written out in the three kernels: as a constructor or member here they change the assembly.)
+// A chunk of more than kRows rows or kPairs pairs is not staged (!inLds): its kernel reads the lists from global memory
+template <uint32_t kPairs> struct IndexPatch {
+    static constexpr uint32_t kRows = 256;
+    using Starts = uint32_t[kRows + 1]; using Pairs = uint32_t[2 * kPairs];
+    uint32_t qBase, qEnd, nRows; bool inLds;   // the chunk's products are [qBase, qEnd) of the pair list
+    __device__ __forceinline__ IndexPatch(SpmmArgs const& a, uint32_t first, uint32_t last)
+        : qBase(a.starts[first]), qEnd(a.starts[last]), nRows(last - first) {      // (uniform: scalar loads)
+        inLds = (nRows <= kRows) && (qEnd - qBase <= kPairs);
+    }
+    // row kr of the chunk has the products [start(kr), start(kr + 1)), as positions in the patch
+    __device__ __forceinline__ uint32_t start(Starts const& starts, uint32_t kr) const { return starts[kr] - qBase; }
+    // (A block, X block) of product q; a q past the patch reads its last slot (unconditional: all reads of a batch in flight at once)
+    __device__ __forceinline__ static void pair(Pairs const& pairs, uint32_t q, uint32_t& ia, uint32_t& ix) {
+        uint32_t const qc = min(q, kPairs - 1);
+        ia = pairs[2 * qc]; ix = pairs[2 * qc + 1];
+    }
+};
 
 using d4 = __attribute__((ext_vector_type(4))) double;
 using f4 = __attribute__((ext_vector_type(4))) float;

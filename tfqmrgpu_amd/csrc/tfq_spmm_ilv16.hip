@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16(SpmmArgs a) {
     uint32_t const chunk = a.order ? a.order[blockIdx.x] : blockIdx.x;   // XCD-aware launch order (tfq_plan.cpp)
     uint32_t const first = a.chunkFirst[chunk], last = a.chunkFirst[chunk + 1], col = a.chunkCol[chunk];
     R sr = 0, si = 0;
-    if constexpr (UPD) { sr = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + lc]; si = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + lc]; }
+    if constexpr (UPD) { sr = epi_scalar<R>(a, col, LN, 0, lc); si = epi_scalar<R>(a, col, LN, 1, lc); }
     double part[NPL > 0 ? NPL : 1] = {};
     __shared__ double s[4][NPL > 0 ? NPL : 1][LN];
 
@@ -111,8 +111,7 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16(SpmmArgs a) {
         }
         if (q < q1) mma(o0);
 
-        uint32_t bq = 0xffffffffu;
-        if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
+        uint32_t const bq = rhs_block<EPI>(a, y);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             // the shadow vector recomputed: one hash for this pair of rows (tfq_device.hpp: shadow_quad).  Drawn here, inside the loop:
@@ -199,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16f(SpmmArgs a) {
     uint32_t const chunk = a.order ? a.order[blockIdx.x] : blockIdx.x;
     uint32_t const first = a.chunkFirst[chunk], last = a.chunkFirst[chunk + 1], col = a.chunkCol[chunk];
     R sr = 0, si = 0;
-    if constexpr (UPD) { sr = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + lc]; si = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + lc]; }
+    if constexpr (UPD) { sr = epi_scalar<R>(a, col, LN, 0, lc); si = epi_scalar<R>(a, col, LN, 1, lc); }
     double part[NPL > 0 ? NPL : 1] = {};
     __shared__ double s[4][NPL > 0 ? NPL : 1][LN];
 
@@ -257,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16f(SpmmArgs a) {
         f4v yr, yi, nr, ni;
         f4v br = f4v{0, 0, 0, 0}, bi = f4v{0, 0, 0, 0};
         if constexpr (EPI == EPI_RESIDUAL) {
-            uint32_t const bq = a.bOfX ? a.bOfX[y] : y;
+            uint32_t const bq = rhs_block<EPI>(a, y);
             if (bq != 0xffffffffu) { R const* b = (R const*)a.B + size_t(bq) * 2 * P + mine; br = *(f4v const*)b; bi = *(f4v const*)(b + P); }
         }
 #pragma unroll
@@ -341,7 +340,7 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilvf(SpmmArgs a) {   // two col
     if constexpr (UPD) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            sr[nt] = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + c0 + lc + 16 * nt];
+            sr[nt] = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + c0 + lc + 16 * nt];   // (written out: epi_scalar changes the assembly)
             si[nt] = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + c0 + lc + 16 * nt];
         }
     }
@@ -415,7 +414,7 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilvf(SpmmArgs a) {   // two col
             }
         }
 
-        uint32_t bq = 0xffffffffu;
+        uint32_t bq = 0xffffffffu;   // (written out: rhs_block changes the assembly)
         if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
 #pragma unroll
         for (int ms = 0; ms < MS; ++ms)

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8(SpmmArgs a) {
     ChunkWG const g(a);
     int const lr = g.lane >> 4, lc = g.lane & 15, cp = lc >> 3, j = lc & 7;
     R sr = 0, si = 0;
-    if constexpr (UPD) { sr = ((R const*)a.sc)[(size_t(g.col) * 2 + 0) * LN + j]; si = ((R const*)a.sc)[(size_t(g.col) * 2 + 1) * LN + j]; }
+    if constexpr (UPD) { sr = epi_scalar<R>(a, g.col, LN, 0, j); si = epi_scalar<R>(a, g.col, LN, 1, j); }
     double part[NPL > 0 ? NPL : 1] = {};
     __shared__ double s[4][NPL > 0 ? NPL : 1][LN];
 
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8(SpmmArgs a) {
             __builtin_nontemporal_store(yM, (d2v*)((R*)a.Y + yoff));
             __builtin_nontemporal_store(cp ? ni : nr, (d2v*)((R*)a.e0 + yoff));
         } else if constexpr (EPI == EPI_RESIDUAL) {       // |A x - b|^2, nothing stored (tfqmrgpu_core.hxx:265-269)
-            uint32_t const bq = a.bOfX ? a.bOfX[y] : y;
+            uint32_t const bq = a.bOfX ? a.bOfX[y] : y;   // (written out: rhs_block changes the assembly)
             d2v bM = d2v{0, 0};
             if (bq != 0xffffffffu) bM = *(d2v const*)((R const*)a.B + size_t(bq) * 2 * P + mine);
             auto const [br, bi] = planes(bM, xor8(bM), cp);
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
         dBlk[k] = 0; dChk[k] = 0; sr[k] = 0; si[k] = 0;
         if (k < nb) {
             dBlk[k] = a.colStart[g.col + k] - a.colStart[g.col]; dChk[k] = a.colChunkPtr[g.col + k] - a.colChunkPtr[g.col];
-            if constexpr (UPD) { sr[k] = ((R const*)a.sc)[(size_t(g.col + k) * 2 + 0) * LN + j]; si[k] = ((R const*)a.sc)[(size_t(g.col + k) * 2 + 1) * LN + j]; }
+            if constexpr (UPD) { sr[k] = ((R const*)a.sc)[(size_t(g.col + k) * 2 + 0) * LN + j]; si[k] = ((R const*)a.sc)[(size_t(g.col + k) * 2 + 1) * LN + j]; }   // (written out: epi_scalar changes the assembly)
         }
     }
     double part[NB][NPL > 0 ? NPL : 1] = {};
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256, 3) void k_spmm_ilv8b(SpmmArgs a) {
                 __builtin_nontemporal_store(yM, (d2v*)((R*)a.Y + yoff));
                 __builtin_nontemporal_store(cp ? ni : nr, (d2v*)((R*)a.e0 + yoff));
             } else if constexpr (EPI == EPI_RESIDUAL) {       // |A x - b|^2, nothing stored (tfqmrgpu_core.hxx:265-269)
-                uint32_t const bq = a.bOfX ? a.bOfX[y + dBlk[k]] : y + dBlk[k];
+                uint32_t const bq = rhs_block<EPI>(a, y + dBlk[k]);
                 d2v bM = d2v{0, 0};
                 if (bq != 0xffffffffu) bM = *(d2v const*)((R const*)a.B + size_t(bq) * 2 * P + mine);
                 auto const [br, bi] = planes(bM, xor8(bM), cp);
@@ -354,8 +354,7 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
         }
         if (q < q1) mma(o0);
 
-        uint32_t bq = 0xffffffffu;
-        if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
+        uint32_t const bq = rhs_block<EPI>(a, y);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             size_t const yoff = yb + mine(t);
@@ -365,7 +364,7 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8w(SpmmArgs a) {
             d2v const yM = cp ? d2v{qa[0] + qb[0], qa[1] + qb[1]} : d2v{qa[0] - qb[0], qa[1] - qb[1]};   // this lane's plane of Y
             auto const [yr, yi] = planes(yM, xor8(yM), cp);
             if constexpr (UPD) {
-                R const srt = on ? ((R const*)a.sc)[(size_t(g.col) * 2 + 0) * LN + 8 * (t0 + t) + j] : R(0);
+                R const srt = on ? ((R const*)a.sc)[(size_t(g.col) * 2 + 0) * LN + 8 * (t0 + t) + j] : R(0);   // (written out: epi_scalar changes the assembly)
                 R const sit = on ? ((R const*)a.sc)[(size_t(g.col) * 2 + 1) * LN + 8 * (t0 + t) + j] : R(0);
                 d2v uM = d2v{0, 0}, vM = d2v{0, 0}; f2v wM = f2v{0, 0};
                 if constexpr (PRE) { uM = uP[t]; vM = vP[t]; wM = wP[t]; }
@@ -520,8 +519,7 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8f(SpmmArgs a) {
         }
         if (q < q1) mma(o0);
 
-        uint32_t bq = 0xffffffffu;
-        if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
+        uint32_t const bq = rhs_block<EPI>(a, y);
         size_t const yb = size_t(y) * 2 * P;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -533,7 +531,7 @@ __global__ __launch_bounds__(256) void k_spmm_ilv8f(SpmmArgs a) {
             auto const [yr, yi] = planes(yM, xor8(yM), cp);
             size_t const yoff = yb + mine(t);
             if constexpr (UPD) {
-                R const srt = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + 8 * (t0 + t) + j];
+                R const srt = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + 8 * (t0 + t) + j];   // (written out: epi_scalar changes the assembly)
                 R const sit = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + 8 * (t0 + t) + j];
                 f4v uM = f4v{0, 0, 0, 0}, vM = f4v{0, 0, 0, 0}, wM = f4v{0, 0, 0, 0};
                 if (owner) {
@@ -645,7 +643,7 @@ __global__ __launch_bounds__(256) void k_spmm_mfma8(SpmmArgs a) {
     if constexpr (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) if (!RAGGED || nt * 8 + ej < LN) {
-            sr[nt] = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + nt * 8 + ej];
+            sr[nt] = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + nt * 8 + ej];   // (written out: epi_scalar changes the assembly)
             si[nt] = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + nt * 8 + ej];
         }
     }
@@ -705,7 +703,7 @@ __global__ __launch_bounds__(256) void k_spmm_mfma8(SpmmArgs a) {
             }
         }
 
-        uint32_t bq = 0xffffffffu;
+        uint32_t bq = 0xffffffffu;   // (written out: rhs_block changes the assembly)
         if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {

@@ -143,8 +143,8 @@ __global__ __launch_bounds__(256, 2) void k_spmm_mfma(SpmmArgs a) {   // at leas
     if constexpr (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            sr[nt] = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + ColMap<R, NT>::col(lc, nt)];
-            si[nt] = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + ColMap<R, NT>::col(lc, nt)];
+            sr[nt] = epi_scalar<R>(a, col, LN, 0, ColMap<R, NT>::col(lc, nt));
+            si[nt] = epi_scalar<R>(a, col, LN, 1, ColMap<R, NT>::col(lc, nt));
         }
     }
     double part[NPL > 0 ? NPL : 1][NT] = {};
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256, 2) void k_spmm_mfma(SpmmArgs a) {   // at leas
 #pragma unroll
         for (int i = 0; i < NSET - 1; ++i) if (t + i < nT) mma(o[i]);
 
-        uint32_t bq = 0xffffffffu;
+        uint32_t bq = 0xffffffffu;   // (written out: rhs_block changes the assembly)
         if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
 #pragma unroll
         for (int ms = 0; ms < MS; ++ms)

@@ -37,24 +37,22 @@ __global__ __launch_bounds__(256) void k_spmm_small4(SpmmArgs a) {
 
     R sr = 0, si = 0;
     if constexpr (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT) {
-        sr = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + j];
-        si = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + j];
+        sr = epi_scalar<R>(a, col, LN, 0, j); si = epi_scalar<R>(a, col, LN, 1, j);
     }
     double part[NPL > 0 ? NPL : 1] = {};
 
     // Three dependent requests lead to a product (row range -> index pairs -> operands).  As in k_spmm_m4 the work group fetches
     // the row ranges and index pairs of its whole chunk into LDS first, and a thread group requests the operands of up to NB
     // products before it multiplies the first: one memory latency per NB products instead of two per product.
-    constexpr uint32_t kRows = 256, kPairs = 2048;       // (a float chunk of 4 x 4 blocks has 128 rows)
+    using Patch = IndexPatch<2048>;                      // (a float chunk of 4 x 4 blocks has 128 rows)
     constexpr int NB = (sizeof(R) == 8) ? 6 : 8;
-    __shared__ uint32_t sStarts[kRows + 1];
-    __shared__ uint32_t sPairs[2 * kPairs];
-    uint32_t const nRows = last - first, nItems = nRows * NSUB;   // item = sub-block of a Y block; item % NSUB == g % NSUB
-    uint32_t const qBase = a.starts[first], qEnd = a.starts[last];
-    bool const inLds = (nRows <= kRows) && (qEnd - qBase <= kPairs);
-    if (inLds) {
-        for (uint32_t i = t; i <= nRows; i += 256) sStarts[i] = a.starts[first + i];
-        for (uint32_t i = t; i < 2 * (qEnd - qBase); i += 256) sPairs[i] = a.pairs[2 * size_t(qBase) + i];
+    __shared__ typename Patch::Starts sStarts;
+    __shared__ typename Patch::Pairs sPairs;
+    uint32_t const nItems = (last - first) * NSUB;       // item = sub-block of a Y block; item % NSUB == g % NSUB
+    Patch const ip(a, first, last);
+    if (ip.inLds) {   // (staging written out: IndexPatch, tfq_spmm.hpp)
+        for (uint32_t x = t; x <= ip.nRows; x += 256) sStarts[x] = a.starts[first + x];
+        for (uint32_t x = t; x < 2 * (ip.qEnd - ip.qBase); x += 256) sPairs[x] = a.pairs[2 * size_t(ip.qBase) + x];
     }
     __syncthreads();
 
@@ -81,16 +79,13 @@ __global__ __launch_bounds__(256) void k_spmm_small4(SpmmArgs a) {
         EpiElem<R, EPI, false> eo;
         if (valid) eo.load(a, off, P);
         R yr = 0, yi = 0;
-        if (inLds) {
-            uint32_t const q0 = sStarts[kr] - qBase, q1 = sStarts[kr + 1] - qBase;
+        if (ip.inLds) {
+            uint32_t const q0 = ip.start(sStarts, kr), q1 = ip.start(sStarts, kr + 1);
             for (uint32_t qb = q0; qb < q1; qb += NB) {
                 R pa[NB][2], px[NB][2];
                 uint32_t ia[NB], ix[NB];
 #pragma unroll
-                for (int u = 0; u < NB; ++u) {           // (unconditional, inside the patch: all NB reads in flight at once)
-                    uint32_t const qc = min(qb + u, kPairs - 1);
-                    ia[u] = sPairs[2 * qc]; ix[u] = sPairs[2 * qc + 1];
-                }
+                for (int u = 0; u < NB; ++u) Patch::pair(sPairs, qb + u, ia[u], ix[u]);
 #pragma unroll
                 for (int u = 0; u < NB; ++u) {
                     pa[u][0] = 0; pa[u][1] = 0; px[u][0] = 0; px[u][1] = 0;
@@ -122,8 +117,7 @@ __global__ __launch_bounds__(256) void k_spmm_small4(SpmmArgs a) {
             }
         }
         if (valid) {
-            uint32_t bq = 0xffffffffu;
-            if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
+            uint32_t const bq = rhs_block<EPI>(a, y);
             epilogue_apply<R, EPI, false>(a, off, P, yr, yi, sr, si, eo, bq, eb, part);
         }
     }
@@ -183,10 +177,7 @@ __global__ __launch_bounds__(256) void k_spmm_m4(SpmmArgs a) {
     for (int w = 0; w < W; ++w) { sr[w] = 0; si[w] = 0; }
     if constexpr (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT) {
 #pragma unroll
-        for (int w = 0; w < W; ++w) {
-            sr[w] = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + j0 + w];
-            si[w] = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + j0 + w];
-        }
+        for (int w = 0; w < W; ++w) { sr[w] = epi_scalar<R>(a, col, LN, 0, j0 + w); si[w] = epi_scalar<R>(a, col, LN, 1, j0 + w); }
     }
     double part[NPL > 0 ? NPL : 1][W] = {};
 
@@ -194,15 +185,14 @@ __global__ __launch_bounds__(256) void k_spmm_m4(SpmmArgs a) {
     // requests lead to a product (row range -> index pairs -> operands).  The work group fetches the row ranges and the index
     // pairs of its whole chunk into LDS first (two latencies, once), so that a trip -- up to NB products of four items per
     // wave -- waits for ONE memory latency; k_spmm_small4 waits for two per product.
-    constexpr uint32_t kRows = 256, kPairs = 1024;       // LDS patch: chunks of at most 256 Y blocks (tfq_plan.cpp: 16 KiB of 256-byte blocks = 64)
-    __shared__ uint32_t sStarts[kRows + 1];
-    __shared__ uint32_t sPairs[2 * kPairs];
-    uint32_t const nRows = last - first, nItems = nRows * NSUB;
-    uint32_t const qBase = a.starts[first], qEnd = a.starts[last];      // (uniform: scalar loads)
-    bool const inLds = (nRows <= kRows) && (qEnd - qBase <= kPairs);
-    if (inLds) {
-        for (uint32_t i = t; i <= nRows; i += 256) sStarts[i] = a.starts[first + i];
-        for (uint32_t i = t; i < 2 * (qEnd - qBase); i += 256) sPairs[i] = a.pairs[2 * size_t(qBase) + i];
+    using Patch = IndexPatch<1024>;                      // chunks of at most 256 Y blocks (tfq_plan.cpp: 16 KiB of 256-byte blocks = 64)
+    __shared__ typename Patch::Starts sStarts;
+    __shared__ typename Patch::Pairs sPairs;
+    uint32_t const nItems = (last - first) * NSUB;
+    Patch const ip(a, first, last);
+    if (ip.inLds) {   // (staging written out: IndexPatch, tfq_spmm.hpp)
+        for (uint32_t x = t; x <= ip.nRows; x += 256) sStarts[x] = a.starts[first + x];
+        for (uint32_t x = t; x < 2 * (ip.qEnd - ip.qBase); x += 256) sPairs[x] = a.pairs[2 * size_t(ip.qBase) + x];
     }
     __syncthreads();
 
@@ -226,16 +216,13 @@ __global__ __launch_bounds__(256) void k_spmm_m4(SpmmArgs a) {
         R yr[W], yi[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) { yr[w] = 0; yi[w] = 0; }
-        if (inLds) {
-            uint32_t const q0 = live ? sStarts[k] - qBase : 0, q1 = live ? sStarts[k + 1] - qBase : 0;
+        if (ip.inLds) {
+            uint32_t const q0 = live ? ip.start(sStarts, k) : 0, q1 = live ? ip.start(sStarts, k + 1) : 0;
             for (uint32_t qb = q0; __any(qb < q1); qb += NB) {
                 R ar[NB], ai[NB], xr[NB][W], xi[NB][W];
                 uint32_t ia[NB], ix[NB];
 #pragma unroll
-                for (int u = 0; u < NB; ++u) {           // (unconditional, inside the patch: all NB reads in flight at once)
-                    uint32_t const qc = min(qb + u, kPairs - 1);
-                    ia[u] = sPairs[2 * qc]; ix[u] = sPairs[2 * qc + 1];
-                }
+                for (int u = 0; u < NB; ++u) Patch::pair(sPairs, qb + u, ia[u], ix[u]);
 #pragma unroll
                 for (int u = 0; u < NB; ++u) {
                     ar[u] = 0; ai[u] = 0;
@@ -268,8 +255,7 @@ __global__ __launch_bounds__(256) void k_spmm_m4(SpmmArgs a) {
             }
         }
         if (live) {
-            uint32_t bq = 0xffffffffu;
-            if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
+            uint32_t const bq = rhs_block<EPI>(a, y);
             epilogue_row<R, EPI, W, NPL, W>(a, off, P, yr, yi, sr, si, 0, eo, bq, ex, part, 0);
         }
     }
@@ -333,22 +319,18 @@ __global__ __launch_bounds__(256) void k_spmm_s4w(SpmmArgs a) {
     for (int w = 0; w < W; ++w) { sr[w] = 0; si[w] = 0; }
     if constexpr (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT) {
 #pragma unroll
-        for (int w = 0; w < W; ++w) {
-            sr[w] = ((R const*)a.sc)[(size_t(col) * 2 + 0) * LN + j0 + w];
-            si[w] = ((R const*)a.sc)[(size_t(col) * 2 + 1) * LN + j0 + w];
-        }
+        for (int w = 0; w < W; ++w) { sr[w] = epi_scalar<R>(a, col, LN, 0, j0 + w); si[w] = epi_scalar<R>(a, col, LN, 1, j0 + w); }
     }
     double part[NPL > 0 ? NPL : 1][W] = {};
 
-    constexpr uint32_t kRows = 256, kPairs = 2048;       // the chunk's row ranges and index pairs in LDS, as k_spmm_small4
-    __shared__ uint32_t sStarts[kRows + 1];
-    __shared__ uint32_t sPairs[2 * kPairs];
-    uint32_t const nRows = last - first, nItems = nRows * NSUB;   // item = sub-block of a Y block; item % NSUB == g % NSUB
-    uint32_t const qBase = a.starts[first], qEnd = a.starts[last];
-    bool const inLds = (nRows <= kRows) && (qEnd - qBase <= kPairs);
-    if (inLds) {
-        for (uint32_t x = t; x <= nRows; x += 256) sStarts[x] = a.starts[first + x];
-        for (uint32_t x = t; x < 2 * (qEnd - qBase); x += 256) sPairs[x] = a.pairs[2 * size_t(qBase) + x];
+    using Patch = IndexPatch<2048>;                      // the chunk's row ranges and index pairs in LDS, as k_spmm_small4
+    __shared__ typename Patch::Starts sStarts;
+    __shared__ typename Patch::Pairs sPairs;
+    uint32_t const nItems = (last - first) * NSUB;       // item = sub-block of a Y block; item % NSUB == g % NSUB
+    Patch const ip(a, first, last);
+    if (ip.inLds) {   // (staging written out: IndexPatch, tfq_spmm.hpp)
+        for (uint32_t x = t; x <= ip.nRows; x += 256) sStarts[x] = a.starts[first + x];
+        for (uint32_t x = t; x < 2 * (ip.qEnd - ip.qBase); x += 256) sPairs[x] = a.pairs[2 * size_t(ip.qBase) + x];
     }
     __syncthreads();
 
@@ -391,16 +373,13 @@ __global__ __launch_bounds__(256) void k_spmm_s4w(SpmmArgs a) {
         R yr[W], yi[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) { yr[w] = 0; yi[w] = 0; }
-        if (inLds) {
-            uint32_t const q0 = sStarts[kr] - qBase, q1 = sStarts[kr + 1] - qBase;
+        if (ip.inLds) {
+            uint32_t const q0 = ip.start(sStarts, kr), q1 = ip.start(sStarts, kr + 1);
             for (uint32_t qb = q0; qb < q1; qb += NB) {
                 Ops o[NB];
                 uint32_t ia[NB], ix[NB];
 #pragma unroll
-                for (int u = 0; u < NB; ++u) {           // (unconditional, inside the patch: all NB reads in flight at once)
-                    uint32_t const qc = min(qb + u, kPairs - 1);
-                    ia[u] = sPairs[2 * qc]; ix[u] = sPairs[2 * qc + 1];
-                }
+                for (int u = 0; u < NB; ++u) Patch::pair(sPairs, qb + u, ia[u], ix[u]);
 #pragma unroll
                 for (int u = 0; u < NB; ++u) if (qb + u < q1) fetch(o[u], ia[u], ix[u]);
 #pragma unroll
@@ -413,8 +392,7 @@ __global__ __launch_bounds__(256) void k_spmm_s4w(SpmmArgs a) {
                 multiply(o, yr, yi);
             }
         }
-        uint32_t bq = 0xffffffffu;
-        if constexpr (EPI == EPI_RESIDUAL) bq = a.bOfX ? a.bOfX[y] : y;
+        uint32_t const bq = rhs_block<EPI>(a, y);
         epilogue_row<R, EPI, W, NPL, W>(a, off, P, yr, yi, sr, si, 0, eo, bq, eb, part, 0);
     }
 
