@@ -255,6 +255,48 @@ tfqmrgpuStatus_t tfqmrgpuExt_getPreconditioner(tfqmrgpuHandle_t handle, tfqmrgpu
                                                void *Minv /* host, [mb][2][LM][LM], plan precision ('m': double) */,
                                                int32_t *nIdentity);
 
+/* ---- (8) listed blocks ------------------------------------------------------------------- */
+/* setMatrix and getMatrix move an operand whole.  Along an energy loop only the diagonal blocks of A change, and a Green-function
+ * caller reads only the X blocks that sit on B's pattern: setBlocks / getBlocks convert the blocks that a list names and leave every
+ * other block of the operand untouched, bit for bit.
+ *
+ * blocks[k] is the 0-based position of a block in the caller's own block order of that operand -- the order of the bsrColInd array
+ *   given to createPlan, whatever indexOffset was.  `values` holds nBlocks blocks, compact: block k of `values` is block blocks[k] of
+ *   the operand.  `blocks` is always a HOST array and is the caller's again when the call returns; `values` may be host or device memory,
+ *   told apart as in setMatrix / getMatrix (device memory: one conversion kernel on the handle's stream, no staging).
+ * Layout, trans, precision and the rule that A is stored transposed are exactly those of setMatrix / getMatrix, and so is the rule
+ *   that an 'm' plan takes 'c' or 'z' data; setBlocks('A') on an 'm' plan writes both its copies of A, the double and the float one.
+ * getBlocks reads X only, as getMatrix: any other `var` returns the status that getMatrix returns for it.
+ *   blocks == NULL: the X blocks on B's pattern, in B's block order (tfqmrgpuPlanView_t::subset); it needs nBlocks == nnzbB, anything
+ *   else returns TFQMRGPU_POINTER_INVALID.  After a preconditioned solve (section 7) getBlocks returns X, the back-transformed
+ *   solution, as getMatrix does.
+ * setBlocks takes no NULL list: TFQMRGPU_POINTER_INVALID (so does getBlocks of an `nBlocks` that is not nnzbB).
+ * nBlocks == 0 returns success and touches nothing.
+ * All checks come before the first device call, in this order: layout, trans and the plan / handle pointers as in setMatrix; no
+ *   bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; `var`; the list -- an index < 0 or >= nnzb of that operand, or in setBlocks an
+ *   index that occurs twice, returns TFQMRGPU_UNDOCUMENTED_ERROR with the key character `var` (status = 14 + 1000 * line + 10^7 * var);
+ *   getBlocks may name a block twice; the check takes O(nBlocks + nnzb) --; no buffer: TFQMRGPU_POINTER_INVALID; precision mismatch;
+ *   values == NULL.  After any error the buffer is what it was.
+ * setBlocks('A') and the state of the plan: like setMatrix('A') it forgets the float floor that an 'm' plan remembers.  It does NOT
+ *   make a plan whose A was never set whole have an A: the first A comes from setMatrix('A').  If the A in the buffer has been scaled
+ *   by the preconditioner (section 7: a preconditioned solve or getPreconditioner since the last setMatrix('A')) it returns
+ *   TFQMRGPU_NO_IMPLEMENTATION and writes nothing: the buffer holds A M^-1, and M changes with the diagonal blocks, so a patch of
+ *   A M^-1 is not a patch of A.  A whole setMatrix('A') makes partial updates possible again until the next preconditioned solve.
+ *   With kind BLOCK_JACOBI chosen but A not yet scaled setBlocks('A') is allowed: the next solve inverts and scales what is then in
+ *   the buffer.
+ * As setMatrix / getMatrix: host arrays are staged through the work vectors v4 ... v9 (call tfqmrgpuExt_getWorkVector first), a list
+ *   of any length in as many batches as the stage needs, one stream synchronisation per batch; do not call during a solve.  The device
+ *   copy of the list is memory that the library owns, grown on demand and released by destroyPlan; bufferSize and the buffer layout do
+ *   not change.  Uploading the list synchronises the handle's stream once; with blocks == NULL nothing is uploaded (the plan's own list
+ *   is on the device), and with device `values` such a call does not synchronise at all.
+ * Several ranks (section 4): the list refers to the rank's own plan.  There are no Fortran wrappers, as for every call of this file. */
+tfqmrgpuStatus_t tfqmrgpuExt_setBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char var /* 'A', 'B', 'X' */,
+    int32_t nBlocks, int32_t const *blocks /* host */, void const *values,
+    char precision, char trans, tfqmrgpuDataLayout_t layout);
+tfqmrgpuStatus_t tfqmrgpuExt_getBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char var /* 'X' only, as getMatrix */,
+    int32_t nBlocks, int32_t const *blocks /* host, or NULL */, void *values,
+    char precision, char trans, tfqmrgpuDataLayout_t layout);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_freeShard", "tfqmrgpuExt_commUniqueId", "tfqmrgpuExt_commInit",
     "tfqmrgpuExt_commDestroy", "tfqmrgpuExt_setReduceCallback", "tfqmrgpuExt_setOperator",
     "tfqmrgpuExt_getRefinementHistory", "tfqmrgpuExt_setThreeProductMultiply",
-    "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner",
+    "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner", "tfqmrgpuExt_setBlocks", "tfqmrgpuExt_getBlocks",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -139,6 +139,8 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_setThreeProductMultiply.argtypes = [P, I]
     lib.tfqmrgpuExt_setPreconditioner.argtypes = [P, I]
     lib.tfqmrgpuExt_getPreconditioner.argtypes = [P, P, P, C.POINTER(C.c_int32)]
+    lib.tfqmrgpuExt_setBlocks.argtypes = [P, P, C.c_char, C.c_int32, P, P, C.c_char, C.c_char, I]
+    lib.tfqmrgpuExt_getBlocks.argtypes = [P, P, C.c_char, C.c_int32, P, P, C.c_char, C.c_char, I]
     return lib
 
 
@@ -300,6 +302,52 @@ class Solver:
             return out.reshape(nnzb, -1)
         c = out[..., 0] + 1j * out[..., 1]
         return c if trans in "n*" else c.reshape(nnzb, self.LN, self.LM)
+
+    # -- listed blocks (tfqmrgpu_ext.h section 8) -------------------------------------------------------
+    def set_blocks(self, var, blocks, values, trans="n", layout=LAYOUT_RIRIRIRI):
+        """set the blocks of operand `var` that `blocks` lists (positions in the caller's block order) from `values`, compact: complex
+        [len(blocks), rows, cols] (interleaved layout) or a raw real array for other layouts, as set_matrix; returns the raw status"""
+        idx = _i32(blocks)
+        a = np.asarray(values)
+        if np.iscomplexobj(a):
+            a = np.ascontiguousarray(a.astype(np.complex128 if self.data_precision == "z" else np.complex64))
+        else:
+            a = np.ascontiguousarray(a, dtype=self._real_dtype())
+        st = lib.tfqmrgpuExt_setBlocks(self.handle, self.plan, var.encode(), len(idx), _ptr(idx), _ptr(a), self.data_precision.encode(),
+                                       trans.encode(), layout)
+        return _check(st, "tfqmrgpuExt_setBlocks('%s')" % var)
+
+    def set_blocks_device(self, var, blocks, device_ptr, trans="n", layout=LAYOUT_RIRIRIRI):
+        """the same with values in DEVICE memory (data_precision says float or double); the list stays a host array"""
+        idx = _i32(blocks)
+        st = lib.tfqmrgpuExt_setBlocks(self.handle, self.plan, var.encode(), len(idx), _ptr(idx), C.c_void_p(device_ptr),
+                                       self.data_precision.encode(), trans.encode(), layout)
+        return _check(st, "tfqmrgpuExt_setBlocks('%s', device array)" % var)
+
+    def _block_list(self, blocks):
+        """(host list or None, its length): None means the X blocks on B's pattern, in B's block order"""
+        if blocks is None:
+            return None, self.problem.nnzbB
+        idx = _i32(blocks)
+        return idx, len(idx)
+
+    def get_blocks(self, blocks=None, trans="n", layout=LAYOUT_RIRIRIRI, raw=False):
+        """the X blocks that `blocks` lists (None: those on B's pattern, in B's block order); shapes as get_matrix"""
+        idx, n = self._block_list(blocks)
+        out = np.zeros((n, self.LM, self.LN, 2), dtype=self._real_dtype())
+        st = lib.tfqmrgpuExt_getBlocks(self.handle, self.plan, b"X", n, None if idx is None else _ptr(idx), _ptr(out),
+                                       self.data_precision.encode(), trans.encode(), layout)
+        _check(st, "tfqmrgpuExt_getBlocks")
+        if raw or layout != LAYOUT_RIRIRIRI:
+            return out.reshape(n, -1)
+        c = out[..., 0] + 1j * out[..., 1]
+        return c if trans in "n*" else c.reshape(n, self.LN, self.LM)
+
+    def get_blocks_device(self, device_ptr, blocks=None, trans="n", layout=LAYOUT_RIRIRIRI):
+        idx, n = self._block_list(blocks)
+        st = lib.tfqmrgpuExt_getBlocks(self.handle, self.plan, b"X", n, None if idx is None else _ptr(idx), C.c_void_p(device_ptr),
+                                       self.data_precision.encode(), trans.encode(), layout)
+        return _check(st, "tfqmrgpuExt_getBlocks(device array)")
 
     def apply_operator(self, repetitions=1):
         """X := A*X on the plan's data (tfqmrgpuExt_applyOperator)"""

@@ -95,7 +95,8 @@ static Stage stage_of(Plan const& p) {
 
 // move blocks between a host array in the caller's layout and a native device array.  userDbl: precision of the caller's array,
 // nativeDbl / ilv: precision and element order of the library's; `also`: a second library-side copy of the same blocks (the float A of a
-// mixed-precision plan next to its double A)
+// mixed-precision plan next to its double A); `list` (device memory): the nBlocks blocks it names, in the caller's block order, instead of all
+// blocks 0 ... nBlocks - 1 -- the caller's array is compact, its block k is block list[k] of the operand (setBlocks / getBlocks)
 struct Target { void* native; bool dbl; int ilv; };
 
 // is `ptr` memory the GPU can read and write directly (hipMalloc, hipMallocManaged)?  Then setMatrix / getMatrix convert in place
@@ -109,11 +110,11 @@ static bool on_device(void const* ptr) {
 
 static tfqmrgpuStatus_t transfer_blocks(Plan& p, hipStream_t s, int direction, bool userDbl, Target const& to,
     void* host, uint32_t const* u2n, uint32_t nBlocks, int nR, int nC, int layout, bool trans, bool conj, Stage const* own = nullptr,
-    Target const* also = nullptr)
+    Target const* also = nullptr, uint32_t const* list = nullptr)
 {
     if (on_device(host)) {   // the caller's array is device memory: one conversion kernel straight from / into it, asynchronous on the stream
-        launch_convert(direction, userDbl, to.dbl, to.native, host, u2n, 0, nBlocks, nR, nC, layout, trans, conj, to.ilv, s);
-        if (also && 0 == direction) launch_convert(0, userDbl, also->dbl, also->native, host, u2n, 0, nBlocks, nR, nC, layout, trans, conj, also->ilv, s);
+        launch_convert(direction, userDbl, to.dbl, to.native, host, u2n, 0, nBlocks, nR, nC, layout, trans, conj, to.ilv, s, list);
+        if (also && 0 == direction) launch_convert(0, userDbl, also->dbl, also->native, host, u2n, 0, nBlocks, nR, nC, layout, trans, conj, also->ilv, s, list);
         TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
         return TFQMRGPU_STATUS_SUCCESS;
     }
@@ -124,12 +125,13 @@ static tfqmrgpuStatus_t transfer_blocks(Plan& p, hipStream_t s, int direction, b
     for (uint32_t first = 0; first < nBlocks; ) {
         uint32_t const n = uint32_t(std::min<size_t>(cap, nBlocks - first));
         char* h = (char*)host + size_t(first) * blockBytes;
+        uint32_t const* const l = list ? list + first : nullptr;
         if (0 == direction) {
             TFQ_HIP(hipMemcpyAsync(st.ptr, h, n * blockBytes, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-            launch_convert(0, userDbl, to.dbl, to.native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, to.ilv, s);
-            if (also) launch_convert(0, userDbl, also->dbl, also->native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, also->ilv, s);
+            launch_convert(0, userDbl, to.dbl, to.native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, to.ilv, s, l);
+            if (also) launch_convert(0, userDbl, also->dbl, also->native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, also->ilv, s, l);
         } else {
-            launch_convert(1, userDbl, to.dbl, to.native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, to.ilv, s);
+            launch_convert(1, userDbl, to.dbl, to.native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, to.ilv, s, l);
             TFQ_HIP(hipMemcpyAsync(h, st.ptr, n * blockBytes, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
         }
         // the stage is reused by the next batch and the host array belongs to the caller
@@ -251,6 +253,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_destroyPlan(tfqmrgpuHandle_t handle, tfqmrgpuBsr
     if (p->ring) { (void)hipHostFree(p->ring); for (auto e : p->ringEvent) (void)hipEventDestroy((hipEvent_t)e); }
     if (p->opScratch) (void)hipFree(p->opScratch);
     if (p->precond) (void)hipFree(p->precond);
+    if (p->blockList) (void)hipFree(p->blockList);
     p->magic = 0;
     delete p;
     return TFQMRGPU_STATUS_SUCCESS;
@@ -335,15 +338,13 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_getBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     return (nullptr == *pBuffer) ? TFQ_ERR(TFQMRGPU_POINTER_INVALID) : TFQMRGPU_STATUS_SUCCESS;
 }
 
-// reference tfqmrgpu::set_or_getMatrix, tfqmrgpu.cu:467-603
-static tfqmrgpuStatus_t set_or_get(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var, void* values,
-    char const precision, char const transposition, tfqmrgpuDataLayout_t const layout, bool const is_get)
-{
+// the layout and transposition arguments of setMatrix / getMatrix (and of setBlocks / getBlocks), checked in the reference's order
+static tfqmrgpuStatus_t layout_and_trans(tfqmrgpuDataLayout_t const layout, char const transposition, bool& conj, bool& trans) {
     switch (layout) {
         case TFQMRGPU_LAYOUT_RRRRIIII: case TFQMRGPU_LAYOUT_RIRIRIRI: case TFQMRGPU_LAYOUT_RRIIRRII: break;
         default: return err(TFQMRGPU_DATALAYOUT_UNKNOWN, layout % 10000);          // line field = layout
     }
-    bool conj = false, trans = false;
+    conj = false; trans = false;
     char const tr = lower(transposition);   // '*' | 32 == '*'
     switch (tr) {
         case 'h': case 'c': conj = true; trans = true; break;
@@ -352,6 +353,15 @@ static tfqmrgpuStatus_t set_or_get(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t 
         case 'n': break;
         default: return err(TFQMRGPU_TANSPOSITION_UNKNOWN, __LINE__ % 10000, tr);
     }
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// reference tfqmrgpu::set_or_getMatrix, tfqmrgpu.cu:467-603
+static tfqmrgpuStatus_t set_or_get(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var, void* values,
+    char const precision, char const transposition, tfqmrgpuDataLayout_t const layout, bool const is_get)
+{
+    bool conj = false, trans = false;
+    if (auto const st = layout_and_trans(layout, transposition, conj, trans)) return st;
     auto p = asPlan(plan); auto h = (Handle*)handle;
     if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
@@ -737,6 +747,87 @@ tfqmrgpuStatus_t tfqmrgpuExt_getPreconditioner(tfqmrgpuHandle_t handle, tfqmrgpu
     }
     if (nIdentity) *nIdentity = p->precondIdentity;
     return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// ---- listed blocks (tfqmrgpu_ext.h section 8) --------------------------------------------------------------------------------------
+// setBlocks / getBlocks: set_or_get for the blocks that `blocks` names.  Every check is host code and comes before the first device call
+static tfqmrgpuStatus_t set_or_get_blocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var, int32_t const nBlocks,
+    int32_t const* blocks, void* values, char const precision, char const transposition, tfqmrgpuDataLayout_t const layout, bool const is_get)
+{
+    bool conj = false, trans = false;
+    if (auto const st = layout_and_trans(layout, transposition, conj, trans)) return st;
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
+    if (is_get && 'x' != lower(var))   // only X: the status of getMatrix itself (it looks at `var` first)
+        return tfqmrgpu_bsrsv_getMatrix(handle, plan, var, values, precision, 0, 0, transposition, layout);
+    uint32_t nnzb = 0; int nR = p->LM, nC = p->LN; int which = 0;
+    switch (lower(var)) {
+        case 'a': nnzb = p->nnzbA; nC = p->LM; trans = !trans; which = 0; break;   // A is stored transposed, as in setMatrix
+        case 'b': nnzb = p->nnzbB; which = 1; break;
+        case 'x': nnzb = p->nnzbX; which = 2; break;
+        default: return err(TFQMRGPU_VARIABLENAME_UNKNOWN, __LINE__ % 10000, var);
+    }
+    // the list: every index inside the operand, and no block set twice (the later of two values would win by chance)
+    bool const onB = (is_get && nullptr == blocks);   // the X blocks on B's pattern, in B's block order
+    if (onB) { if (nBlocks < 0 || uint32_t(nBlocks) != p->nnzbB) return TFQ_ERR(TFQMRGPU_POINTER_INVALID); }
+    else if (nBlocks < 0) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
+    if (0 == nBlocks) return TFQMRGPU_STATUS_SUCCESS;
+    if (!onB) {
+        if (nullptr == blocks) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+        try {
+            std::vector<bool> listed(is_get ? 0 : nnzb, false);
+            for (int32_t k = 0; k < nBlocks; ++k) {
+                if (blocks[k] < 0 || uint32_t(blocks[k]) >= nnzb) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
+                if (is_get) continue;   // reading a block twice is harmless
+                if (listed[blocks[k]]) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
+                listed[blocks[k]] = true;
+            }
+        } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    }
+    if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    bool const mixed = ('m' == p->precision);
+    bool const is_double = ('z' == p->precision);
+    bool const user_double = ('z' == lower(precision));
+    if (!mixed && user_double != is_double) return err(TFQMRGPU_PRECISION_MISSMATCH, __LINE__ % 10000, precision);
+    if (nullptr == values) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    // A M^-1 cannot be patched: M changes with the diagonal blocks.  A whole setMatrix('A') brings the caller's A back
+    if (0 == which && TFQMRGPU_PRECOND_NONE != p->precondInA) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+
+    hipStream_t const s = (hipStream_t)h->stream;
+    DevPlan const d = mixed ? resolveZ(*p) : resolve(*p);
+    uint32_t const* list = d.subset;            // B's pattern: the plan's own list, which holds NATIVE block indices of X (Plan::subset_i)
+    uint32_t const* u2n = nullptr;
+    if (!onB) {
+        if (p->blockListCap < size_t(nBlocks)) {
+            // (a launch of an earlier call may still read the old list: hipFree waits for the device)
+            if (p->blockList) { (void)hipFree(p->blockList); p->blockList = nullptr; p->blockListCap = 0; }
+            if (hipSuccess != hipMalloc((void**)&p->blockList, size_t(nBlocks) * 4)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
+            p->blockListCap = size_t(nBlocks);
+        }
+        // stream order keeps this copy behind the launches of an earlier call; the caller's list is free again once the call returns
+        TFQ_HIP(hipMemcpyAsync(p->blockList, blocks, size_t(nBlocks) * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        list = p->blockList;                    // (checked: 0 <= blocks[k] < nnzb, so int32 and uint32 read the same)
+        u2n = (2 == which) ? d.u2i : nullptr;
+    }
+    if (0 == which) p->mixedFloor = 0;          // a new operator: the remembered float floor goes.  haveA stays: a patch makes no whole A
+    Target const to{ (0 == which) ? d.A : (1 == which) ? d.B : d.x, d.dbl, d.ilv };
+    Target const floatA{ p->buffer + p->wA.offset, false, p->ilv };              // mixed: the inner solves multiply with A in float
+    return transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, uint32_t(nBlocks), nR, nC, layout, trans, conj, nullptr,
+                           (mixed && 0 == which && !is_get) ? &floatA : nullptr, list);
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_setBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var,
+    int32_t const nBlocks, int32_t const* blocks, void const* values, char const precision, char const trans, tfqmrgpuDataLayout_t const layout)
+{
+    return set_or_get_blocks(handle, plan, var, nBlocks, blocks, (void*)values, precision, trans, layout, false);
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_getBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var,
+    int32_t const nBlocks, int32_t const* blocks, void* values, char const precision, char const trans, tfqmrgpuDataLayout_t const layout)
+{
+    return set_or_get_blocks(handle, plan, var, nBlocks, blocks, values, precision, trans, layout, true);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_setReduceCallback(tfqmrgpuHandle_t handle, tfqmrgpuReduceMax_t fn, void* ctx) {

@@ -152,8 +152,10 @@ bool multiply_shape_allowed(char precision, int lm, int ln);              // the
 // [firstUser, firstUser + nBlocks) whose raw bytes sit in `stage`; u2n: user -> native block index
 // ilv: element order of the library-side blocks (see ilv_offset)
 // userDbl / nativeDbl: precision of the caller's array and of the library-side array (they differ in the mixed-precision mode only)
+// list (device memory, nBlocks entries): the user blocks named by it instead of a run of them, block k of `stage` being user block list[k]
 void launch_convert(int direction, bool userDbl, bool nativeDbl, void* native, void* stage, uint32_t const* u2n,
-    uint32_t firstUser, uint32_t nBlocks, int nR, int nC, int layout, bool trans, bool conj, int ilv, hipStream_t s);
+    uint32_t firstUser, uint32_t nBlocks, int nR, int nC, int layout, bool trans, bool conj, int ilv, hipStream_t s,
+    uint32_t const* list = nullptr);
 void launch_shadow_hash(DevPlan const& d, hipStream_t s);
 
 } // namespace tfq

@@ -24,19 +24,10 @@ __device__ inline uint32_t user_offset(int layout, bool trans, int nR, int nC, i
     }
 }
 
-// direction 0: native[n(ub)] := op(user[ub]) ; direction 1: user[ub] := op^-1(native[n(ub)])
-// One work group per USER block ub = firstUser + blockIdx.x; `stage` holds the raw user blocks of the
-// current batch (block 0 of the stage is user block firstUser); u2n maps user -> native block index
-// (nullptr: identity, used for A and B; X-shaped operators pass the column-sorted permutation).
+// direction 0: nblock := op(ublock) ; direction 1: ublock := op^-1(nblock) -- one block, by the 256 threads of a work group
 template <typename R, typename U>   // R: library side, U: caller's side
-__global__ __launch_bounds__(256) void k_convert(int direction, R* native, U* stage, uint32_t const* u2n,
-    uint32_t firstUser, int nR, int nC, int layout, bool trans, bool conj, int ilv)
-{
-    uint32_t const ub = firstUser + blockIdx.x;
-    uint32_t const nb = u2n ? u2n[ub] : ub;
+__device__ inline void convert_block(int direction, R* nblock, U* ublock, int nR, int nC, int layout, bool trans, bool conj, int ilv) {
     int const E = 2 * nR * nC;
-    U* ublock = stage + size_t(blockIdx.x) * E;
-    R* nblock = native + size_t(nb) * E;
     for (int e = threadIdx.x; e < E; e += 256) {
         int const c = e / (nR * nC), r = (e % (nR * nC)) / nC, s = e % nC;
         uint32_t const uo = user_offset(layout, trans, nR, nC, r, s, c);
@@ -47,18 +38,44 @@ __global__ __launch_bounds__(256) void k_convert(int direction, R* native, U* st
     }
 }
 
+// direction 0: native[n(ub)] := op(user[ub]) ; direction 1: user[ub] := op^-1(native[n(ub)])
+// One work group per USER block ub = firstUser + blockIdx.x; `stage` holds the raw user blocks of the
+// current batch (block 0 of the stage is user block firstUser); u2n maps user -> native block index
+// (nullptr: identity, used for A and B; X-shaped operators pass the column-sorted permutation).
+template <typename R, typename U>
+__global__ __launch_bounds__(256) void k_convert(int direction, R* native, U* stage, uint32_t const* u2n,
+    uint32_t firstUser, int nR, int nC, int layout, bool trans, bool conj, int ilv)
+{
+    uint32_t const ub = firstUser + blockIdx.x;
+    uint32_t const nb = u2n ? u2n[ub] : ub;
+    size_t const E = size_t(2) * nR * nC;
+    convert_block(direction, native + size_t(nb) * E, stage + size_t(blockIdx.x) * E, nR, nC, layout, trans, conj, ilv);
+}
+
+// The same for LISTED blocks (setBlocks / getBlocks, tfqmrgpu_ext.h section 8): one work group per entry k = blockIdx.x of `list`, which
+// names a block of the operand in the caller's block order; block k of `stage` is the caller's side of it (the values are compact).
+template <typename R, typename U>
+__global__ __launch_bounds__(256) void k_convert_list(int direction, R* native, U* stage, uint32_t const* list, uint32_t const* u2n,
+    int nR, int nC, int layout, bool trans, bool conj, int ilv)
+{
+    uint32_t const ub = list[blockIdx.x];
+    uint32_t const nb = u2n ? u2n[ub] : ub;
+    size_t const E = size_t(2) * nR * nC;
+    convert_block(direction, native + size_t(nb) * E, stage + size_t(blockIdx.x) * E, nR, nC, layout, trans, conj, ilv);
+}
+
+// list == nullptr: blocks firstUser ... firstUser + nBlocks - 1 (k_convert); else the nBlocks entries of `list` (firstUser is not used)
 void launch_convert(int direction, bool userDbl, bool nativeDbl, void* native, void* stage, uint32_t const* u2n,
-    uint32_t firstUser, uint32_t nBlocks, int nR, int nC, int layout, bool trans, bool conj, int ilv, hipStream_t s)
+    uint32_t firstUser, uint32_t nBlocks, int nR, int nC, int layout, bool trans, bool conj, int ilv, hipStream_t s, uint32_t const* list)
 {
     if (0 == nBlocks) return;
     dim3 const g(nBlocks), b(256);
-    if (nativeDbl) {
-        if (userDbl) k_convert<double, double><<<g, b, 0, s>>>(direction, (double*)native, (double*)stage, u2n, firstUser, nR, nC, layout, trans, conj, ilv);
-        else         k_convert<double, float ><<<g, b, 0, s>>>(direction, (double*)native, (float*)stage, u2n, firstUser, nR, nC, layout, trans, conj, ilv);
-    } else {
-        if (userDbl) k_convert<float, double><<<g, b, 0, s>>>(direction, (float*)native, (double*)stage, u2n, firstUser, nR, nC, layout, trans, conj, ilv);
-        else         k_convert<float, float ><<<g, b, 0, s>>>(direction, (float*)native, (float*)stage, u2n, firstUser, nR, nC, layout, trans, conj, ilv);
-    }
+#define TFQ_CONVERT(R, U) { \
+        if (list) k_convert_list<R, U><<<g, b, 0, s>>>(direction, (R*)native, (U*)stage, list, u2n, nR, nC, layout, trans, conj, ilv); \
+        else      k_convert<R, U><<<g, b, 0, s>>>(direction, (R*)native, (U*)stage, u2n, firstUser, nR, nC, layout, trans, conj, ilv); }
+    if (nativeDbl) { if (userDbl) TFQ_CONVERT(double, double) else TFQ_CONVERT(double, float) }
+    else           { if (userDbl) TFQ_CONVERT(float, double)  else TFQ_CONVERT(float, float) }
+#undef TFQ_CONVERT
 }
 
 // ---- shadow vector: the counter-based hash of tfq_device.hpp written out (k_dot35 and the GLIBC/user modes read v3) ----

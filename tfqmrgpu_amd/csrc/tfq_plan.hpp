@@ -146,6 +146,9 @@ struct Plan {
     int32_t precondIdentity = 0;       // block rows whose M_ii is the unit matrix (no diagonal block, or a singular one)
     char* precond = nullptr;           // library-owned device memory [M^-1 | diagOfRow | colOfA | counter], allocated at the first preconditioned solve
 
+    // setBlocks / getBlocks (tfqmrgpu_ext.h section 8): library-owned device copy of the caller's block list, grown on demand
+    uint32_t* blockList = nullptr; size_t blockListCap = 0;   // (entries)
+
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;
     int iterations_needed = -1;
