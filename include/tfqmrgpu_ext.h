@@ -233,7 +233,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_setOperator(tfqmrgpuBsrsvPlan_t plan, tfqmrgpuOpera
  * getMatrix('X') and tfqmrgpuExt_getWorkVector(.., 1, ..) return X, not Y: the back transform runs at the end of solve, on the
  *   solver's stream, also when the solve ends at maxIterations or in a breakdown.  The other work vectors (4 ... 9) are those of the
  *   scaled system.  tfqmrgpuExt_applyOperator on such a plan multiplies with what is in the buffer: A M^-1 once a solve (or
- *   getPreconditioner) has scaled A, the caller's A before.  The caller's A itself is not kept: whoever reads the A window of the
+ *   getPreconditioner) has scaled A, the caller's A before.  The caller's A itself is not kept (unless section 9 is switched on): whoever reads the A window of the
  *   buffer directly finds A M^-1 there (getMatrix hands out X only, as in the reference).  setBuffer starts afresh: the new buffer
  *   holds no A, so setMatrix('A') has to follow it and is inverted and scaled at the next solve; bufferSize does the same.
  * Precisions 'z', 'c' and 'm'.  'm': both copies of A (double and float) are scaled, M^-1 is kept in double and the back transform
@@ -281,7 +281,8 @@ tfqmrgpuStatus_t tfqmrgpuExt_getPreconditioner(tfqmrgpuHandle_t handle, tfqmrgpu
  *   make a plan whose A was never set whole have an A: the first A comes from setMatrix('A').  If the A in the buffer has been scaled
  *   by the preconditioner (section 7: a preconditioned solve or getPreconditioner since the last setMatrix('A')) it returns
  *   TFQMRGPU_NO_IMPLEMENTATION and writes nothing: the buffer holds A M^-1, and M changes with the diagonal blocks, so a patch of
- *   A M^-1 is not a patch of A.  A whole setMatrix('A') makes partial updates possible again until the next preconditioned solve.
+ *   A M^-1 is not a patch of A.  A whole setMatrix('A') makes partial updates possible again until the next preconditioned solve;
+ *   a plan that keeps the caller's A (section 9) takes the patch at any time.
  *   With kind BLOCK_JACOBI chosen but A not yet scaled setBlocks('A') is allowed: the next solve inverts and scales what is then in
  *   the buffer.
  * As setMatrix / getMatrix: host arrays are staged through the work vectors v4 ... v9 (call tfqmrgpuExt_getWorkVector first), a list
@@ -296,6 +297,43 @@ tfqmrgpuStatus_t tfqmrgpuExt_setBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPla
 tfqmrgpuStatus_t tfqmrgpuExt_getBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char var /* 'X' only, as getMatrix */,
     int32_t nBlocks, int32_t const *blocks /* host, or NULL */, void *values,
     char precision, char trans, tfqmrgpuDataLayout_t layout);
+
+/* ---- (9) keeping the caller's A on a preconditioned plan --------------------------------- */
+/* The first preconditioned solve (section 7) overwrites the A in the buffer with A M^-1, so that setBlocks('A') (section 8) has nothing
+ * left to patch and a change of kind needs a whole setMatrix('A').  keepOperator(plan, 1) makes the plan keep the caller's own A next to
+ * the scaled one: a patch of A is then a patch of the copy, and the set-up is redone for the block rows and block columns that the patch
+ * touched.  This is what lets an energy loop -- only the diagonal blocks of A change -- run with the preconditioner.
+ *
+ * keepOperator: off is the default.  A plan that never calls it, or calls it with 0, behaves bit for bit as without this section: same
+ *   buffer size, same launches, same results, same statuses (TFQMRGPU_NO_IMPLEMENTATION of setBlocks('A') on a scaled plan, the status
+ *   with the key character 'A' after a change of kind).  Call it after bufferSize, like setPreconditioner; it survives bufferSize and
+ *   setBuffer as the kind does.  Switching it ON while the A in the buffer has been scaled already and the plan has no copy returns
+ *   TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A' (status = 14 + 1000 * line + 10^7 * 'A'): the caller's A is gone, setMatrix('A')
+ *   brings one.  Switching it OFF releases the copy; the plan then behaves as if it had never been on.
+ * The copy: made at the set-up (the first preconditioned solve, or getPreconditioner, after setMatrix('A')) from the A window of the
+ *   buffer, device to device, before that window is scaled in place -- the buffer's own block order, transposition and element order; an
+ *   'm' plan keeps both its copies of A, the double and the float one.  It is device memory that the library owns (the size of the A
+ *   window(s)), allocated at the first such set-up and released by destroyPlan, by keepOperator(plan, 0), by setBuffer and by bufferSize;
+ *   bufferSize and the buffer layout do not change.  The first preconditioned solve gives the bits it gives without the switch.
+ * setBlocks('A') while the A in the buffer is scaled writes the listed blocks into the copy and returns success.  Arguments and list
+ *   are checked as in section 8, in the same order; after an error nothing has changed.  Like every setBlocks('A') it forgets the float
+ *   floor of an 'm' plan.  The library remembers the block columns that hold a listed block and the block rows whose diagonal block is
+ *   listed; several calls before a solve add up.  While the A in the buffer is NOT scaled (kind NONE, or between setMatrix('A') and
+ *   the set-up) setBlocks('A') writes the buffer, as in section 8.
+ * The next set-up (solve or getPreconditioner) redoes what was touched: M_ii^-1 for the remembered rows, from the copy; every block
+ *   A_ij M_jj^-1 of the remembered columns, from the copy into the buffer ('m': both copies); the count of unit matrices (a diagonal
+ *   block can become singular, or stop being so).  Each block has the bits that a whole setMatrix('A') of the patched matrix and a whole
+ *   set-up give it, so the solve is that solve, bit for bit.  The lists of the partial set-up live in library-owned device memory, grown
+ *   on demand and released by destroyPlan; uploading them synchronises the handle's stream once.
+ * setPreconditioner(plan, NONE) on a scaled plan needs no new matrix: the next solve copies the caller's A back into the buffer and
+ *   solves without a preconditioner; BLOCK_JACOBI again scales it again.
+ * setMatrix('A') whole works as always: it writes the buffer; the copy is taken again at the next set-up, patches that no set-up has
+ *   seen are forgotten.
+ * tfqmrgpuExt_applyOperator multiplies with what is in the buffer (A M^-1 once scaled), not with the copy; getWorkVector, the back
+ *   transform and flops_performed are those of section 7 (the partial set-up is not counted, like the whole one).  A plan with a
+ *   user-defined operator (section 5) accepts the switch and keeps nothing: it has no blocks to scale.
+ * Several ranks (section 4): every rank holds all of A, and everything above is local to a rank. */
+tfqmrgpuStatus_t tfqmrgpuExt_keepOperator(tfqmrgpuBsrsvPlan_t plan, int on);
 
 #ifdef __cplusplus
 }

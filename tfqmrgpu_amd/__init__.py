@@ -40,6 +40,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_commDestroy", "tfqmrgpuExt_setReduceCallback", "tfqmrgpuExt_setOperator",
     "tfqmrgpuExt_getRefinementHistory", "tfqmrgpuExt_setThreeProductMultiply",
     "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner", "tfqmrgpuExt_setBlocks", "tfqmrgpuExt_getBlocks",
+    "tfqmrgpuExt_keepOperator",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -141,6 +142,7 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_getPreconditioner.argtypes = [P, P, P, C.POINTER(C.c_int32)]
     lib.tfqmrgpuExt_setBlocks.argtypes = [P, P, C.c_char, C.c_int32, P, P, C.c_char, C.c_char, I]
     lib.tfqmrgpuExt_getBlocks.argtypes = [P, P, C.c_char, C.c_int32, P, P, C.c_char, C.c_char, I]
+    lib.tfqmrgpuExt_keepOperator.argtypes = [P, I]
     return lib
 
 
@@ -397,6 +399,12 @@ class Solver:
     def set_preconditioner(self, kind=PRECOND_BLOCK_JACOBI):
         """tfqmrgpu_ext.h section 7: PRECOND_NONE or PRECOND_BLOCK_JACOBI (applied from the right); call after buffer_size"""
         _check(lib.tfqmrgpuExt_setPreconditioner(self.plan, int(kind)), "tfqmrgpuExt_setPreconditioner")
+
+    def keep_operator(self, on=True):
+        """tfqmrgpu_ext.h section 9: keep the caller's A next to the scaled one, so that set_blocks('A') and a change of the
+        preconditioner kind work on a preconditioned plan; call after buffer_size.  Raises TfqmrError (status 14, key 'A') when the A in
+        the buffer is scaled already and the plan has no copy of the caller's"""
+        return _check(lib.tfqmrgpuExt_keepOperator(self.plan, int(bool(on))), "tfqmrgpuExt_keepOperator")
 
     def get_preconditioner(self, values=True):
         """(M^-1 as complex [mb, LM, LM] -- None with values=False --, number of block rows whose M_ii is the unit matrix); between

@@ -254,6 +254,8 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_destroyPlan(tfqmrgpuHandle_t handle, tfqmrgpuBsr
     if (p->opScratch) (void)hipFree(p->opScratch);
     if (p->precond) (void)hipFree(p->precond);
     if (p->blockList) (void)hipFree(p->blockList);
+    release_kept(*p);
+    if (p->keepList) (void)hipFree(p->keepList);
     p->magic = 0;
     delete p;
     return TFQMRGPU_STATUS_SUCCESS;
@@ -285,6 +287,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     if (p->opScratch) { (void)hipFree(p->opScratch); p->opScratch = nullptr; }   // sized for the previous block shape
     if (p->precond) { (void)hipFree(p->precond); p->precond = nullptr; }         // likewise
     p->precondInA = TFQMRGPU_PRECOND_NONE; p->haveA = false;                     // (the A of the new layout has not been set)
+    release_kept(*p);                                                            // (a kept copy is one of the old layout)
     p->precision = prec;
     p->buffer = nullptr;
     *pBufferSizeInBytes = p->bufferBytes;
@@ -300,6 +303,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     hipStream_t const s = (hipStream_t)h->stream;
     p->buffer = (char*)pBuffer;
     p->precondInA = TFQMRGPU_PRECOND_NONE; p->haveA = false;   // this buffer holds no A yet, scaled or not (tfqmrgpu_ext.h section 7)
+    release_kept(*p);                                           // and a kept copy (section 9) belongs to the A of the old one
     auto at = [&](Window const& w) { return (void*)(p->buffer + w.offset); };
     for (auto const& l : indexLists(*p))   // (tfq_plan.cpp: the windows were sized from the same list)
         if (auto const st = upload(at(*l.window), l.data, l.bytes, s)) return st;
@@ -388,7 +392,7 @@ static tfqmrgpuStatus_t set_or_get(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t 
     uint32_t const* u2n = (2 == which) ? d.u2i : nullptr;
     auto const st = transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, nnzb, nR, nC, layout, trans, conj, nullptr,
                                     (mixed && 0 == which && !is_get) ? &floatA : nullptr);
-    if (0 == which && !is_get) { p->haveA = !st; p->precondInA = TFQMRGPU_PRECOND_NONE; }   // a new A: not scaled, the preconditioner of the last one is stale
+    if (0 == which && !is_get) { p->haveA = !st; p->precondInA = TFQMRGPU_PRECOND_NONE; forget_dirty(*p); }   // a new A: not scaled, the preconditioner of the last one is stale (and so is a kept copy, with its patches)
     return st;
 }
 
@@ -734,6 +738,20 @@ tfqmrgpuStatus_t tfqmrgpuExt_setPreconditioner(tfqmrgpuBsrsvPlan_t plan, int kin
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
+tfqmrgpuStatus_t tfqmrgpuExt_keepOperator(tfqmrgpuBsrsvPlan_t plan, int on) {
+    auto p = asPlan(plan);
+    if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 != on) {
+        // the A in the buffer is A M^-1 already and nobody has the caller's: there is nothing to keep (a plan that is on has its copy)
+        if (!p->keepA && TFQMRGPU_PRECOND_NONE != p->precondInA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+        p->keepA = true;
+    } else {
+        p->keepA = false;
+        release_kept(*p);                       // from here on the plan is one that never kept anything
+    }
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
 tfqmrgpuStatus_t tfqmrgpuExt_getPreconditioner(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, void* Minv, int32_t* nIdentity) {
     auto p = asPlan(plan); auto h = (Handle*)handle;
     if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
@@ -791,8 +809,23 @@ static tfqmrgpuStatus_t set_or_get_blocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     bool const user_double = ('z' == lower(precision));
     if (!mixed && user_double != is_double) return err(TFQMRGPU_PRECISION_MISSMATCH, __LINE__ % 10000, precision);
     if (nullptr == values) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    // A M^-1 cannot be patched: M changes with the diagonal blocks.  A whole setMatrix('A') brings the caller's A back
-    if (0 == which && TFQMRGPU_PRECOND_NONE != p->precondInA) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+    // A M^-1 cannot be patched: M changes with the diagonal blocks.  A whole setMatrix('A') brings the caller's A back -- unless the plan
+    // keeps it (section 9): then the patch goes into the copy, and the next set-up redoes the block rows and columns that it touches
+    bool const intoKept = (0 == which && !is_get && kept_is_callers_a(*p));
+    if (0 == which && TFQMRGPU_PRECOND_NONE != p->precondInA && !intoKept) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+    if (intoKept) {
+        try {
+            if (p->cscPtr.empty()) {                // once per plan: the blocks of A grouped by block column
+                p->cscPtr.assign(size_t(p->nRows) + 1, 0u);
+                for (auto const c : p->colOfA) ++p->cscPtr[c + 1];
+                for (uint32_t c = 0; c < p->nRows; ++c) p->cscPtr[c + 1] += p->cscPtr[c];
+                p->cscBlock.resize(p->nnzbA);
+                std::vector<uint32_t> fill(p->cscPtr.begin(), p->cscPtr.end() - 1);
+                for (uint32_t q = 0; q < p->nnzbA; ++q) p->cscBlock[fill[p->colOfA[q]]++] = q;
+            }
+            p->dirtyRow.resize(p->nRows, uint8_t(0)); p->dirtyCol.resize(p->nRows, uint8_t(0));
+        } catch (std::bad_alloc const&) { p->cscPtr.clear(); return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    }
 
     hipStream_t const s = (hipStream_t)h->stream;
     DevPlan const d = mixed ? resolveZ(*p) : resolve(*p);
@@ -812,8 +845,17 @@ static tfqmrgpuStatus_t set_or_get_blocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
         u2n = (2 == which) ? d.u2i : nullptr;
     }
     if (0 == which) p->mixedFloor = 0;          // a new operator: the remembered float floor goes.  haveA stays: a patch makes no whole A
-    Target const to{ (0 == which) ? d.A : (1 == which) ? d.B : d.x, d.dbl, d.ilv };
-    Target const floatA{ p->buffer + p->wA.offset, false, p->ilv };              // mixed: the inner solves multiply with A in float
+    if (intoKept) {                             // what the next set-up has to redo: the columns that hold a listed block, the rows whose diagonal block is listed
+        for (int32_t k = 0; k < nBlocks; ++k) {
+            uint32_t const q = uint32_t(blocks[k]), c = p->colOfA[q];
+            p->dirtyCol[c] = 1;
+            if (p->diagOfRow[c] == q) p->dirtyRow[c] = 1;
+        }
+        p->anyDirty = true;
+    }
+    auto const kept = kept_a(*p);
+    Target const to{ intoKept ? (void*)kept.a : (0 == which) ? d.A : (1 == which) ? d.B : d.x, d.dbl, d.ilv };
+    Target const floatA{ intoKept ? kept.aFloat : p->buffer + p->wA.offset, false, p->ilv };   // mixed: the inner solves multiply with A in float
     return transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, uint32_t(nBlocks), nR, nC, layout, trans, conj, nullptr,
                            (mixed && 0 == which && !is_get) ? &floatA : nullptr, list);
 }

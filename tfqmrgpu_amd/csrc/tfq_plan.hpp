@@ -146,6 +146,15 @@ struct Plan {
     int32_t precondIdentity = 0;       // block rows whose M_ii is the unit matrix (no diagonal block, or a singular one)
     char* precond = nullptr;           // library-owned device memory [M^-1 | diagOfRow | colOfA | counter], allocated at the first preconditioned solve
 
+    // the caller's own A next to the scaled one (tfqmrgpu_ext.h section 9; tfq_solve.cpp: precond_prepare)
+    bool keepA = false;                // tfqmrgpuExt_keepOperator
+    char* aKept = nullptr;             // library-owned device copy of the A window as it was before it was scaled ('m': the double A, then the float A);
+                                       // it is the caller's A while precondInA != NONE, stale otherwise
+    std::vector<uint8_t> dirtyRow, dirtyCol;   // [nRows] since the last set-up setBlocks('A') has written: the diagonal block of this row | a block of this column
+    bool anyDirty = false;
+    std::vector<uint32_t> cscPtr, cscBlock;    // the blocks of A grouped by block column, built at the first such setBlocks('A')
+    uint32_t* keepList = nullptr; size_t keepListCap = 0;   // device copy of [dirty rows | blocks of the dirty columns], grown on demand (entries)
+
     // setBlocks / getBlocks (tfqmrgpu_ext.h section 8): library-owned device copy of the caller's block list, grown on demand
     uint32_t* blockList = nullptr; size_t blockListCap = 0;   // (entries)
 

@@ -18,4 +18,14 @@ void launch_precond_invert(bool aDbl, bool wDbl, void const* A, uint32_t const* 
 void launch_precond_apply(bool dataDbl, bool wDbl, bool transW, void* data, uint32_t nBlocks, uint32_t const* wOfBlock,
                           void const* Minv, int LM, int nC, int ilv, hipStream_t s);
 
+// ---- the listed, out-of-place forms (tfqmrgpu_ext.h section 9: a kept copy of the caller's A) -- the same arithmetic, element by element
+// work group k inverts block row rows[k] (rows == nullptr: row k) for k < nListed; A may be the kept copy.  isIdentity [nRows]: 1 where
+// the row got the unit matrix, 0 where not -- written for the listed rows only
+void launch_precond_invert_listed(bool aDbl, bool wDbl, void const* A, uint32_t const* diagOfRow, void* Minv, uint32_t* isIdentity,
+                                  uint32_t const* rows, uint32_t nListed, int LM, int ilv, hipStream_t s);
+
+// block list[k] of `dst` := W * block list[k] of `src` for k < nListed, W = Minv[wOfBlock[list[k]]] or its transpose; no block twice in the list
+void launch_precond_apply_listed(bool dataDbl, bool wDbl, bool transW, void const* src, void* dst, uint32_t nListed, uint32_t const* list,
+                                 uint32_t const* wOfBlock, void const* Minv, int LM, int nC, int ilv, hipStream_t s);
+
 } // namespace tfq

@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <algorithm>
+#include <new>
 #include <vector>
 #include <dlfcn.h>
 
@@ -390,20 +391,103 @@ PrecondMem precond_mem(Plan const& p) {
     m.diag = (uint32_t*)q;   q += align256(size_t(p.nRows) * 4);
     m.colA = (uint32_t*)q;   q += align256(size_t(p.nnzbA) * 4);
     m.counter = (uint32_t*)q; q += 256;
+    m.identity = (uint32_t*)q; q += align256(size_t(p.nRows) * 4);   // a flag per block row: M_ii is the unit matrix (plans that keep A)
     m.bytes = size_t(q - p.precond);
     return m;
 }
 
+KeptA kept_a(Plan const& p) {
+    bool const mixed = ('m' == p.precision);
+    KeptA k{};
+    k.aBytes = mixed ? p.wAz.bytes : p.wA.bytes;
+    k.aFloatBytes = mixed ? p.wA.bytes : 0;
+    k.a = p.aKept;
+    k.aFloat = mixed ? p.aKept + align256(k.aBytes) : nullptr;
+    k.bytes = align256(k.aBytes) + align256(k.aFloatBytes);
+    return k;
+}
+void forget_dirty(Plan& p) {
+    if (!p.anyDirty) return;
+    std::fill(p.dirtyRow.begin(), p.dirtyRow.end(), uint8_t(0));
+    std::fill(p.dirtyCol.begin(), p.dirtyCol.end(), uint8_t(0));
+    p.anyDirty = false;
+}
+void release_kept(Plan& p) {
+    if (p.aKept) { (void)hipFree(p.aKept); p.aKept = nullptr; }
+    forget_dirty(p);
+}
+
+// precondIdentity from the flags that the listed inversion keeps per block row
+static tfqmrgpuStatus_t count_identity_flags(Plan& p, PrecondMem const& m, hipStream_t s) {
+    std::vector<uint32_t> flags(p.nRows);
+    TFQ_HIP(hipMemcpyAsync(flags.data(), m.identity, flags.size() * 4, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    int32_t n = 0;
+    for (auto const f : flags) n += (0 != f);
+    p.precondIdentity = n;
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// setBlocks('A') has patched the kept copy since the last set-up: M^-1 again for the block rows whose diagonal block was written, and
+// A_ij M_jj^-1 again, from the copy into the buffer, for every block of the block columns that hold a written block.  The listed kernels
+// share their element loops with the whole set-up, so each block has the bits that a whole setMatrix('A') and a whole set-up would give it
+static tfqmrgpuStatus_t precond_update(Handle& h, Plan& p) {
+    hipStream_t const s = (hipStream_t)h.stream;
+    std::vector<uint32_t> list;                             // [dirty rows | blocks of the dirty columns]
+    for (uint32_t r = 0; r < p.nRows; ++r) if (p.dirtyRow[r]) list.push_back(r);
+    uint32_t const nRowsListed = uint32_t(list.size());
+    for (uint32_t c = 0; c < p.nRows; ++c) if (p.dirtyCol[c]) list.insert(list.end(), p.cscBlock.begin() + p.cscPtr[c], p.cscBlock.begin() + p.cscPtr[c + 1]);
+    uint32_t const nBlocksListed = uint32_t(list.size()) - nRowsListed;
+    if (p.keepListCap < list.size()) {
+        if (p.keepList) { (void)hipFree(p.keepList); p.keepList = nullptr; p.keepListCap = 0; }
+        TFQ_HIP(hipMalloc((void**)&p.keepList, list.size() * 4), TFQMRGPU_STATUS_ALLOCATION_FAILED)
+        p.keepListCap = list.size();
+    }
+    TFQ_HIP(hipMemcpyAsync(p.keepList, list.data(), list.size() * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)   // (`list` is a local)
+    auto const m = precond_mem(p);
+    auto const k = kept_a(p);
+    bool const mixed = ('m' == p.precision), wDbl = ('c' != p.precision);
+    DevPlan const d = mixed ? resolveZ(p) : resolve(p);
+    uint32_t const* const blocks = p.keepList + nRowsListed;
+    launch_precond_invert_listed(d.dbl, wDbl, k.a, m.diag, m.minv, m.identity, p.keepList, nRowsListed, p.LM, d.ilv, s);
+    launch_precond_apply_listed(d.dbl, wDbl, true, k.a, d.A, nBlocksListed, blocks, m.colA, m.minv, p.LM, p.LM, d.ilv, s);
+    if (mixed) launch_precond_apply_listed(false, true, true, k.aFloat, p.buffer + p.wA.offset, nBlocksListed, blocks, m.colA, m.minv, p.LM, p.LM, p.ilv, s);
+    if (auto const st = count_identity_flags(p, m, s)) return st;   // a row can have become singular, or regular
+    forget_dirty(p);
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// the kind has changed on a plan that keeps A: the caller's A goes back into the buffer
+static tfqmrgpuStatus_t precond_restore(Handle& h, Plan& p) {
+    hipStream_t const s = (hipStream_t)h.stream;
+    auto const k = kept_a(p);
+    bool const mixed = ('m' == p.precision);
+    TFQ_HIP(hipMemcpyAsync(p.buffer + (mixed ? p.wAz.offset : p.wA.offset), k.a, k.aBytes, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    if (mixed) TFQ_HIP(hipMemcpyAsync(p.buffer + p.wA.offset, k.aFloat, k.aFloatBytes, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    p.precondInA = TFQMRGPU_PRECOND_NONE;
+    p.mixedFloor = 0;                                       // (the floor that was remembered is that of the scaled operator)
+    forget_dirty(p);                                        // the copy had every patch
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
 // what a solve needs before its first iteration: nothing when the preconditioner is off; otherwise M^-1 and the scaled A, made here
-// when the A in the buffer is still the caller's (the first solve after setMatrix('A')) and reused by every later solve of that A
-tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p) {
+// when the A in the buffer is still the caller's (the first solve after setMatrix('A')) and reused by every later solve of that A.
+// A plan that keeps A (section 9) copies the A window first; later it redoes what setBlocks('A') has touched, and follows a change of kind
+static tfqmrgpuStatus_t precond_prepare_(Handle& h, Plan& p) {
     if (TFQMRGPU_PRECOND_NONE == p.precondKind && TFQMRGPU_PRECOND_NONE == p.precondInA) return TFQMRGPU_STATUS_SUCCESS;
     if (p.opFn) {   // a user-defined operator has no blocks to scale -- and never reads the A in the buffer, scaled or not
         return (TFQMRGPU_PRECOND_NONE != p.precondKind) ? TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION) : TFQMRGPU_STATUS_SUCCESS;
     }
-    if (p.precondInA == p.precondKind) return TFQMRGPU_STATUS_SUCCESS;
-    // the kind has changed since A was scaled: only a fresh setMatrix('A') brings the caller's A back
-    if (TFQMRGPU_PRECOND_NONE != p.precondInA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+    bool const kept = kept_is_callers_a(p);
+    if (p.precondInA == p.precondKind) return (kept && p.anyDirty) ? precond_update(h, p) : TFQMRGPU_STATUS_SUCCESS;
+    if (TFQMRGPU_PRECOND_NONE != p.precondInA) {
+        // the kind has changed since A was scaled: only a fresh setMatrix('A') brings the caller's A back -- or the kept copy
+        if (!kept) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+        if (auto const st = precond_restore(h, p)) return st;
+        if (TFQMRGPU_PRECOND_NONE == p.precondKind) return TFQMRGPU_STATUS_SUCCESS;
+    }
     if (!p.buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     if (!p.haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
     hipStream_t const s = (hipStream_t)h.stream;
@@ -417,18 +501,36 @@ tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p) {
     auto const m = precond_mem(p);
     bool const mixed = ('m' == p.precision), wDbl = ('c' != p.precision);
     DevPlan const d = mixed ? resolveZ(p) : resolve(p);      // mixed: M^-1 comes from the double copy of A
-    TFQ_HIP(hipMemsetAsync(m.counter, 0, 4, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    launch_precond_invert(d.dbl, wDbl, d.A, m.diag, m.minv, m.counter, p.nRows, p.LM, d.ilv, s);
+    if (p.keepA) {   // the caller's A, device to device, before it is scaled in place: block order, transposition and element order are the buffer's
+        if (!p.aKept) TFQ_HIP(hipMalloc((void**)&p.aKept, std::max<size_t>(kept_a(p).bytes, 256)), TFQMRGPU_STATUS_ALLOCATION_FAILED)
+        auto const k = kept_a(p);
+        TFQ_HIP(hipMemcpyAsync(k.a, d.A, k.aBytes, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        if (mixed) TFQ_HIP(hipMemcpyAsync(k.aFloat, p.buffer + p.wA.offset, k.aFloatBytes, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        forget_dirty(p);
+        // every row through the listed form: it leaves the flag per row that a later partial set-up recounts from
+        launch_precond_invert_listed(d.dbl, wDbl, d.A, m.diag, m.minv, m.identity, nullptr, p.nRows, p.LM, d.ilv, s);
+    } else {
+        TFQ_HIP(hipMemsetAsync(m.counter, 0, 4, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        launch_precond_invert(d.dbl, wDbl, d.A, m.diag, m.minv, m.counter, p.nRows, p.LM, d.ilv, s);
+    }
     // A_ij := A_ij M_jj^-1; the blocks are stored transposed, so this is block := (M_jj^-1)^T block
     launch_precond_apply(d.dbl, wDbl, true, d.A, p.nnzbA, m.colA, m.minv, p.LM, p.LM, d.ilv, s);
     if (mixed) launch_precond_apply(false, true, true, p.buffer + p.wA.offset, p.nnzbA, m.colA, m.minv, p.LM, p.LM, p.ilv, s);   // the float copy of the inner solves
-    uint32_t n = 0;
-    TFQ_HIP(hipMemcpyAsync(&n, m.counter, 4, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    p.precondIdentity = int32_t(n);
+    if (p.keepA) { if (auto const st = count_identity_flags(p, m, s)) return st; }
+    else {
+        uint32_t n = 0;
+        TFQ_HIP(hipMemcpyAsync(&n, m.counter, 4, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        p.precondIdentity = int32_t(n);
+    }
     p.precondInA = p.precondKind;
     return TFQMRGPU_STATUS_SUCCESS;
+}
+
+tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p) {
+    try { return precond_prepare_(h, p); }   // (the lists of a partial set-up are host vectors; no exception may cross the C boundary)
+    catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
 }
 
 // X := M^-1 Y at the end of a solve, on the solver's stream ('m': once, in double, on the refined solution)

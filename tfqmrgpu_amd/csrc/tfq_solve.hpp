@@ -32,9 +32,17 @@ inline bool several_ranks(Handle const& h) { return h.comm != nullptr || h.reduc
 inline bool folds(Plan const& p, bool severalRanks) { return p.foldOk && !severalRanks && !p.opFn; }
 
 // ---- block-Jacobi right preconditioner: the library-owned memory of a plan, and what a solve needs before its first iteration
-struct PrecondMem { char* minv; uint32_t* diag; uint32_t* colA; uint32_t* counter; size_t minvBytes, bytes; };
+struct PrecondMem { char* minv; uint32_t* diag; uint32_t* colA; uint32_t* counter; uint32_t* identity; size_t minvBytes, bytes; };
 PrecondMem precond_mem(Plan const& p);
 tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p);
+
+// ---- the kept copy of the caller's A (tfqmrgpu_ext.h section 9): Plan::aKept holds the A window of the buffer, for 'm' the double A
+// (`a`) followed by the float A (`aFloat`)
+struct KeptA { char* a; char* aFloat; size_t aBytes, aFloatBytes, bytes; };
+KeptA kept_a(Plan const& p);
+inline bool kept_is_callers_a(Plan const& p) { return p.keepA && p.aKept && TFQMRGPU_PRECOND_NONE != p.precondInA; }
+void forget_dirty(Plan& p);            // a whole new A, or the set-up has caught up
+void release_kept(Plan& p);            // the copy goes (bufferSize, setBuffer, keepOperator(0), destroyPlan)
 
 extern Rccl g_rccl;
 
