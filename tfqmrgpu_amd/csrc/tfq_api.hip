@@ -1,15 +1,18 @@
 // C-ABI of libtfQMRgpu.so (include/tfqmrgpu.h, include/tfqmrgpu_ext.h) for MI355X.
 // Mirrors the entry points of real-space/tfQMRgpu tfQMRgpu/source/tfqmrgpu.cu (same names,
 // argument meaning and status codes); the implementation behind them is this library's own.
-// The solve itself -- the tfQMR driver, the refinement, the preconditioner's glue -- is tfq_solve.cpp.
+// The solve itself -- the tfQMR driver, the refinement -- is tfq_solve.cpp; the preconditioner's set-up and the state of the A in the
+// buffer are tfq_precond_host.cpp.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <vector>
 
 #include "tfq_solve.hpp"
+#include "tfq_precond.hpp"
 #include "tfq_order.hpp"
 #include "tfq_vec.hpp"
 #include "tfq_switch.hpp"
@@ -142,6 +145,11 @@ static tfqmrgpuStatus_t transfer_blocks(Plan& p, hipStream_t s, int direction, b
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
+// an X-shaped native vector of the plan (float or double, as the caller's) <-> the caller's array [nnzbX][2][LM][LN] in its own block order
+static tfqmrgpuStatus_t transfer_x_vector(Plan& p, DevPlan const& d, hipStream_t s, int direction, bool dbl, void* native, void* user, Stage const* own = nullptr) {
+    return transfer_blocks(p, s, direction, dbl, Target{native, dbl, p.ilv}, user, d.u2i, p.nnzbX, p.LM, p.LN, TFQMRGPU_LAYOUT_RRRRIIII, false, false, own);
+}
+
 static tfqmrgpuStatus_t upload(void* dst, void const* src, size_t bytes, hipStream_t s) {
     if (0 == bytes || !src) return TFQMRGPU_STATUS_SUCCESS;
     TFQ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
@@ -186,8 +194,7 @@ tfqmrgpuStatus_t tfqmrgpuDestroyHandle(tfqmrgpuHandle_t handle) {       // refer
     if (nullptr == handle) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
     auto h = (Handle*)handle;
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
-    if (h->voteBuf) (void)hipFree(h->voteBuf);
-    delete h;
+    delete h;                               // (its device memory goes with it: DevMem)
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
@@ -250,14 +257,8 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_destroyPlan(tfqmrgpuHandle_t handle, tfqmrgpuBsr
     (void)handle;
     auto p = asPlan(plan);
     if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (p->ring) { (void)hipHostFree(p->ring); for (auto e : p->ringEvent) (void)hipEventDestroy((hipEvent_t)e); }
-    if (p->opScratch) (void)hipFree(p->opScratch);
-    if (p->precond) (void)hipFree(p->precond);
-    if (p->blockList) (void)hipFree(p->blockList);
-    release_kept(*p);
-    if (p->keepList) (void)hipFree(p->keepList);
     p->magic = 0;
-    delete p;
+    delete p;                               // (every piece of library-owned memory has its owner in the plan: DevMem, PinnedRing)
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
@@ -284,10 +285,8 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     tfqmrgpuStatus_t st;
     try { st = layoutBuffer(*p, LM, LN, prec); }
     catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    if (p->opScratch) { (void)hipFree(p->opScratch); p->opScratch = nullptr; }   // sized for the previous block shape
-    if (p->precond) { (void)hipFree(p->precond); p->precond = nullptr; }         // likewise
-    p->precondInA = TFQMRGPU_PRECOND_NONE; p->haveA = false;                     // (the A of the new layout has not been set)
-    release_kept(*p);                                                            // (a kept copy is one of the old layout)
+    p->opScratch.release();                // sized for the previous block shape
+    a_new_layout(*p);
     p->precision = prec;
     p->buffer = nullptr;
     *pBufferSizeInBytes = p->bufferBytes;
@@ -302,8 +301,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);        // bufferSize has not been called
     hipStream_t const s = (hipStream_t)h->stream;
     p->buffer = (char*)pBuffer;
-    p->precondInA = TFQMRGPU_PRECOND_NONE; p->haveA = false;   // this buffer holds no A yet, scaled or not (tfqmrgpu_ext.h section 7)
-    release_kept(*p);                                           // and a kept copy (section 9) belongs to the A of the old one
+    a_new_buffer(*p);
     auto at = [&](Window const& w) { return (void*)(p->buffer + w.offset); };
     for (auto const& l : indexLists(*p))   // (tfq_plan.cpp: the windows were sized from the same list)
         if (auto const st = upload(at(*l.window), l.data, l.bytes, s)) return st;
@@ -323,8 +321,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
         GlibcRand rng(1);
         float const denom = 1. / 2147483647;                            // tfqmrgpu_linalg.hxx:799-801
         for (size_t i = 0; i < n; ++i) v3[i] = rng.next() * denom;
-        auto const st = transfer_blocks(*p, s, 0, false, Target{d.v3, false, p->ilv}, v3.data(), d.u2i, p->nnzbX, p->LM, p->LN, TFQMRGPU_LAYOUT_RRRRIIII, false, false);
-        if (st) return st;
+        if (auto const st = transfer_x_vector(*p, d, s, 0, false, d.v3, v3.data())) return st;
         p->v3IsHash = false; p->selfStale = true;
     } else {
         p->v3IsHash = true; p->selfStale = true;
@@ -360,23 +357,59 @@ static tfqmrgpuStatus_t layout_and_trans(tfqmrgpuDataLayout_t const layout, char
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
-// reference tfqmrgpu::set_or_getMatrix, tfqmrgpu.cu:467-603
-static tfqmrgpuStatus_t set_or_get(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var, void* values,
-    char const precision, char const transposition, tfqmrgpuDataLayout_t const layout, bool const is_get)
+// an operand of the plan by its name, as far as the argument checks need it (no buffer yet)
+struct Operand { int which; uint32_t nnzb; int nC; };   // which: 0 A, 1 B, 2 X; blocks of LM x nC
+static bool operand_of(Plan const& p, char const var, Operand& o) {
+    switch (lower(var)) {
+        case 'a': o = Operand{0, p.nnzbA, p.LM}; return true;
+        case 'b': o = Operand{1, p.nnzbB, p.LN}; return true;
+        case 'x': o = Operand{2, p.nnzbX, p.LN}; return true;
+        default: return false;
+    }
+}
+
+// setMatrix / getMatrix (reference tfqmrgpu::set_or_getMatrix, tfqmrgpu.cu:467-603) and setBlocks / getBlocks (tfqmrgpu_ext.h section 8)
+// are one path.  The whole operand is the case "no list" (listed == false): its blocks 0 ... nnzb - 1.  A listed call names nBlocks blocks
+// in `blocks`; getBlocks(blocks == NULL) is a third case: the X blocks on B's pattern, by the plan's own list.  Every check is host code and
+// comes before the first device call; the ORDER of the checks is each entry point's own and is pinned by tests
+static tfqmrgpuStatus_t operand_transfer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var, bool const listed, int32_t const nListed,
+    int32_t const* blocks, void* values, char const precision, char const transposition, tfqmrgpuDataLayout_t const layout, bool const is_get)
 {
     bool conj = false, trans = false;
     if (auto const st = layout_and_trans(layout, transposition, conj, trans)) return st;
     auto p = asPlan(plan); auto h = (Handle*)handle;
     if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
-    uint32_t nnzb = 0; int nR = p->LM, nC = p->LN; int which = 0;
-    switch (lower(var)) {
-        case 'a': nnzb = p->nnzbA; nC = p->LM; trans = !trans; which = 0; if (!is_get) p->mixedFloor = 0; break; // A is stored transposed (tfqmrgpu.cu:514-517); (a new operator: the remembered float floor goes)
-        case 'b': nnzb = p->nnzbB; which = 1; break;
-        case 'x': nnzb = p->nnzbX; which = 2; break;
-        default: return err(TFQMRGPU_VARIABLENAME_UNKNOWN, __LINE__ % 10000, var);
+    if (listed && is_get && 'x' != lower(var))   // only X: the status of getMatrix itself (it looks at `var` first)
+        return tfqmrgpu_bsrsv_getMatrix(handle, plan, var, values, precision, 0, 0, transposition, layout);
+    Operand o{};
+    if (!operand_of(*p, var, o)) return err(TFQMRGPU_VARIABLENAME_UNKNOWN, __LINE__ % 10000, var);
+    bool const isA = (0 == o.which);
+    if (isA) trans = !trans;                     // A is stored transposed (tfqmrgpu.cu:514-517)
+    bool const onB = (listed && is_get && nullptr == blocks);   // the X blocks on B's pattern, in B's block order
+    uint32_t nBlocks = o.nnzb;
+    if (!listed) {
+        if (isA && !is_get) a_named(*p);
+        if (o.nnzb < 1) return TFQMRGPU_STATUS_SUCCESS;
+    } else {
+        // the list: every index inside the operand, and no block set twice (the later of two values would win by chance)
+        if (onB) { if (nListed < 0 || uint32_t(nListed) != p->nnzbB) return TFQ_ERR(TFQMRGPU_POINTER_INVALID); }
+        else if (nListed < 0) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
+        if (0 == nListed) return TFQMRGPU_STATUS_SUCCESS;
+        nBlocks = uint32_t(nListed);
+        if (!onB) {
+            if (nullptr == blocks) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+            try {
+                std::vector<bool> seen(is_get ? 0 : o.nnzb, false);
+                for (int32_t k = 0; k < nListed; ++k) {
+                    if (blocks[k] < 0 || uint32_t(blocks[k]) >= o.nnzb) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
+                    if (is_get) continue;   // reading a block twice is harmless
+                    if (seen[blocks[k]]) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
+                    seen[blocks[k]] = true;
+                }
+            } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+        }
     }
-    if (nnzb < 1) return TFQMRGPU_STATUS_SUCCESS;
     if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     bool const mixed = ('m' == p->precision);
     bool const is_double = ('z' == p->precision);
@@ -385,14 +418,28 @@ static tfqmrgpuStatus_t set_or_get(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t 
     // A, B and X are double (A also float), the values are converted on the way
     if (!mixed && user_double != is_double) return err(TFQMRGPU_PRECISION_MISSMATCH, __LINE__ % 10000, precision);
     if (nullptr == values) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    bool intoKept = false;                       // listed blocks of a scaled A: refused, or into the kept copy of the caller's A (section 9)
+    if (listed && isA && !is_get) if (auto const st = a_patched(*p, blocks, nListed, intoKept)) return st;
+
+    // where the operand lives: the buffer ('m': its double side, and for A the float copy of the inner solves beside it), or the kept copy
     hipStream_t const s = (hipStream_t)h->stream;
     DevPlan const d = mixed ? resolveZ(*p) : resolve(*p);
-    Target const to{ (0 == which) ? d.A : (1 == which) ? d.B : d.x, d.dbl, d.ilv };
-    Target const floatA{ p->buffer + p->wA.offset, false, p->ilv };              // mixed: the inner solves multiply with A in float
-    uint32_t const* u2n = (2 == which) ? d.u2i : nullptr;
-    auto const st = transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, nnzb, nR, nC, layout, trans, conj, nullptr,
-                                    (mixed && 0 == which && !is_get) ? &floatA : nullptr);
-    if (0 == which && !is_get) { p->haveA = !st; p->precondInA = TFQMRGPU_PRECOND_NONE; forget_dirty(*p); }   // a new A: not scaled, the preconditioner of the last one is stale (and so is a kept copy, with its patches)
+    Target to{ isA ? d.A : (1 == o.which) ? d.B : d.x, d.dbl, d.ilv };
+    Target floatA{ p->buffer + p->wA.offset, false, p->ilv };
+    if (intoKept) { auto const kept = kept_a(*p); to.native = kept.a; floatA.native = kept.aFloat; }
+    uint32_t const* u2n = (2 == o.which && !onB) ? d.u2i : nullptr;
+    uint32_t const* list = nullptr;
+    if (onB) list = d.subset;                    // the plan's own list, which holds NATIVE block indices of X (Plan::subset_i)
+    else if (listed) {
+        if (auto const st = p->blockList.reserve(size_t(nBlocks) * 4)) return st;
+        // stream order keeps this copy behind the launches of an earlier call; the caller's list is free again once the call returns
+        TFQ_HIP(hipMemcpyAsync(p->blockList.ptr, blocks, size_t(nBlocks) * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        list = p->blockList.as<uint32_t>();      // (checked: 0 <= blocks[k] < nnzb, so int32 and uint32 read the same)
+    }
+    auto const st = transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, nBlocks, p->LM, o.nC, layout, trans, conj, nullptr,
+                                    (mixed && isA && !is_get) ? &floatA : nullptr, list);
+    if (!listed && isA && !is_get) a_set_whole(*p, !st);
     return st;
 }
 
@@ -400,7 +447,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setMatrix(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     void const* val, char const precision, int const ld, int const d2, char const trans, tfqmrgpuDataLayout_t const layout)
 {
     (void)ld; (void)d2;   // ignored by the reference as well (tfqmrgpu.cu:615-616)
-    return set_or_get(handle, plan, var, (void*)val, precision, trans, layout, false);
+    return operand_transfer(handle, plan, var, false, 0, nullptr, (void*)val, precision, trans, layout, false);
 }
 
 tfqmrgpuStatus_t tfqmrgpu_bsrsv_getMatrix(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var,
@@ -408,7 +455,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_getMatrix(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
 {
     (void)ld; (void)d2;
     if ('x' != lower(var)) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);  // only X (tfqmrgpu.cu:635-643)
-    return set_or_get(handle, plan, var, val, precision, trans, layout, true);
+    return operand_transfer(handle, plan, var, false, 0, nullptr, val, precision, trans, layout, true);
 }
 
 tfqmrgpuStatus_t tfqmrgpu_bsrsv_solve(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double const threshold, int const maxIterations) {
@@ -503,6 +550,14 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_c(int mb, int ldA, int ldB,
 
 // ---- extensions (include/tfqmrgpu_ext.h) --------------------------------------------------------------
 
+// the three views of a solve's profile: all launches that did work, those that returned at once, those of the first iteration
+static tfqmrgpuStatus_t get_profile(tfqmrgpuBsrsvPlan_t plan, int64_t const (Plan::*count)[16], double const (Plan::*ms)[16], int64_t* launches, double* milliseconds) {
+    auto p = asPlan(plan);
+    if (!p || !launches || !milliseconds) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    for (int k = 0; k < TFQMRGPU_PROFILE_CLASSES; ++k) { launches[k] = (p->*count)[k]; milliseconds[k] = (p->*ms)[k]; }
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
 tfqmrgpuStatus_t tfqmrgpuExt_planView(tfqmrgpuBsrsvPlan_t plan, tfqmrgpuPlanView_t* v) {
     auto p = asPlan(plan);
     if (!p || !v) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
@@ -530,17 +585,15 @@ tfqmrgpuStatus_t tfqmrgpuExt_setProfiling(tfqmrgpuBsrsvPlan_t plan, int on) {
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getProfile(tfqmrgpuBsrsvPlan_t plan, int64_t* launches, double* milliseconds) {
-    auto p = asPlan(plan);
-    if (!p || !launches || !milliseconds) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    for (int k = 0; k < TFQMRGPU_PROFILE_CLASSES; ++k) { launches[k] = p->profLaunches[k]; milliseconds[k] = p->profMs[k]; }
-    return TFQMRGPU_STATUS_SUCCESS;
+    return get_profile(plan, &Plan::profLaunches, &Plan::profMs, launches, milliseconds);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getProfileGated(tfqmrgpuBsrsvPlan_t plan, int64_t* launches, double* milliseconds) {
-    auto p = asPlan(plan);
-    if (!p || !launches || !milliseconds) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    for (int k = 0; k < TFQMRGPU_PROFILE_CLASSES; ++k) { launches[k] = p->profGatedLaunches[k]; milliseconds[k] = p->profGatedMs[k]; }
-    return TFQMRGPU_STATUS_SUCCESS;
+    return get_profile(plan, &Plan::profGatedLaunches, &Plan::profGatedMs, launches, milliseconds);
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_getProfileFirst(tfqmrgpuBsrsvPlan_t plan, int64_t* launches, double* milliseconds) {
+    return get_profile(plan, &Plan::profFirstLaunches, &Plan::profFirstMs, launches, milliseconds);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getMultiplyKernel(tfqmrgpuBsrsvPlan_t plan, char* name, int32_t capacity) {
@@ -552,13 +605,6 @@ tfqmrgpuStatus_t tfqmrgpuExt_getMultiplyKernel(tfqmrgpuBsrsvPlan_t plan, char* n
     std::snprintf(name, size_t(capacity), "%s", spmm_kernel_family(d));
     return TFQMRGPU_STATUS_SUCCESS;
 }
-tfqmrgpuStatus_t tfqmrgpuExt_getProfileFirst(tfqmrgpuBsrsvPlan_t plan, int64_t* launches, double* milliseconds) {
-    auto p = asPlan(plan);
-    if (!p || !launches || !milliseconds) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    for (int k = 0; k < TFQMRGPU_PROFILE_CLASSES; ++k) { launches[k] = p->profFirstLaunches[k]; milliseconds[k] = p->profFirstMs[k]; }
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
 tfqmrgpuStatus_t tfqmrgpuExt_setThreeProductMultiply(tfqmrgpuBsrsvPlan_t plan, int on) {
     auto p = asPlan(plan);
     if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
@@ -590,16 +636,14 @@ tfqmrgpuStatus_t tfqmrgpuExt_setShadowVector(tfqmrgpuHandle_t handle, tfqmrgpuBs
     if (!p || !h || !v3 || !p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     DevPlan const d = resolve(*p);
     p->v3IsHash = false; p->selfStale = true;
-    return transfer_blocks(*p, (hipStream_t)h->stream, 0, false, Target{d.v3, false, p->ilv}, (void*)v3, d.u2i, p->nnzbX, p->LM, p->LN,
-                           TFQMRGPU_LAYOUT_RRRRIIII, false, false);
+    return transfer_x_vector(*p, d, (hipStream_t)h->stream, 0, false, d.v3, (void*)v3);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getShadowVector(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, float* v3) {
     auto p = asPlan(plan); auto h = (Handle*)handle;
     if (!p || !h || !v3 || !p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     DevPlan const d = resolve(*p);
-    return transfer_blocks(*p, (hipStream_t)h->stream, 1, false, Target{d.v3, false, p->ilv}, (void*)v3, d.u2i, p->nnzbX, p->LM, p->LN,
-                           TFQMRGPU_LAYOUT_RRRRIIII, false, false);
+    return transfer_x_vector(*p, d, (hipStream_t)h->stream, 1, false, d.v3, (void*)v3);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getWorkVector(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, int which, void* values) {
@@ -614,17 +658,15 @@ tfqmrgpuStatus_t tfqmrgpuExt_getWorkVector(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
         default: return err(TFQMRGPU_VARIABLENAME_UNKNOWN, __LINE__ % 10000, char('0' + (which & 7)));
     }
     // the usual staging area IS the work vectors: this getter brings its own
-    Stage st{nullptr, std::min<size_t>(p->S, size_t(64) << 20)};
-    st.bytes = std::max(st.bytes, size_t(2) * p->LM * p->LN * ('z' == p->precision ? 8 : 4));
-    if (hipSuccess != hipMalloc((void**)&st.ptr, st.bytes)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
-    auto const status = transfer_blocks(*p, (hipStream_t)h->stream, 1, 'z' == p->precision, Target{v, 'z' == p->precision, p->ilv}, values, d.u2i, p->nnzbX, p->LM, p->LN,
-                                        TFQMRGPU_LAYOUT_RRRRIIII, false, false, &st);
-    (void)hipFree(st.ptr);
-    return status;
+    DevMem mem;
+    size_t const bytes = std::max(std::min<size_t>(p->S, size_t(64) << 20), size_t(2) * p->LM * p->LN * ('z' == p->precision ? 8 : 4));
+    if (auto const st = mem.reserve(bytes)) return st;
+    Stage const stage{mem.as<char>(), bytes};
+    return transfer_x_vector(*p, d, (hipStream_t)h->stream, 1, 'z' == p->precision, v, values, &stage);
 }
 
 // ---- prepared launch order of the stand-alone multiply (tfq_order.cpp) -----------------------------------------------------------
-namespace { struct MultiplyOrder { uint32_t magic = 0x6f726472u; uint32_t nY = 0; uint32_t* perm = nullptr; }; }
+namespace { struct MultiplyOrder { uint32_t magic = 0x6f726472u; uint32_t nY = 0; DevMem perm; }; }
 
 tfqmrgpuStatus_t tfqmrgpuExt_multiplyPrepare(tfqmrgpuHandle_t handle, char precision, int lm, int ln, uint32_t nnzbY,
     uint32_t const* starts_d, uint32_t const* pairs_d, int mode, void** order)
@@ -645,13 +687,12 @@ tfqmrgpuStatus_t tfqmrgpuExt_multiplyPrepare(tfqmrgpuHandle_t handle, char preci
         TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
         for (uint32_t y = 0; y < nnzbY; ++y) if (starts[y + 1] < starts[y]) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
         auto const perm = multiply_order(nnzbY, starts.data(), pairs.data(), ch, mode, uint32_t(lm * lm), uint32_t(lm * ln));
-        auto* o = new MultiplyOrder;
+        std::unique_ptr<MultiplyOrder> o(new MultiplyOrder);
         o->nY = nnzbY;
-        if (hipSuccess != hipMalloc((void**)&o->perm, size_t(nnzbY) * 4)) { delete o; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-        if (hipSuccess != hipMemcpyAsync(o->perm, perm.data(), size_t(nnzbY) * 4, hipMemcpyHostToDevice, s) || hipSuccess != hipStreamSynchronize(s)) {
-            (void)hipFree(o->perm); delete o; return TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
-        }
-        *order = o;
+        if (auto const st = o->perm.reserve(size_t(nnzbY) * 4)) return st;
+        TFQ_HIP(hipMemcpyAsync(o->perm.ptr, perm.data(), size_t(nnzbY) * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        *order = o.release();
     } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     return TFQMRGPU_STATUS_SUCCESS;
 }
@@ -660,7 +701,6 @@ tfqmrgpuStatus_t tfqmrgpuExt_multiplyRelease(void* order) {
     auto o = (MultiplyOrder*)order;
     if (!o) return TFQMRGPU_STATUS_SUCCESS;
     if (o->magic != 0x6f726472u) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (o->perm) (void)hipFree(o->perm);
     o->magic = 0; delete o;
     return TFQMRGPU_STATUS_SUCCESS;
 }
@@ -672,7 +712,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_multiplyOrdered(tfqmrgpuHandle_t handle, char preci
     if (!h || !starts_d || !pairs_d || !A_d || !X_d || !Y_d) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     auto o = (MultiplyOrder const*)order;
     if (o && (o->magic != 0x6f726472u || o->nY != nnzbY)) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);   // an order belongs to ONE listing
-    return launch_multiply(precision, lm, ln, nnzbY, starts_d, pairs_d, A_d, X_d, Y_d, (hipStream_t)h->stream, o ? o->perm : nullptr);
+    return launch_multiply(precision, lm, ln, nnzbY, starts_d, pairs_d, A_d, X_d, Y_d, (hipStream_t)h->stream, o ? o->perm.as<uint32_t>() : nullptr);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_multiply(tfqmrgpuHandle_t handle, char precision, int lm, int ln,
@@ -741,15 +781,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_setPreconditioner(tfqmrgpuBsrsvPlan_t plan, int kin
 tfqmrgpuStatus_t tfqmrgpuExt_keepOperator(tfqmrgpuBsrsvPlan_t plan, int on) {
     auto p = asPlan(plan);
     if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (0 != on) {
-        // the A in the buffer is A M^-1 already and nobody has the caller's: there is nothing to keep (a plan that is on has its copy)
-        if (!p->keepA && TFQMRGPU_PRECOND_NONE != p->precondInA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
-        p->keepA = true;
-    } else {
-        p->keepA = false;
-        release_kept(*p);                       // from here on the plan is one that never kept anything
-    }
-    return TFQMRGPU_STATUS_SUCCESS;
+    return a_keep(*p, 0 != on);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getPreconditioner(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, void* Minv, int32_t* nIdentity) {
@@ -767,109 +799,17 @@ tfqmrgpuStatus_t tfqmrgpuExt_getPreconditioner(tfqmrgpuHandle_t handle, tfqmrgpu
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
-// ---- listed blocks (tfqmrgpu_ext.h section 8) --------------------------------------------------------------------------------------
-// setBlocks / getBlocks: set_or_get for the blocks that `blocks` names.  Every check is host code and comes before the first device call
-static tfqmrgpuStatus_t set_or_get_blocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var, int32_t const nBlocks,
-    int32_t const* blocks, void* values, char const precision, char const transposition, tfqmrgpuDataLayout_t const layout, bool const is_get)
-{
-    bool conj = false, trans = false;
-    if (auto const st = layout_and_trans(layout, transposition, conj, trans)) return st;
-    auto p = asPlan(plan); auto h = (Handle*)handle;
-    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
-    if (is_get && 'x' != lower(var))   // only X: the status of getMatrix itself (it looks at `var` first)
-        return tfqmrgpu_bsrsv_getMatrix(handle, plan, var, values, precision, 0, 0, transposition, layout);
-    uint32_t nnzb = 0; int nR = p->LM, nC = p->LN; int which = 0;
-    switch (lower(var)) {
-        case 'a': nnzb = p->nnzbA; nC = p->LM; trans = !trans; which = 0; break;   // A is stored transposed, as in setMatrix
-        case 'b': nnzb = p->nnzbB; which = 1; break;
-        case 'x': nnzb = p->nnzbX; which = 2; break;
-        default: return err(TFQMRGPU_VARIABLENAME_UNKNOWN, __LINE__ % 10000, var);
-    }
-    // the list: every index inside the operand, and no block set twice (the later of two values would win by chance)
-    bool const onB = (is_get && nullptr == blocks);   // the X blocks on B's pattern, in B's block order
-    if (onB) { if (nBlocks < 0 || uint32_t(nBlocks) != p->nnzbB) return TFQ_ERR(TFQMRGPU_POINTER_INVALID); }
-    else if (nBlocks < 0) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
-    if (0 == nBlocks) return TFQMRGPU_STATUS_SUCCESS;
-    if (!onB) {
-        if (nullptr == blocks) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-        try {
-            std::vector<bool> listed(is_get ? 0 : nnzb, false);
-            for (int32_t k = 0; k < nBlocks; ++k) {
-                if (blocks[k] < 0 || uint32_t(blocks[k]) >= nnzb) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
-                if (is_get) continue;   // reading a block twice is harmless
-                if (listed[blocks[k]]) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
-                listed[blocks[k]] = true;
-            }
-        } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    }
-    if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    bool const mixed = ('m' == p->precision);
-    bool const is_double = ('z' == p->precision);
-    bool const user_double = ('z' == lower(precision));
-    if (!mixed && user_double != is_double) return err(TFQMRGPU_PRECISION_MISSMATCH, __LINE__ % 10000, precision);
-    if (nullptr == values) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    // A M^-1 cannot be patched: M changes with the diagonal blocks.  A whole setMatrix('A') brings the caller's A back -- unless the plan
-    // keeps it (section 9): then the patch goes into the copy, and the next set-up redoes the block rows and columns that it touches
-    bool const intoKept = (0 == which && !is_get && kept_is_callers_a(*p));
-    if (0 == which && TFQMRGPU_PRECOND_NONE != p->precondInA && !intoKept) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
-    if (intoKept) {
-        try {
-            if (p->cscPtr.empty()) {                // once per plan: the blocks of A grouped by block column
-                p->cscPtr.assign(size_t(p->nRows) + 1, 0u);
-                for (auto const c : p->colOfA) ++p->cscPtr[c + 1];
-                for (uint32_t c = 0; c < p->nRows; ++c) p->cscPtr[c + 1] += p->cscPtr[c];
-                p->cscBlock.resize(p->nnzbA);
-                std::vector<uint32_t> fill(p->cscPtr.begin(), p->cscPtr.end() - 1);
-                for (uint32_t q = 0; q < p->nnzbA; ++q) p->cscBlock[fill[p->colOfA[q]]++] = q;
-            }
-            p->dirtyRow.resize(p->nRows, uint8_t(0)); p->dirtyCol.resize(p->nRows, uint8_t(0));
-        } catch (std::bad_alloc const&) { p->cscPtr.clear(); return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    }
-
-    hipStream_t const s = (hipStream_t)h->stream;
-    DevPlan const d = mixed ? resolveZ(*p) : resolve(*p);
-    uint32_t const* list = d.subset;            // B's pattern: the plan's own list, which holds NATIVE block indices of X (Plan::subset_i)
-    uint32_t const* u2n = nullptr;
-    if (!onB) {
-        if (p->blockListCap < size_t(nBlocks)) {
-            // (a launch of an earlier call may still read the old list: hipFree waits for the device)
-            if (p->blockList) { (void)hipFree(p->blockList); p->blockList = nullptr; p->blockListCap = 0; }
-            if (hipSuccess != hipMalloc((void**)&p->blockList, size_t(nBlocks) * 4)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
-            p->blockListCap = size_t(nBlocks);
-        }
-        // stream order keeps this copy behind the launches of an earlier call; the caller's list is free again once the call returns
-        TFQ_HIP(hipMemcpyAsync(p->blockList, blocks, size_t(nBlocks) * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        list = p->blockList;                    // (checked: 0 <= blocks[k] < nnzb, so int32 and uint32 read the same)
-        u2n = (2 == which) ? d.u2i : nullptr;
-    }
-    if (0 == which) p->mixedFloor = 0;          // a new operator: the remembered float floor goes.  haveA stays: a patch makes no whole A
-    if (intoKept) {                             // what the next set-up has to redo: the columns that hold a listed block, the rows whose diagonal block is listed
-        for (int32_t k = 0; k < nBlocks; ++k) {
-            uint32_t const q = uint32_t(blocks[k]), c = p->colOfA[q];
-            p->dirtyCol[c] = 1;
-            if (p->diagOfRow[c] == q) p->dirtyRow[c] = 1;
-        }
-        p->anyDirty = true;
-    }
-    auto const kept = kept_a(*p);
-    Target const to{ intoKept ? (void*)kept.a : (0 == which) ? d.A : (1 == which) ? d.B : d.x, d.dbl, d.ilv };
-    Target const floatA{ intoKept ? kept.aFloat : p->buffer + p->wA.offset, false, p->ilv };   // mixed: the inner solves multiply with A in float
-    return transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, uint32_t(nBlocks), nR, nC, layout, trans, conj, nullptr,
-                           (mixed && 0 == which && !is_get) ? &floatA : nullptr, list);
-}
-
+// ---- listed blocks (tfqmrgpu_ext.h section 8): operand_transfer with a list ----------------------------------------------------------
 tfqmrgpuStatus_t tfqmrgpuExt_setBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var,
     int32_t const nBlocks, int32_t const* blocks, void const* values, char const precision, char const trans, tfqmrgpuDataLayout_t const layout)
 {
-    return set_or_get_blocks(handle, plan, var, nBlocks, blocks, (void*)values, precision, trans, layout, false);
+    return operand_transfer(handle, plan, var, true, nBlocks, blocks, (void*)values, precision, trans, layout, false);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, char const var,
     int32_t const nBlocks, int32_t const* blocks, void* values, char const precision, char const trans, tfqmrgpuDataLayout_t const layout)
 {
-    return set_or_get_blocks(handle, plan, var, nBlocks, blocks, values, precision, trans, layout, true);
+    return operand_transfer(handle, plan, var, true, nBlocks, blocks, values, precision, trans, layout, true);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_setReduceCallback(tfqmrgpuHandle_t handle, tfqmrgpuReduceMax_t fn, void* ctx) {

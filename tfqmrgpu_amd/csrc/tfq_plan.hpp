@@ -4,7 +4,9 @@
 #pragma once
 #include <cstdint>
 #include <cstddef>
+#include <utility>
 #include <vector>
+#include <hip/hip_runtime_api.h>
 
 #include "tfqmrgpu.h"
 #include "tfqmrgpu_ext.h"
@@ -18,6 +20,55 @@ inline tfqmrgpuStatus_t err(int code, int line = 0, int key = 0) {
 #define TFQ_ERR(code) ::tfq::err((code), __LINE__ % 10000)
 
 inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+// ---- library-owned memory: every allocation the library makes for itself has ONE owner, whose destructor releases it.  destroyPlan,
+// DestroyHandle and multiplyRelease are `delete`; a new member of this kind needs no line anywhere else
+struct DevMem {     // device memory (hipMalloc), move-only
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { release(); std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); } return *this; }
+    DevMem(DevMem const&) = delete;
+    DevMem& operator=(DevMem const&) = delete;
+    ~DevMem() { release(); }
+    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
+    // at least n bytes.  Grows only, and never copies: what is there is FREED before the larger piece is allocated -- a launch of an earlier
+    // call may still read the old piece, and hipFree waits for the device
+    tfqmrgpuStatus_t reserve(size_t n) {
+        if (ptr && n <= bytes) return TFQMRGPU_STATUS_SUCCESS;
+        release();
+        if (hipSuccess != hipMalloc(&ptr, n)) { ptr = nullptr; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+        bytes = n;
+        return TFQMRGPU_STATUS_SUCCESS;
+    }
+    template <typename T> T* as() const { return static_cast<T*>(ptr); }
+    explicit operator bool() const { return nullptr != ptr; }
+};
+
+// pinned host memory in kDepth slots with an event (no timing) behind each: the copies of the control block that a solve reads back
+// (tfq_solve.cpp: Slots).  It lives with the plan: hipHostMalloc and event creation cost more than a small solve
+struct PinnedRing {
+    static constexpr int kDepth = 4;
+    void* ptr = nullptr;
+    hipEvent_t event[kDepth] = {};
+    PinnedRing() = default;
+    PinnedRing(PinnedRing const&) = delete;
+    PinnedRing& operator=(PinnedRing const&) = delete;
+    ~PinnedRing() { release(); }
+    void release() {
+        for (auto& e : event) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+        if (ptr) (void)hipHostFree(ptr);
+        ptr = nullptr;
+    }
+    tfqmrgpuStatus_t ensure(size_t slotBytes) {     // all of it or nothing
+        if (ptr) return TFQMRGPU_STATUS_SUCCESS;
+        if (hipSuccess != hipHostMalloc(&ptr, kDepth * slotBytes, hipHostMallocDefault)) { ptr = nullptr; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+        for (auto& e : event)
+            if (hipSuccess != hipEventCreateWithFlags(&e, hipEventDisableTiming)) { e = nullptr; release(); return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+        return TFQMRGPU_STATUS_SUCCESS;
+    }
+};
 
 // Long block columns are summed by several work groups (tfq_colops.hpp: column_total).  A segment is what one work group sums in ONE
 // round of loads (256 / LN lane groups x 16 records in flight); columns of at most four segments stay with one work group.  The plan sizes
@@ -63,7 +114,7 @@ struct Handle {
     int nranks = 1, rank = 0;
     tfqmrgpuReduceMax_t reduceFn = nullptr;
     void* reduceCtx = nullptr;
-    double* voteBuf = nullptr;            // 4 doubles of device memory for the collective in front of a solve (RCCL path)
+    DevMem voteBuf;                       // 4 doubles of device memory for the collective in front of a solve (RCCL path)
 };
 
 struct Plan {
@@ -123,40 +174,40 @@ struct Plan {
     bool foldOk = false;               // few enough chunks that an iteration slot is launch latency: fold (tfq_colops.hpp)
 
     char* buffer = nullptr;            // device buffer registered by setBuffer
-    static constexpr int kDepth = 4;   // iterations the host keeps enqueued ahead of the stopping decision
-    void* ring = nullptr;              // pinned copies of the control block, one per in-flight iteration
-    void* ringEvent[kDepth] = {};      // hipEvent_t behind each copy
+    static constexpr int kDepth = PinnedRing::kDepth;   // iterations the host keeps enqueued ahead of the stopping decision
+    PinnedRing ring;                   // pinned copies of the control block, one per in-flight iteration, and the event behind each copy
     int shadowMode = TFQMRGPU_SHADOW_HASH;
     bool v3IsHash = false;             // the buffer's v3 holds the counter-based hash (set by setBuffer, cleared by a user-supplied vector)
     bool threeProducts = false;        // tfqmrgpuExt_setThreeProductMultiply: Gauss' three real products per complex one in the double multiplies
     std::vector<double> cycleResidual; // 'm': relative residual (double arithmetic) in front of every inner solve and at the end
     std::vector<int32_t> cycleIterations; // 'm': float iterations of every inner solve
     int refinementCycles = 0;
-    double mixedFloor = 0;             // 'm': the gain at which the first float solve of this plan's last solve ran into its floor (0: not known; forgotten with a new A)
     // user-defined operator (tfqmrgpu_ext.h section 5): callback, and library-owned device scratch
     // [xu | yu | i2u | colindx in the caller's block order]
     void* opFn = nullptr; void* opCtx = nullptr;
-    char* opScratch = nullptr;
+    DevMem opScratch;                  // (tfq_solve.cpp: op_scratch; sized by the block shape: released by bufferSize)
     // block-Jacobi right preconditioner (tfqmrgpu_ext.h section 7)
     std::vector<uint32_t> diagOfRow;   // [nRows] the diagonal block of each block row of A, ~0u: the pattern has none
     std::vector<uint32_t> colOfA;      // [nnzbA] block column of each block of A
     int precondKind = TFQMRGPU_PRECOND_NONE;     // what the caller asked for
-    int precondInA = TFQMRGPU_PRECOND_NONE;      // what the A in the buffer has been scaled with (NONE: it is the caller's A)
-    bool haveA = false;
-    int32_t precondIdentity = 0;       // block rows whose M_ii is the unit matrix (no diagonal block, or a singular one)
-    char* precond = nullptr;           // library-owned device memory [M^-1 | diagOfRow | colOfA | counter], allocated at the first preconditioned solve
+    DevMem precond;                    // library-owned device memory [M^-1 | diagOfRow | colOfA | counter | flags], allocated at the first preconditioned solve
+    bool keepA = false;                // tfqmrgpuExt_keepOperator: keep the caller's own A next to the scaled one (tfqmrgpu_ext.h section 9)
+    DevMem keepList;                   // device copy of [dirty rows | blocks of the dirty columns] of a partial set-up, grown on demand
 
-    // the caller's own A next to the scaled one (tfqmrgpu_ext.h section 9; tfq_solve.cpp: precond_prepare)
-    bool keepA = false;                // tfqmrgpuExt_keepOperator
-    char* aKept = nullptr;             // library-owned device copy of the A window as it was before it was scaled ('m': the double A, then the float A);
+    // ---- the state of the A in the buffer: what it holds, and what is stale.  Written by the transitions of tfq_precond_host.cpp
+    // (a_new_layout ... a_restored) and by nobody else
+    bool haveA = false;                // a whole setMatrix('A') has succeeded on this buffer
+    int precondInA = TFQMRGPU_PRECOND_NONE;      // what the A in the buffer has been scaled with (NONE: it is the caller's A)
+    int32_t precondIdentity = 0;       // block rows whose M_ii is the unit matrix (no diagonal block, or a singular one), as of the last set-up
+    double mixedFloor = 0;             // 'm': the gain at which the first float solve of this plan's last solve ran into its floor (0: not known; forgotten with a new A)
+    DevMem aKept;                      // library-owned device copy of the A window as it was before it was scaled ('m': the double A, then the float A);
                                        // it is the caller's A while precondInA != NONE, stale otherwise
     std::vector<uint8_t> dirtyRow, dirtyCol;   // [nRows] since the last set-up setBlocks('A') has written: the diagonal block of this row | a block of this column
     bool anyDirty = false;
     std::vector<uint32_t> cscPtr, cscBlock;    // the blocks of A grouped by block column, built at the first such setBlocks('A')
-    uint32_t* keepList = nullptr; size_t keepListCap = 0;   // device copy of [dirty rows | blocks of the dirty columns], grown on demand (entries)
 
     // setBlocks / getBlocks (tfqmrgpu_ext.h section 8): library-owned device copy of the caller's block list, grown on demand
-    uint32_t* blockList = nullptr; size_t blockListCap = 0;   // (entries)
+    DevMem blockList;
 
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;

@@ -1,9 +1,39 @@
-// launch interface of the block-Jacobi right preconditioner (tfq_precond.hip; tfqmrgpu_ext.h section 7)
+// The block-Jacobi right preconditioner (tfqmrgpu_ext.h sections 7 and 9): the launch interface of its kernels (tfq_precond.hip), and its
+// host side (tfq_precond_host.cpp): the plan's memory for it, the set-up in front of a solve, and the state of the A in the buffer
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
+#include "tfq_plan.hpp"
+
 namespace tfq {
+
+#pragma GCC visibility push(hidden)   // the host side is shared by files of the library and no part of its symbol list
+
+// ---- the library-owned memory of a plan: one function says how large, one where
+struct PrecondMem { char* minv; uint32_t* diag; uint32_t* colA; uint32_t* counter; uint32_t* identity; size_t minvBytes; };
+size_t precond_bytes(Plan const& p);
+PrecondMem precond_mem(Plan const& p);      // the pieces of Plan::precond (allocated)
+
+// the kept copy of the caller's A (section 9): Plan::aKept holds the A window of the buffer, for 'm' the double A (`a`) followed by the float A (`aFloat`)
+struct KeptA { char* a; char* aFloat; size_t aBytes, aFloatBytes; };
+size_t kept_a_bytes(Plan const& p);
+KeptA kept_a(Plan const& p);                // the pieces of Plan::aKept (allocated)
+inline bool kept_is_callers_a(Plan const& p) { return p.keepA && p.aKept && TFQMRGPU_PRECOND_NONE != p.precondInA; }
+
+// ---- what a solve needs before its first iteration, and behind its last
+tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p);
+tfqmrgpuStatus_t precond_back(Handle& h, Plan& p);      // X := M^-1 Y
+
+// ---- the state of the A in the buffer (Plan::haveA ... Plan::cscBlock): every transition, by the call that causes it
+void a_new_layout(Plan& p);                             // bufferSize
+void a_new_buffer(Plan& p);                             // setBuffer
+void a_named(Plan& p);                                  // setMatrix('A'), before its argument checks
+void a_set_whole(Plan& p, bool ok);                     // setMatrix('A'), behind its transfer
+tfqmrgpuStatus_t a_patched(Plan& p, int32_t const* blocks, int32_t nBlocks, bool& intoKept);   // setBlocks('A'), behind its argument checks
+tfqmrgpuStatus_t a_keep(Plan& p, bool on);              // keepOperator
+
+#pragma GCC visibility pop
 
 // Minv[row] := inverse of the diagonal block of block row `row` of A, [nRows][2][LM][LM] (Re plane, Im plane, row-major, NOT transposed),
 // in double (wDbl) or float.  A: the plan's operator as it sits in the buffer (blocks transposed, element order ilv), double (aDbl) or

@@ -1,5 +1,5 @@
-// Host side of the solver: the tfQMR driver (run_tfqmr), the mixed-precision refinement around it (run_mixed), the glue of the
-// block-Jacobi preconditioner, the RCCL and roctx loaders and the flop model.  No kernel lives here; tfq_api.hip is the C-ABI in front.
+// Host side of the solver: the tfQMR driver (run_tfqmr), the mixed-precision refinement around it (run_mixed), the RCCL and roctx loaders
+// and the flop model.  No kernel lives here; tfq_api.hip is the C-ABI in front, tfq_precond_host.cpp the preconditioner's set-up.
 #include <cstdlib>
 #include <cmath>
 #include <algorithm>
@@ -48,8 +48,7 @@ static tfqmrgpuStatus_t reduce_over_ranks(Handle& h, double* red, int n, hipStre
 }
 
 tfqmrgpuStatus_t ensure_vote_buffer(Handle& h) {
-    if (!h.voteBuf) TFQ_HIP(hipMalloc((void**)&h.voteBuf, 4 * sizeof(double)), TFQMRGPU_STATUS_ALLOCATION_FAILED)
-    return TFQMRGPU_STATUS_SUCCESS;
+    return h.voteBuf.reserve(4 * sizeof(double));
 }
 
 // the mark "this rank has failed" in a record that is about to be max-reduced: a pageable source the device may read at any later time
@@ -118,48 +117,28 @@ tfqmrgpuStatus_t vote(Handle& h, hipStream_t s, tfqmrgpuStatus_t early, int& ahe
     if (!several_ranks(h)) return early;
     if (!h.voteBuf) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
     double ballot[2] = { double(ahead), early ? 1. : 0. };
-    TFQ_HIP(hipMemcpyAsync(h.voteBuf, ballot, sizeof ballot, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    if (auto const st = reduce_over_ranks(h, h.voteBuf, 2, s)) return st;
-    TFQ_HIP(hipMemcpyAsync(ballot, h.voteBuf, sizeof ballot, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    double* const buf = h.voteBuf.as<double>();
+    TFQ_HIP(hipMemcpyAsync(buf, ballot, sizeof ballot, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    if (auto const st = reduce_over_ranks(h, buf, 2, s)) return st;
+    TFQ_HIP(hipMemcpyAsync(ballot, buf, sizeof ballot, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
     TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
     ahead = std::min(DEPTH, std::max(1, int(ballot[0])));
     if (!early && ballot[1] > 0.) early = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);   // a peer cannot start: nobody does
     return early;
 }
 
-// pinned ring + events live with the plan (hipHostMalloc / event creation cost more than a small solve)
-tfqmrgpuStatus_t ensure_ring(Plan& p) {
-    if (p.ring) return TFQMRGPU_STATUS_SUCCESS;
-    TFQ_HIP(hipHostMalloc((void**)&p.ring, DEPTH * sizeof(Ctl), hipHostMallocDefault), TFQMRGPU_STATUS_ALLOCATION_FAILED)
-    for (auto& e : p.ringEvent) {
-        hipEvent_t ev_ = nullptr;
-        if (hipSuccess != hipEventCreateWithFlags(&ev_, hipEventDisableTiming)) {
-            for (auto& f : p.ringEvent) { if (f) (void)hipEventDestroy((hipEvent_t)f); f = nullptr; }
-            (void)hipHostFree(p.ring); p.ring = nullptr;
-            return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
-        }
-        e = (void*)ev_;
-    }
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
 // user-defined operator (tfqmrgpu_ext.h section 5): the plan's scratch [xu | yu | i2u | colindx in the caller's block order]
-struct OpScratch { char* xu; char* yu; uint32_t* i2u; uint16_t* colU; size_t bytes; };
-OpScratch op_scratch(Plan const& p) {
-    size_t const vecBytes = size_t(p.nnzbX) * 2 * p.LM * p.LN * ('z' == p.precision ? 8 : 4);
-    OpScratch o{};
-    char* q = p.opScratch;
-    o.xu = q;               q += align256(vecBytes);
-    o.yu = q;               q += align256(vecBytes);
-    o.i2u = (uint32_t*)q;   q += align256(size_t(p.nnzbX) * 4);
-    o.colU = (uint16_t*)q;  q += align256(size_t(p.nnzbX) * 2);
-    o.bytes = size_t(q - p.opScratch);
-    return o;
+struct OpScratch { char* xu; char* yu; uint32_t* i2u; uint16_t* colU; };
+size_t op_vector_bytes(Plan const& p) { return align256(size_t(p.nnzbX) * 2 * p.LM * p.LN * ('z' == p.precision ? 8 : 4)); }
+size_t op_scratch_bytes(Plan const& p) { return 2 * op_vector_bytes(p) + align256(size_t(p.nnzbX) * 4) + align256(size_t(p.nnzbX) * 2); }
+OpScratch op_scratch(Plan const& p) {       // the pieces of Plan::opScratch (allocated)
+    char* const b = p.opScratch.as<char>();
+    size_t const v = op_vector_bytes(p);
+    return { b, b + v, (uint32_t*)(b + 2 * v), (uint16_t*)(b + 2 * v + align256(size_t(p.nnzbX) * 4)) };
 }
 tfqmrgpuStatus_t ensure_op_scratch(Plan& p, hipStream_t s) {
     if (p.opScratch) return TFQMRGPU_STATUS_SUCCESS;
-    size_t const bytes = op_scratch(p).bytes;               // (offsets only: p.opScratch is null)
-    TFQ_HIP(hipMalloc((void**)&p.opScratch, bytes ? bytes : 256), TFQMRGPU_STATUS_ALLOCATION_FAILED)
+    if (auto const st = p.opScratch.reserve(std::max<size_t>(op_scratch_bytes(p), 256))) return st;
     auto const o = op_scratch(p);
     std::vector<uint16_t> cu(p.nnzbX);      // compressed block column per block, caller's order
     for (uint32_t u = 0; u < p.nnzbX; ++u) cu[u] = p.colindx[u];
@@ -198,8 +177,8 @@ struct Slots {
         if (p.opFn) op = op_scratch(p);
         last.state = (maxIt > 0) ? 0 : 3; last.residual2_reached = 1e300; last.iterations_needed = maxIt;
     }
-    Ctl* ring() const { return (Ctl*)p.ring; }
-    hipEvent_t ringEvent(int slot) const { return (hipEvent_t)p.ringEvent[slot]; }
+    Ctl* ring() const { return (Ctl*)p.ring.ptr; }
+    hipEvent_t ringEvent(int slot) const { return p.ring.event[slot]; }
 
     // the device-resident copy that the folded column operations read: taken again whenever a plan flag has changed since the last
     // one (hashV3, m3: setShadowVector / setShadowMode / setThreeProductMultiply; the copy of setBuffer predates the shadow vector),
@@ -356,7 +335,7 @@ static tfqmrgpuStatus_t run_tfqmr(Handle& h, Plan& p, double tol, int maxIt, tfq
     int ahead = (depthEnv >= 1 && depthEnv <= DEPTH) ? depthEnv : 2;
     if (auto const st = vote(h, s, early, ahead)) return st;
 
-    if (auto const st = ensure_ring(p)) return st;
+    if (auto const st = p.ring.ensure(sizeof(Ctl))) return st;
     if (p.opFn) if (auto const st = ensure_op_scratch(p, s)) return st;
     Slots run(h, p, maxIt, histScale);
     if (auto const st = run.refresh_self()) return st;
@@ -378,171 +357,6 @@ struct FlopModel {
     }
     double solve(Ctl const& c) const { return fNrm + c.iteration * (2 * fMult + 2 * fDot + 2 * fNrm + 10 * fAxp) + c.nprobes * (fMult + fNrm); }
 };
-
-// ---- block-Jacobi right preconditioner (tfqmrgpu_ext.h section 7; kernels: tfq_precond.hip) ------------------------------------------
-// With M = blockdiag(A) the iteration runs on (A M^-1) Y = B: A M^-1 has the pattern of A and takes its place in the buffer, once per
-// setMatrix('A'); X = M^-1 Y has the pattern of Y and is formed in place at the end of a solve.  No iteration kernel knows about it.
-PrecondMem precond_mem(Plan const& p) {
-    size_t const real = ('c' == p.precision) ? 4 : 8;       // M^-1 in the plan's precision, double for 'm'
-    PrecondMem m{};
-    m.minvBytes = size_t(p.nRows) * 2 * p.LM * p.LM * real;
-    char* q = p.precond;
-    m.minv = q;              q += align256(m.minvBytes);
-    m.diag = (uint32_t*)q;   q += align256(size_t(p.nRows) * 4);
-    m.colA = (uint32_t*)q;   q += align256(size_t(p.nnzbA) * 4);
-    m.counter = (uint32_t*)q; q += 256;
-    m.identity = (uint32_t*)q; q += align256(size_t(p.nRows) * 4);   // a flag per block row: M_ii is the unit matrix (plans that keep A)
-    m.bytes = size_t(q - p.precond);
-    return m;
-}
-
-KeptA kept_a(Plan const& p) {
-    bool const mixed = ('m' == p.precision);
-    KeptA k{};
-    k.aBytes = mixed ? p.wAz.bytes : p.wA.bytes;
-    k.aFloatBytes = mixed ? p.wA.bytes : 0;
-    k.a = p.aKept;
-    k.aFloat = mixed ? p.aKept + align256(k.aBytes) : nullptr;
-    k.bytes = align256(k.aBytes) + align256(k.aFloatBytes);
-    return k;
-}
-void forget_dirty(Plan& p) {
-    if (!p.anyDirty) return;
-    std::fill(p.dirtyRow.begin(), p.dirtyRow.end(), uint8_t(0));
-    std::fill(p.dirtyCol.begin(), p.dirtyCol.end(), uint8_t(0));
-    p.anyDirty = false;
-}
-void release_kept(Plan& p) {
-    if (p.aKept) { (void)hipFree(p.aKept); p.aKept = nullptr; }
-    forget_dirty(p);
-}
-
-// precondIdentity from the flags that the listed inversion keeps per block row
-static tfqmrgpuStatus_t count_identity_flags(Plan& p, PrecondMem const& m, hipStream_t s) {
-    std::vector<uint32_t> flags(p.nRows);
-    TFQ_HIP(hipMemcpyAsync(flags.data(), m.identity, flags.size() * 4, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    int32_t n = 0;
-    for (auto const f : flags) n += (0 != f);
-    p.precondIdentity = n;
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-// setBlocks('A') has patched the kept copy since the last set-up: M^-1 again for the block rows whose diagonal block was written, and
-// A_ij M_jj^-1 again, from the copy into the buffer, for every block of the block columns that hold a written block.  The listed kernels
-// share their element loops with the whole set-up, so each block has the bits that a whole setMatrix('A') and a whole set-up would give it
-static tfqmrgpuStatus_t precond_update(Handle& h, Plan& p) {
-    hipStream_t const s = (hipStream_t)h.stream;
-    std::vector<uint32_t> list;                             // [dirty rows | blocks of the dirty columns]
-    for (uint32_t r = 0; r < p.nRows; ++r) if (p.dirtyRow[r]) list.push_back(r);
-    uint32_t const nRowsListed = uint32_t(list.size());
-    for (uint32_t c = 0; c < p.nRows; ++c) if (p.dirtyCol[c]) list.insert(list.end(), p.cscBlock.begin() + p.cscPtr[c], p.cscBlock.begin() + p.cscPtr[c + 1]);
-    uint32_t const nBlocksListed = uint32_t(list.size()) - nRowsListed;
-    if (p.keepListCap < list.size()) {
-        if (p.keepList) { (void)hipFree(p.keepList); p.keepList = nullptr; p.keepListCap = 0; }
-        TFQ_HIP(hipMalloc((void**)&p.keepList, list.size() * 4), TFQMRGPU_STATUS_ALLOCATION_FAILED)
-        p.keepListCap = list.size();
-    }
-    TFQ_HIP(hipMemcpyAsync(p.keepList, list.data(), list.size() * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)   // (`list` is a local)
-    auto const m = precond_mem(p);
-    auto const k = kept_a(p);
-    bool const mixed = ('m' == p.precision), wDbl = ('c' != p.precision);
-    DevPlan const d = mixed ? resolveZ(p) : resolve(p);
-    uint32_t const* const blocks = p.keepList + nRowsListed;
-    launch_precond_invert_listed(d.dbl, wDbl, k.a, m.diag, m.minv, m.identity, p.keepList, nRowsListed, p.LM, d.ilv, s);
-    launch_precond_apply_listed(d.dbl, wDbl, true, k.a, d.A, nBlocksListed, blocks, m.colA, m.minv, p.LM, p.LM, d.ilv, s);
-    if (mixed) launch_precond_apply_listed(false, true, true, k.aFloat, p.buffer + p.wA.offset, nBlocksListed, blocks, m.colA, m.minv, p.LM, p.LM, p.ilv, s);
-    if (auto const st = count_identity_flags(p, m, s)) return st;   // a row can have become singular, or regular
-    forget_dirty(p);
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-// the kind has changed on a plan that keeps A: the caller's A goes back into the buffer
-static tfqmrgpuStatus_t precond_restore(Handle& h, Plan& p) {
-    hipStream_t const s = (hipStream_t)h.stream;
-    auto const k = kept_a(p);
-    bool const mixed = ('m' == p.precision);
-    TFQ_HIP(hipMemcpyAsync(p.buffer + (mixed ? p.wAz.offset : p.wA.offset), k.a, k.aBytes, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    if (mixed) TFQ_HIP(hipMemcpyAsync(p.buffer + p.wA.offset, k.aFloat, k.aFloatBytes, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    p.precondInA = TFQMRGPU_PRECOND_NONE;
-    p.mixedFloor = 0;                                       // (the floor that was remembered is that of the scaled operator)
-    forget_dirty(p);                                        // the copy had every patch
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-// what a solve needs before its first iteration: nothing when the preconditioner is off; otherwise M^-1 and the scaled A, made here
-// when the A in the buffer is still the caller's (the first solve after setMatrix('A')) and reused by every later solve of that A.
-// A plan that keeps A (section 9) copies the A window first; later it redoes what setBlocks('A') has touched, and follows a change of kind
-static tfqmrgpuStatus_t precond_prepare_(Handle& h, Plan& p) {
-    if (TFQMRGPU_PRECOND_NONE == p.precondKind && TFQMRGPU_PRECOND_NONE == p.precondInA) return TFQMRGPU_STATUS_SUCCESS;
-    if (p.opFn) {   // a user-defined operator has no blocks to scale -- and never reads the A in the buffer, scaled or not
-        return (TFQMRGPU_PRECOND_NONE != p.precondKind) ? TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION) : TFQMRGPU_STATUS_SUCCESS;
-    }
-    bool const kept = kept_is_callers_a(p);
-    if (p.precondInA == p.precondKind) return (kept && p.anyDirty) ? precond_update(h, p) : TFQMRGPU_STATUS_SUCCESS;
-    if (TFQMRGPU_PRECOND_NONE != p.precondInA) {
-        // the kind has changed since A was scaled: only a fresh setMatrix('A') brings the caller's A back -- or the kept copy
-        if (!kept) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
-        if (auto const st = precond_restore(h, p)) return st;
-        if (TFQMRGPU_PRECOND_NONE == p.precondKind) return TFQMRGPU_STATUS_SUCCESS;
-    }
-    if (!p.buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (!p.haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
-    hipStream_t const s = (hipStream_t)h.stream;
-    if (!p.precond) {
-        size_t const bytes = precond_mem(p).bytes;          // (offsets only: p.precond is null)
-        TFQ_HIP(hipMalloc((void**)&p.precond, bytes), TFQMRGPU_STATUS_ALLOCATION_FAILED)
-        auto const m = precond_mem(p);
-        TFQ_HIP(hipMemcpyAsync(m.diag, p.diagOfRow.data(), p.diagOfRow.size() * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        if (p.nnzbA) TFQ_HIP(hipMemcpyAsync(m.colA, p.colOfA.data(), p.colOfA.size() * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    }
-    auto const m = precond_mem(p);
-    bool const mixed = ('m' == p.precision), wDbl = ('c' != p.precision);
-    DevPlan const d = mixed ? resolveZ(p) : resolve(p);      // mixed: M^-1 comes from the double copy of A
-    if (p.keepA) {   // the caller's A, device to device, before it is scaled in place: block order, transposition and element order are the buffer's
-        if (!p.aKept) TFQ_HIP(hipMalloc((void**)&p.aKept, std::max<size_t>(kept_a(p).bytes, 256)), TFQMRGPU_STATUS_ALLOCATION_FAILED)
-        auto const k = kept_a(p);
-        TFQ_HIP(hipMemcpyAsync(k.a, d.A, k.aBytes, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        if (mixed) TFQ_HIP(hipMemcpyAsync(k.aFloat, p.buffer + p.wA.offset, k.aFloatBytes, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        forget_dirty(p);
-        // every row through the listed form: it leaves the flag per row that a later partial set-up recounts from
-        launch_precond_invert_listed(d.dbl, wDbl, d.A, m.diag, m.minv, m.identity, nullptr, p.nRows, p.LM, d.ilv, s);
-    } else {
-        TFQ_HIP(hipMemsetAsync(m.counter, 0, 4, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        launch_precond_invert(d.dbl, wDbl, d.A, m.diag, m.minv, m.counter, p.nRows, p.LM, d.ilv, s);
-    }
-    // A_ij := A_ij M_jj^-1; the blocks are stored transposed, so this is block := (M_jj^-1)^T block
-    launch_precond_apply(d.dbl, wDbl, true, d.A, p.nnzbA, m.colA, m.minv, p.LM, p.LM, d.ilv, s);
-    if (mixed) launch_precond_apply(false, true, true, p.buffer + p.wA.offset, p.nnzbA, m.colA, m.minv, p.LM, p.LM, p.ilv, s);   // the float copy of the inner solves
-    if (p.keepA) { if (auto const st = count_identity_flags(p, m, s)) return st; }
-    else {
-        uint32_t n = 0;
-        TFQ_HIP(hipMemcpyAsync(&n, m.counter, 4, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        p.precondIdentity = int32_t(n);
-    }
-    p.precondInA = p.precondKind;
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p) {
-    try { return precond_prepare_(h, p); }   // (the lists of a partial set-up are host vectors; no exception may cross the C boundary)
-    catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-}
-
-// X := M^-1 Y at the end of a solve, on the solver's stream ('m': once, in double, on the refined solution)
-static tfqmrgpuStatus_t precond_back(Handle& h, Plan& p) {
-    if (TFQMRGPU_PRECOND_BLOCK_JACOBI != p.precondInA) return TFQMRGPU_STATUS_SUCCESS;
-    auto const m = precond_mem(p);
-    DevPlan const d = ('m' == p.precision) ? resolveZ(p) : resolve(p);
-    launch_precond_apply(d.dbl, 'c' != p.precision, false, d.x, p.nnzbX, d.rowI, m.minv, p.LM, p.LN, d.ilv, (hipStream_t)h.stream);
-    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    p.flops_performed += 8. * p.LM * p.LM * p.LN * p.nnzbX;
-    return TFQMRGPU_STATUS_SUCCESS;
-}
 
 // What a refinement cycle asks of its float solve (host arithmetic only; every rank computes the same values from the same reduced residual).
 // tol: the refinement's threshold, res2: the double residual^2 in front of this cycle, bestGain / lastGain: the factor the best / the last
@@ -605,9 +419,9 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt) {
         if (!multi) return st;
         if (!h.voteBuf) return st;                           // (allocated with the communicator / callback; without it no collective can be entered)
         double const mark[3] = { 0., 0., 1. };
-        if (hipSuccess != hipMemcpyAsync(h.voteBuf, mark, sizeof mark, hipMemcpyHostToDevice, s)) return st;
+        if (hipSuccess != hipMemcpyAsync(h.voteBuf.ptr, mark, sizeof mark, hipMemcpyHostToDevice, s)) return st;
         if (hipSuccess != hipStreamSynchronize(s)) return st;
-        (void)reduce_over_ranks(h, h.voteBuf, 3, s);
+        (void)reduce_over_ranks(h, h.voteBuf.as<double>(), 3, s);
         (void)hipStreamSynchronize(s);
         return st;
     };

@@ -1,5 +1,5 @@
-// What tfq_api.hip (the C-ABI) and tfq_solve.cpp (the host side of the solver) share: the entry points of the solve that the ABI
-// calls, and the status check of runtime calls that both use.
+// What tfq_api.hip (the C-ABI), tfq_solve.cpp (the host side of the solver) and tfq_precond_host.cpp (that of the preconditioner) share:
+// the entry points of the solve that the ABI calls, and the status check of runtime calls that all three use.
 #pragma once
 #include "tfq_device.hpp"
 
@@ -16,7 +16,7 @@ struct Rccl {
     bool load();
 };
 
-#pragma GCC visibility push(hidden)   // what follows is shared by two files of the library and no part of its symbol list
+#pragma GCC visibility push(hidden)   // what follows is shared by files of the library and no part of its symbol list
 
 static inline tfqmrgpuStatus_t hipCheck(hipError_t e, int code, int line) {
     return (hipSuccess == e) ? TFQMRGPU_STATUS_SUCCESS : err(code, line % 10000);
@@ -30,19 +30,6 @@ tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt);
 // a reduction over ranks or a foreign multiply sits between the producer and the decision otherwise
 inline bool several_ranks(Handle const& h) { return h.comm != nullptr || h.reduceFn != nullptr; }
 inline bool folds(Plan const& p, bool severalRanks) { return p.foldOk && !severalRanks && !p.opFn; }
-
-// ---- block-Jacobi right preconditioner: the library-owned memory of a plan, and what a solve needs before its first iteration
-struct PrecondMem { char* minv; uint32_t* diag; uint32_t* colA; uint32_t* counter; uint32_t* identity; size_t minvBytes, bytes; };
-PrecondMem precond_mem(Plan const& p);
-tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p);
-
-// ---- the kept copy of the caller's A (tfqmrgpu_ext.h section 9): Plan::aKept holds the A window of the buffer, for 'm' the double A
-// (`a`) followed by the float A (`aFloat`)
-struct KeptA { char* a; char* aFloat; size_t aBytes, aFloatBytes, bytes; };
-KeptA kept_a(Plan const& p);
-inline bool kept_is_callers_a(Plan const& p) { return p.keepA && p.aKept && TFQMRGPU_PRECOND_NONE != p.precondInA; }
-void forget_dirty(Plan& p);            // a whole new A, or the set-up has caught up
-void release_kept(Plan& p);            // the copy goes (bufferSize, setBuffer, keepOperator(0), destroyPlan)
 
 extern Rccl g_rccl;
 
