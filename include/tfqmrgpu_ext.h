@@ -335,6 +335,50 @@ tfqmrgpuStatus_t tfqmrgpuExt_getBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPla
  * Several ranks (section 4): every rank holds all of A, and everything above is local to a rank. */
 tfqmrgpuStatus_t tfqmrgpuExt_keepOperator(tfqmrgpuBsrsvPlan_t plan, int on);
 
+/* ---- (10) per-right-hand-side residual of the caller's system ---------------------------- */
+/* getInfo gives ONE residual, the maximum over all right-hand sides of all block columns, and solve ONE status.  After
+ * TFQMRGPU_STATUS_MAX_ITERATIONS or TFQMRGPU_STATUS_BREAKDOWN the caller cannot tell which right-hand sides are good; the solver's own
+ * probe sums in the plan's precision (float on a 'c' plan and inside the float solves of an 'm' plan); and nothing grades an X that the
+ * caller brought.  residual computes |B - A X|^2 and |B|^2 per (block column, right-hand side) on the device, in double, without
+ * fetching X.
+ *
+ * residual2[c*LN + j] = sum over the blocks of compressed block column c of |(B - A X)(:, j)|^2,
+ * bnorm2[c*LN + j]    = the same sum of |B(:, j)|^2,           both HOST arrays [nCols][LN] of double, either may be NULL;
+ * columns[c]          = the caller's block column index of compressed column c (tfqmrgpuPlanView_t::original_bsrColIndX, incl. indexOffset),
+ *                       a HOST array [nCols], may be NULL;
+ * *worst              = sqrt(max over c, j of residual2 / bnorm2), may be NULL.  All four NULL: TFQMRGPU_STATUS_NO_INFO_PASSED.
+ *
+ * Operands: A is the caller's A; B what the last setMatrix('B') / setBlocks('B') left; X what getMatrix('X') would return at that
+ *   moment -- after a solve the solution (back-transformed on a preconditioned plan, section 7), after setMatrix('X') / setBlocks('X')
+ *   the caller's X.
+ * The product A X is truncated to the pattern of X, as every product of the solver is; blocks of X that carry no B
+ *   block contribute |A X|^2.  This is the quantity `threshold` is defined on.
+ * Arithmetic: every product and every sum runs in double, whatever the plan's precision.  'z': double data.  'c': float data converted
+ *   on load, so that each float x float product is exact in double.  'm': the plan's double copies of X, B and A.  Always four real
+ *   products per complex one, whatever setThreeProductMultiply says.
+ * Deterministic: one [LN] record per chunk of a block column, written by one work group; the chunks of a column are added in chunk
+ *   order by one work group per column; no atomics.  Two calls on the same data give the same bits.
+ * The quotient is the IEEE one: a right-hand side with b = 0 gives NaN if r = 0, else +inf.  *worst ignores NaN entries; it is NaN only
+ *   if every entry is.
+ * Non-destructive: the call writes nothing into the caller's buffer -- not the work vectors v4 ... v9, not the partial sums and
+ *   records of a solve, not its control block.  tfqmrgpuExt_getWorkVector and getBoundHistory behind it return what they returned in
+ *   front of it, and a following solve is the solve it would have been.  Its scratch ([nChunks][2][LN] + [nCols][2][LN] doubles) is
+ *   device memory that the library owns, allocated at the first call and released by destroyPlan and by bufferSize; bufferSize and the
+ *   buffer layout do not change.  A plan that never calls it runs the launches it ran before.
+ * Stream: asynchronous on the handle's stream up to the copy-out; it synchronises that stream once to fill the host arrays.  Do not
+ *   call it during a solve.
+ * All checks come before the first device call, in this order: plan / handle pointers as in getMatrix; no bufferSize yet:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR; all four outputs NULL: TFQMRGPU_STATUS_NO_INFO_PASSED; no buffer: TFQMRGPU_POINTER_INVALID; a plan with a
+ *   user-defined operator (section 5): TFQMRGPU_NO_IMPLEMENTATION, the operator is the caller's to apply; A never set whole on this
+ *   buffer: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A' (status = 14 + 1000 * line + 10^7 * 'A'); the A in the buffer has been
+ *   scaled by the preconditioner (section 7) and the plan keeps no copy: TFQMRGPU_NO_IMPLEMENTATION -- the caller's A is gone;
+ *   `keepOperator` keeps it.  After any error nothing has been written, neither device nor host arrays.
+ * With keepOperator (section 9) and a scaled buffer the kernel reads the kept copy ('m': its double part).  Patches of setBlocks('A')
+ *   that no set-up has seen yet are in the copy already, so they count.
+ * Several ranks (section 4): local to the rank's own block columns, no collective.  getInfo: nothing in it changes. */
+tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double *residual2, double *bnorm2, int32_t *columns, double *worst);
+
 #ifdef __cplusplus
 }
 #endif

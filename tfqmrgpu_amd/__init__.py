@@ -40,7 +40,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_commDestroy", "tfqmrgpuExt_setReduceCallback", "tfqmrgpuExt_setOperator",
     "tfqmrgpuExt_getRefinementHistory", "tfqmrgpuExt_setThreeProductMultiply",
     "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner", "tfqmrgpuExt_setBlocks", "tfqmrgpuExt_getBlocks",
-    "tfqmrgpuExt_keepOperator",
+    "tfqmrgpuExt_keepOperator", "tfqmrgpuExt_residual",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -143,6 +143,7 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_setBlocks.argtypes = [P, P, C.c_char, C.c_int32, P, P, C.c_char, C.c_char, I]
     lib.tfqmrgpuExt_getBlocks.argtypes = [P, P, C.c_char, C.c_int32, P, P, C.c_char, C.c_char, I]
     lib.tfqmrgpuExt_keepOperator.argtypes = [P, I]
+    lib.tfqmrgpuExt_residual.argtypes = [P, P, P, P, P, C.POINTER(C.c_double)]
     return lib
 
 
@@ -413,6 +414,19 @@ class Solver:
         m = np.zeros((self.problem.mb, 2, self.LM, self.LM), dtype=np.float32 if self.precision == "c" else np.float64) if values else None
         _check(lib.tfqmrgpuExt_getPreconditioner(self.handle, self.plan, _ptr(m) if values else None, C.byref(n)), "tfqmrgpuExt_getPreconditioner")
         return (m[:, 0].astype(np.float64) + 1j * m[:, 1]) if values else None, int(n.value)
+
+    def residual(self):
+        """tfqmrgpu_ext.h section 10: |B - A X|^2 and |B|^2 per (block column, right-hand side) of the caller's A, the plan's B and the
+        X that get_matrix would return, summed in double on the device.  Returns a dict: residual2, bnorm2 [nCols, LN], columns [nCols]
+        (the caller's block column indices), relative = sqrt(residual2 / bnorm2) (IEEE: NaN where both are 0, inf where only b is) and
+        worst, the largest relative residual that is not NaN"""
+        n = int(self.plan_view()["nCols"])
+        r2, b2 = np.zeros((n, self.LN), np.float64), np.zeros((n, self.LN), np.float64)
+        cols, worst = np.zeros(n, np.int32), C.c_double(0)
+        _check(lib.tfqmrgpuExt_residual(self.handle, self.plan, _ptr(r2), _ptr(b2), _ptr(cols), C.byref(worst)), "tfqmrgpuExt_residual")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel = np.sqrt(r2 / b2)
+        return dict(residual2=r2, bnorm2=b2, columns=cols, relative=rel, worst=worst.value)
 
     def bound_history(self):
         n = lib.tfqmrgpuExt_getBoundHistory(self.plan, None, 0)

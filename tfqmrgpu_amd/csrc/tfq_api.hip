@@ -3,6 +3,7 @@
 // argument meaning and status codes); the implementation behind them is this library's own.
 // The solve itself -- the tfQMR driver, the refinement -- is tfq_solve.cpp; the preconditioner's set-up and the state of the A in the
 // buffer are tfq_precond_host.cpp.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -286,6 +287,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     try { st = layoutBuffer(*p, LM, LN, prec); }
     catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     p->opScratch.release();                // sized for the previous block shape
+    p->residualScratch.release();          // ... and the previous chunks
     a_new_layout(*p);
     p->precision = prec;
     p->buffer = nullptr;
@@ -735,6 +737,51 @@ tfqmrgpuStatus_t tfqmrgpuExt_applyOperator(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     // repetitions < 0: |repetitions| launches and nothing else (timing: X stays as it is, the product is left in the work vector)
     if (repetitions >= 0) TFQ_HIP(hipMemcpyAsync(d.x, y, mixed ? p->wXz.bytes : p->S, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
     TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// ---- per-right-hand-side residual of the caller's system (tfqmrgpu_ext.h section 10) --------------------------------------------------
+tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double* residual2, double* bnorm2, int32_t* columns, double* worst)
+{
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
+    if (!residual2 && !bnorm2 && !columns && !worst) return TFQMRGPU_STATUS_NO_INFO_PASSED;
+    if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (p->opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);        // a user-defined operator is the caller's to apply
+    if (!p->haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+    bool const scaled = (TFQMRGPU_PRECOND_NONE != p->precondInA);
+    if (scaled && !kept_is_callers_a(*p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone; keepOperator keeps it
+
+    hipStream_t const s = (hipStream_t)h->stream;
+    DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X, B and A
+    size_t const nRec = size_t(d.nChunks) * 2 * p->LN, nCol = size_t(p->nCols) * 2 * p->LN;
+    std::vector<double> host;
+    try { host.resize(nCol); } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    if (auto const st = p->residualScratch.reserve(std::max<size_t>((nRec + nCol) * sizeof(double), 256))) return st;
+    double* const rec = p->residualScratch.as<double>();
+    // the caller's A: the buffer's, or the kept copy while the buffer holds A M^-1 ('m': its double part) -- a patch of setBlocks('A')
+    // that no set-up has seen yet is in the copy already
+    void const* const A = scaled ? (void const*)kept_a(*p).a : d.A;
+    residual_launch(d, A, rec, rec + nRec, s);
+    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    if (nCol) TFQ_HIP(hipMemcpyAsync(host.data(), rec + nRec, nCol * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+
+    size_t const LN = size_t(p->LN);
+    double wmax = 0; bool any = false;                             // NaN entries (r = b = 0) are left out of the maximum
+    for (size_t c = 0; c < p->nCols; ++c) {
+        for (size_t j = 0; j < LN; ++j) {
+            double const r2 = host[(2 * c) * LN + j], b2 = host[(2 * c + 1) * LN + j];
+            if (residual2) residual2[c * LN + j] = r2;
+            if (bnorm2) bnorm2[c * LN + j] = b2;
+            double const quot = r2 / b2;
+            if (quot == quot) { wmax = any ? std::max(wmax, quot) : quot; any = true; }
+        }
+        if (columns) columns[c] = p->original_bsrColIndX[c];
+    }
+    if (worst) *worst = any ? std::sqrt(wmax) : std::nan("");
     return TFQMRGPU_STATUS_SUCCESS;
 }
 

@@ -209,6 +209,10 @@ struct Plan {
     // setBlocks / getBlocks (tfqmrgpu_ext.h section 8): library-owned device copy of the caller's block list, grown on demand
     DevMem blockList;
 
+    // tfqmrgpuExt_residual (tfqmrgpu_ext.h section 10): library-owned scratch [nChunks][2][LN] + [nCols][2][LN] doubles, allocated at the
+    // first call (sized by the block shape and the chunks: released by bufferSize)
+    DevMem residualScratch;
+
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;
     int iterations_needed = -1;

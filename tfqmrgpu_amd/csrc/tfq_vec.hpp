@@ -32,4 +32,9 @@ void spmm_apply(DevPlan const& d, void const* X, void* Y, hipStream_t s);
 // Yext holds the blocks in the caller's order, i2u[internal block] = caller's block
 void epilogue_launch(int epi, DevPlan const& d, void const* Yext, uint32_t const* i2u, hipStream_t s);
 
+// |B - A X|^2 and |B|^2 per (block column, right-hand side) of the plan's X and B and the operator A (the plan's storage type, block and
+// element order; d.A is NOT read), every product and sum in double (tfq_residual.hip; tfqmrgpuExt_residual).
+// rec [nChunks][2][LN] and col [nCols][2][LN] (the result) are the caller's scratch; nothing else is written
+void residual_launch(DevPlan const& d, void const* A, double* rec, double* col, hipStream_t s);
+
 } // namespace tfq
