@@ -109,11 +109,13 @@ def spmm(precision, LM, LN, starts, pairs, A_nat, X_nat):
     return Y
 
 
-def solve(pr, precision="z", threshold=None, max_iterations=2000, transA="n", v3=None, plan=None, reduce=None, dump_iteration=None):
+def solve(pr, precision="z", threshold=None, max_iterations=2000, transA="n", v3=None, plan=None, reduce=None, dump_iteration=None, status=False):
     """tfQMR on the CPU with the documented (CUDA-path) semantics of the reference.
     v3: float array [nnzbX*2*LM*LN] (default: the glibc rand() sequence of the reference CPU path).
     dump_iteration: info["vectors"] = {1: x, 4: v4, ... 9: v9} (complex [nnzbX][LM][LN]) at the end of that iteration,
-    before its stopping test (tfqmrgpu_core.hxx:233)."""
+    before its stopping test (tfqmrgpu_core.hxx:233).
+    status: info["status"] = the per-RHS status [nCols, LN] as the solve leaves it (0, -1 dec35, -2 dec34, -3 decT, +1 zero residual at a
+    probe), info["status_when"] = {value: [nCols, LN] iteration in which a RHS was first given that value, 0 = never}."""
     L = lib()
     real = np.float64 if precision == "z" else np.float32
     an = plan or analyse(pr)
@@ -134,12 +136,21 @@ def solve(pr, precision="z", threshold=None, max_iterations=2000, transA="n", v3
     dump = np.zeros((7,) + X.shape, dtype=real) if dump_iteration else None
     if dump is not None:
         hook(C.c_int(dump_iteration), _p(dump))
+    shook = L.tfqo_set_status_z if precision == "z" else L.tfqo_set_status_c
+    shook.restype = None
+    stat = np.zeros((an["nCols"], pr.LN), np.int8) if status else None
+    when = np.zeros((4, an["nCols"], pr.LN), np.int32) if status else None
+    if status:
+        shook(_p(stat), _p(when))
     st = fn(C.c_int(pr.LM), C.c_int(pr.LN), C.c_uint32(pr.nnzbX), C.c_uint32(pr.nnzbB), C.c_uint32(an["nCols"]),
             _p(an["starts"]), _p(an["pairs"]), _p(an["subset"]), _p(an["colindx"]),
             _p(A), _p(B), _p(v3), _p(X),
             C.c_double(pr.tolerance if threshold is None else threshold), C.c_int(max_iterations),
             C.byref(it), C.byref(res), C.byref(flops), _p(hist), C.byref(nh), cb, None)
     info = dict(iterations=it.value, residual=res.value, flops=flops.value, bound_history=hist[:nh.value].copy())
+    if status:
+        shook(None, None)
+        info["status"], info["status_when"] = stat, {-1: when[0], -2: when[1], -3: when[2], 1: when[3]}
     if dump is not None:
         hook(C.c_int(0), None)
         info["vectors"] = {w: from_native(dump[n]).astype(np.complex128) for n, w in enumerate((1, 4, 5, 6, 7, 8, 9))}

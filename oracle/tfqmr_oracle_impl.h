@@ -213,6 +213,21 @@ static REAL *FN(dump_buf);
 static int FN(dump_iteration);
 void FN(tfqo_set_dump)(int iteration, REAL *buf) { FN(dump_iteration) = iteration; FN(dump_buf) = buf; }
 
+/* test hook (not in the reference): the per-RHS status array [nCols][LN] as the solve leaves it, and when[4][nCols][LN], the iteration in
+ * which a RHS was FIRST given the value -1 | -2 | -3 | +1 (0: never) -- looked at behind every call that can set one, since a later
+ * one overwrites it (a dec35 breakdown is a dec34 breakdown half a step later: rho == 0); NULL switches it off */
+static int8_t *FN(status_buf);
+static int32_t *FN(status_when);
+void FN(tfqo_set_status)(int8_t *status, int32_t *when) { FN(status_buf) = status; FN(status_when) = when; }
+static void FN(note_status)(int8_t const *status, size_t nR, int iteration)
+{
+    if (!FN(status_when)) return;
+    for (size_t r = 0; r < nR; ++r) {
+        int const v = status[r], k = (v < 0) ? -v - 1 : (v == 1) ? 3 : -1;
+        if (k >= 0 && 0 == FN(status_when)[(size_t)k * nR + r]) FN(status_when)[(size_t)k * nR + r] = iteration;
+    }
+}
+
 /* The tfQMR driver: restates tfqmrgpu::solve (tfqmrgpu_core.hxx:114-325) operation by operation.
  * v3 is supplied by the caller (the reference draws it at setBuffer time).
  * reduce (may be NULL): max-reduces doubles over ranks for the sharded mode (not in the reference).
@@ -253,16 +268,19 @@ int FN(tfqo_solve)(int LM, int LN, uint32_t nnzbX, uint32_t nnzbB, uint32_t nCol
         ++iteration;
         FN(tfqo_dotp)(LM, LN, nnzbX, nCols, colindx, zvv, v5, v3); nFlop += fDot;          /* :189 */
         FN(tfqo_dec35)(LN, nCols, status, rho, beta, zvv);                                  /* :192 */
+        FN(note_status)(status, nR, iteration);
         FN(tfqo_xpay)(LM, LN, nnzbX, colindx, v6, beta, v5); nFlop += fAxp;                 /* :194 */
         FN(tfqo_xpay)(LM, LN, nnzbX, colindx, v4, beta, v8); nFlop += fAxp;                 /* :196 */
         FN(tfqo_spmm)(LM, LN, nnzbX, starts, pairs, A, v6, v9); nFlop += fMult;             /* :198 */
         FN(tfqo_xpay)(LM, LN, nnzbX, colindx, v4, beta, v9); nFlop += fAxp;                 /* :200 */
         FN(tfqo_dotp)(LM, LN, nnzbX, nCols, colindx, zvv, v4, v3); nFlop += fDot;           /* :202 */
         FN(tfqo_dec34)(LN, nCols, status, c67, alfa, rho, eta, zvv, var);                   /* :205 */
+        FN(note_status)(status, nR, iteration);
         FN(tfqo_xpay)(LM, LN, nnzbX, colindx, v7, c67, v6); nFlop += fAxp;                  /* :207 */
         FN(tfqo_axpy)(LM, LN, nnzbX, colindx, v5, v9, alfa); nFlop += fAxp;                 /* :209 */
         FN(tfqo_nrm2)(LM, LN, nnzbX, nCols, colindx, dvv, v5); nFlop += fNrm;               /* :211 */
         FN(tfqo_decT)(LN, nCols, status, c67, eta, var, tau, alfa, dvv);                    /* :214 */
+        FN(note_status)(status, nR, iteration);
         FN(tfqo_axpy)(LM, LN, nnzbX, colindx, v1, v7, eta); nFlop += fAxp;                  /* :216 */
         FN(tfqo_axpy)(LM, LN, nnzbX, colindx, v6, v4, alfa); nFlop += fAxp;                 /* :218 */
         FN(tfqo_xpay)(LM, LN, nnzbX, colindx, v7, c67, v6); nFlop += fAxp;                  /* :220 */
@@ -270,6 +288,7 @@ int FN(tfqo_solve)(int LM, int LN, uint32_t nnzbX, uint32_t nnzbB, uint32_t nCol
         FN(tfqo_axpy)(LM, LN, nnzbX, colindx, v5, v8, alfa); nFlop += fAxp;                 /* :226 */
         FN(tfqo_nrm2)(LM, LN, nnzbX, nCols, colindx, dvv, v5); nFlop += fNrm;               /* :228 */
         FN(tfqo_decT)(LN, nCols, status, NULL, eta, var, tau, alfa, dvv);                   /* :231 */
+        FN(note_status)(status, nR, iteration);
         FN(tfqo_axpy)(LM, LN, nnzbX, colindx, v1, v7, eta); nFlop += fAxp;                  /* :233 */
 
         if (FN(dump_buf) && iteration == FN(dump_iteration)) {
@@ -302,6 +321,7 @@ int FN(tfqo_solve)(int LM, int LN, uint32_t nnzbX, uint32_t nnzbB, uint32_t nCol
                 if (res2 > tol2) { if (0 == status[r]) pr[1] = 1; }
                 else if (res2 <= 0) status[r] = 1;
             }
+            FN(note_status)(status, nR, iteration);
             if (reduce) reduce(reduce_ctx, pr, 2);
             double const max_residual2 = (pr[0] > 1.4e-76) ? pr[0] : 1.4e-76;
             residual2_reached = max_residual2;
@@ -312,6 +332,7 @@ int FN(tfqo_solve)(int LM, int LN, uint32_t nnzbX, uint32_t nnzbB, uint32_t nCol
     *residuum_reached = sqrt(residual2_reached);
     *flops_performed = nFlop;
     if (n_history) *n_history = nhist;
+    if (FN(status_buf)) memcpy(FN(status_buf), status, nR);
     free(v4); free(v5); free(v6); free(v7); free(v8); free(v9);
     free(rho); free(alfa); free(beta); free(c67); free(eta);
     free(zvv); free(dvv); free(tau); free(var); free(invBn2); free(status);

@@ -2,7 +2,9 @@
 and solution to argv[1].  With TFQMRGPU_* tuning switches in the environment the LAB build of the library is loaded
 (libtfQMRgpu_lab.so: the same sources compiled with -DTFQ_LAB, tfq_switch.hpp -- the product has its switches frozen and reads
 nothing from the environment); without, the product.
-argv: out.npz fixture precision threshold [shape for `stencil:` fixtures]"""
+argv: out.npz fixture precision threshold [shape for `stencil:` fixtures]
+A fixture `breakdown:<kind:shape>[,<kind:shape> ...]` names fixtures of tests/breakdown_cases.py: each is solved with its own shadow vector,
+threshold and iteration cap (the threshold argument is not used), and the five arrays are written once per fixture, as `<kind:shape>/status` ..."""
 import os
 import sys
 
@@ -33,6 +35,15 @@ def main():
         os.environ["TFQMRGPU_LIB"] = os.path.join(ROOT, "tfqmrgpu_amd", "lib", "libtfQMRgpu_lab.so")
     import tfqmrgpu_amd as T
     assert os.path.basename(T.LIB_PATH) == ("libtfQMRgpu_lab.so" if switches else "libtfQMRgpu.so"), T.LIB_PATH
+    if name.startswith("breakdown:"):
+        import breakdown_cases as BC
+        out_arrays = {}
+        for case in name[len("breakdown:"):].split(","):
+            st, X, info = BC.gpu_solve(BC.by_name(case), prec)
+            out_arrays.update({case + "/status": st, case + "/iterations": info["iterations"], case + "/residual": info["residual"],
+                               case + "/history": info["bound_history"], case + "/X": X})
+        np.savez(out, **out_arrays)
+        return
     st, X, info = T.solve_problem(problem(name), prec, threshold=tol, max_iterations=300)
     np.savez(out, status=st, iterations=info["iterations"], residual=info["residual"], history=info["bound_history"], X=X)
 

@@ -49,11 +49,15 @@ def plan_paths(pr, prec, fold_max=FOLD_MAX):
     return ch, seg, sum(ch) <= fold_max and max(seg) == 1
 
 
-def gpu_state(pr, prec, k, three=False):
-    """(multiply kernel family, work vectors 1 and 4-9 after exactly k iterations, X)"""
+def gpu_state(pr, prec, k, three=False, v3=None, status=9):
+    """(multiply kernel family, work vectors 1 and 4-9 after exactly k iterations, X)
+    v3: a user shadow vector (float32 [nnzbX, 2, LM, LN]) in place of the default; status: what a solve of k iterations returns"""
     with T.Solver() as s:
         s.create_plan(pr)
         s.set_buffer(nbytes=s.buffer_size(pr.LM, pr.LN, prec))
+        if v3 is not None:
+            v3 = np.ascontiguousarray(v3, dtype=np.float32)
+            assert T.lib.tfqmrgpuExt_setShadowVector(s.handle, s.plan, T._ptr(v3)) == 0
         if three:
             s.set_three_product_multiply(True)
         family = s.multiply_kernel()
@@ -62,21 +66,33 @@ def gpu_state(pr, prec, k, three=False):
         st = s.solve(1e-30, k)
         got = {w: s.get_work_vector(w) for w in (1, 4, 5, 6, 7, 8, 9)}
         X = s.get_matrix()
-    assert st == 9                                            # out of iterations (tfqmrgpu_core.hxx:258)
-    assert np.array_equal(got[1], X)
+    assert st == status                                       # 9: out of iterations (tfqmrgpu_core.hxx:258)
+    assert np.array_equal(got[1], X, equal_nan=v3 is not None)
     return family, got
 
 
-def state_deviation(oracle, pr, prec, k, got):
-    """max over the work vectors of max|gpu - oracle| / max|oracle| after k iterations"""
-    v3 = T.hash_shadow_vector(pr).reshape(-1)
-    st0, X0, info0 = oracle.solve(pr, prec, threshold=1e-30, max_iterations=k, v3=v3, dump_iteration=k)
-    assert st0 == 9
+def state_deviation(oracle, pr, prec, k, got, v3=None, status=9, failed=None):
+    """max over the work vectors of max|gpu - oracle| / max|oracle| after k iterations
+    failed (bool [nnzbX, LN]): right-hand sides that break down on purpose (tests/breakdown_cases.py).  The deviation is then taken
+    over the others alone; on the failed ones the two must agree in what rounding cannot move: the NaN mask, and a zero of the oracle is a
+    zero (asserted here, vector by vector)."""
+    v3 = T.hash_shadow_vector(pr) if v3 is None else v3
+    st0, X0, info0 = oracle.solve(pr, prec, threshold=1e-30, max_iterations=k, v3=np.asarray(v3).reshape(-1), dump_iteration=k)
+    assert st0 == status
     worst = {}
     for w, want in info0["vectors"].items():
+        if failed is not None:
+            dead = np.broadcast_to(failed[:, None, :], want.shape)
+            assert np.array_equal(np.isnan(got[w][dead]), np.isnan(want[dead])), (w, k)
+            assert np.all(got[w][dead][want[dead] == 0] == 0), (w, k)
+            if dead.all():
+                continue
+            got_w, want = got[w][~dead], want[~dead]
+        else:
+            got_w = got[w]
         scale = np.abs(want).max()
         assert scale > 0, w
-        worst[w] = float(np.abs(got[w] - want).max() / scale)
+        worst[w] = float(np.abs(got_w - want).max() / scale)
     return worst
 
 
