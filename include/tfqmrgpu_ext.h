@@ -379,6 +379,53 @@ tfqmrgpuStatus_t tfqmrgpuExt_keepOperator(tfqmrgpuBsrsvPlan_t plan, int on);
 tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
     double *residual2, double *bnorm2, int32_t *columns, double *worst);
 
+/* ---- (11) truncation leak: what A X puts outside the pattern of X ------------------------------------------------------------- */
+/* Every product of this library is truncated to the block pattern of X: solve, `threshold`, getInfo and residual
+ * (section 10) all grade the TRUNCATED problem.  The pattern is the caller's choice -- a truncation radius around each source --, and
+ * nothing above tells whether it was large enough.  What does is the part of A X that falls on block rows OUTSIDE a block column's
+ * pattern: each of those missing blocks is a term of the untruncated residual B - A X~ (X~: X padded with zero blocks to full columns)
+ * that section 10 leaves out.  With X~ zero there and B inside the pattern,
+ *     |B - A X~|^2 (:, j) of block column c  =  residual2[c*LN + j] (section 10)  +  leak2[c*LN + j],
+ * per right-hand side, so that a caller can widen or shrink the radius column by column.
+ *
+ * leak2[c*LN + j] = sum over the block rows i with (i, c) NOT in the pattern of X
+ *                   of | sum over k with (i, k) in the pattern of A and (k, c) in the pattern of X of  A_ik X_kc  (:, j) |^2,
+ *                   a HOST array [nCols][LN] of double, may be NULL; c is the compressed block column, as in section 10.  A block column
+ *                   with no such row (a full column, say) gets exactly 0.0;
+ * columns[c]      = the caller's block column index of compressed column c, a HOST array [nCols], may be NULL: as in section 10;
+ * *nLeakBlocks    = the number of (block row, block column) positions outside the pattern of X that receive a product, may be NULL;
+ * *nLeakPairs     = the number of block products that land there, may be NULL (the products inside the pattern: tfqmrgpuPlanView_t::nPairs).
+ *
+ * Operands: A is the caller's A -- the buffer's, or the kept copy (section 9) while the buffer holds A M^-1, patches of setBlocks('A')
+ *   that no set-up has seen yet included; X what getMatrix('X') would return at that moment.  B is not read.
+ * Arithmetic: every product and every sum runs in double, whatever the plan's precision.  'z': double data.  'c': float data converted
+ *   on load, so that each float x float product is exact in double.  'm': the plan's double copies of X and A.  Always four real
+ *   products per complex one, whatever setThreeProductMultiply says.
+ * Deterministic: one [LN] record per work unit (a run of leak positions of one block column, cut by the number of products, so that a
+ *   long shell is summed by several units), written by one work group; the units of a column are added in unit order by one work group
+ *   per column, which writes 0 for a column without units; no atomics.  Two calls on the same data give the same bits.
+ * Non-destructive: the call writes nothing into the caller's buffer -- not the work vectors v4 ... v9, not the partial sums and records
+ *   of a solve, not its control block; a following solve is the solve it would have been.  bufferSize and the buffer layout do not change.
+ * The listing of the leak positions and their products is built on the host from the plan's patterns at the first call, in time linear
+ *   in the products of A X, the blocks of A and the blocks of X, and kept in the plan; its device copy and the records are device memory
+ *   that the library owns, allocated by the first call that asks for leak2.  Both are released by destroyPlan and by bufferSize.  A plan
+ *   that never makes the call runs the launches it ran before and allocates nothing.
+ * Stream: the first call that asks for leak2 uploads the listing on the handle's stream and synchronises it once; every such call is
+ *   asynchronous on that stream up to the copy-out and synchronises it once to fill leak2.  Do not call it during a solve.
+ * All checks come before the first device call, in the order of section 10: plan / handle pointers; no bufferSize yet:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR; all four outputs NULL: TFQMRGPU_STATUS_NO_INFO_PASSED.  columns, nLeakBlocks and nLeakPairs depend on the
+ *   patterns alone: with leak2 == NULL the call does the host analysis, launches nothing and returns HERE -- it needs the plan and
+ *   bufferSize only, no buffer and no A.  With leak2: no buffer: TFQMRGPU_POINTER_INVALID; a plan with a user-defined operator:
+ *   TFQMRGPU_NO_IMPLEMENTATION; A never set whole on this buffer: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A'; the A in the
+ *   buffer has been scaled by the preconditioner and the plan keeps no copy: TFQMRGPU_NO_IMPLEMENTATION.  After any error nothing has been
+ *   written, neither device nor host arrays.
+ * Several ranks (section 4): local to the rank's own block columns, no collective; every rank holds all of A, so its listing is complete. */
+tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double *leak2, int32_t *columns, uint64_t *nLeakBlocks, uint64_t *nLeakPairs);
+/* How the listing of truncationLeak is cut: the number of work units of every compressed block column into unitsPerColumn (a HOST array
+ * [nCols], may be NULL); returns the number of work units of the plan, 0 while the listing has not been built. */
+int64_t tfqmrgpuExt_leakUnits(tfqmrgpuBsrsvPlan_t plan, uint32_t *unitsPerColumn);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,7 +40,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_commDestroy", "tfqmrgpuExt_setReduceCallback", "tfqmrgpuExt_setOperator",
     "tfqmrgpuExt_getRefinementHistory", "tfqmrgpuExt_setThreeProductMultiply",
     "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner", "tfqmrgpuExt_setBlocks", "tfqmrgpuExt_getBlocks",
-    "tfqmrgpuExt_keepOperator", "tfqmrgpuExt_residual",
+    "tfqmrgpuExt_keepOperator", "tfqmrgpuExt_residual", "tfqmrgpuExt_truncationLeak", "tfqmrgpuExt_leakUnits",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -144,6 +144,9 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_getBlocks.argtypes = [P, P, C.c_char, C.c_int32, P, P, C.c_char, C.c_char, I]
     lib.tfqmrgpuExt_keepOperator.argtypes = [P, I]
     lib.tfqmrgpuExt_residual.argtypes = [P, P, P, P, P, C.POINTER(C.c_double)]
+    lib.tfqmrgpuExt_truncationLeak.argtypes = [P, P, P, P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.tfqmrgpuExt_leakUnits.argtypes = [P, P]
+    lib.tfqmrgpuExt_leakUnits.restype = C.c_int64
     return lib
 
 
@@ -427,6 +430,26 @@ class Solver:
         with np.errstate(divide="ignore", invalid="ignore"):
             rel = np.sqrt(r2 / b2)
         return dict(residual2=r2, bnorm2=b2, columns=cols, relative=rel, worst=worst.value)
+
+    def truncation_leak(self):
+        """tfqmrgpu_ext.h section 11: what A X puts on the block rows OUTSIDE each block column's pattern, |.|^2 per (block column,
+        right-hand side) of the caller's A and the X that get_matrix would return, summed in double on the device; residual2 + leak2 is
+        the residual of the untruncated system.  Returns a dict: leak2 [nCols, LN] float64, columns [nCols] (the caller's block column
+        indices), n_leak_blocks, n_leak_pairs, and units [nCols], the work units that each column's leak positions are cut into"""
+        n = int(self.plan_view()["nCols"])
+        leak2, cols = np.zeros((n, self.LN), np.float64), np.zeros(n, np.int32)
+        nb, npairs = C.c_uint64(0), C.c_uint64(0)
+        _check(lib.tfqmrgpuExt_truncationLeak(self.handle, self.plan, _ptr(leak2), _ptr(cols), C.byref(nb), C.byref(npairs)), "tfqmrgpuExt_truncationLeak")
+        units = np.zeros(n, np.uint32)
+        lib.tfqmrgpuExt_leakUnits(self.plan, _ptr(units))
+        return dict(leak2=leak2, columns=cols, n_leak_blocks=int(nb.value), n_leak_pairs=int(npairs.value), units=units)
+
+    def leak_counts(self):
+        """the pattern-only form of truncation_leak: (n_leak_blocks, n_leak_pairs).  Host analysis, no launch: needs create_plan and
+        buffer_size only"""
+        nb, npairs = C.c_uint64(0), C.c_uint64(0)
+        _check(lib.tfqmrgpuExt_truncationLeak(self.handle, self.plan, None, None, C.byref(nb), C.byref(npairs)), "tfqmrgpuExt_truncationLeak")
+        return int(nb.value), int(npairs.value)
 
     def bound_history(self):
         n = lib.tfqmrgpuExt_getBoundHistory(self.plan, None, 0)

@@ -242,10 +242,12 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_createPlan(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     try {   // for the block-Jacobi preconditioner (tfqmrgpu_ext.h section 7): where the diagonal blocks of A are, and the block column of every block
         p->diagOfRow.assign(size_t(mb), ~0u);
         p->colOfA.resize(size_t(nnzbA));
+        p->rowOfA.resize(size_t(nnzbA));   // (for the truncation leak, section 11)
         for (int r = 0; r < mb; ++r) {
             for (int32_t q = bsrRowPtrA[r] - indexOffset; q < bsrRowPtrA[r + 1] - indexOffset; ++q) {
                 auto const col = uint32_t(bsrColIndA[q] - indexOffset);
                 p->colOfA[q] = col;
+                p->rowOfA[q] = uint32_t(r);
                 if (col == uint32_t(r) && ~0u == p->diagOfRow[r]) p->diagOfRow[r] = uint32_t(q);
             }
         }
@@ -288,6 +290,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     p->opScratch.release();                // sized for the previous block shape
     p->residualScratch.release();          // ... and the previous chunks
+    p->leak = LeakListing{}; p->leakDev.release();   // ... and the work units of the previous block shape
     a_new_layout(*p);
     p->precision = prec;
     p->buffer = nullptr;
@@ -783,6 +786,75 @@ tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
     }
     if (worst) *worst = any ? std::sqrt(wmax) : std::nan("");
     return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// ---- truncation leak: what A X puts outside the pattern of X (tfqmrgpu_ext.h section 11) ----------------------------------------------
+tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double* leak2, int32_t* columns, uint64_t* nLeakBlocks, uint64_t* nLeakPairs)
+{
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
+    if (!leak2 && !columns && !nLeakBlocks && !nLeakPairs) return TFQMRGPU_STATUS_NO_INFO_PASSED;
+    if (leak2) {                                                    // everything else depends on the patterns alone: plan and bufferSize suffice
+        if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+        if (p->opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);    // a user-defined operator is the caller's to apply
+        if (!p->haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+        if (TFQMRGPU_PRECOND_NONE != p->precondInA && !kept_is_callers_a(*p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone
+    }
+    auto& l = p->leak;
+    if (!l.built) {                                                 // the host analysis, once per plan and block shape
+        try {
+            if (p->cscPtr.empty()) a_by_column(p->nRows, p->colOfA, p->cscPtr, p->cscBlock);
+            if (!leak_listing(l, p->nRows, p->nCols, p->nnzbA, p->rowOfA.data(), p->colOfA.data(), p->cscPtr.data(), p->cscBlock.data(),
+                              p->nnzbX, p->rowOfX.data(), p->col32.data(), p->u2i.data(), leak_unit_products(p->LM, p->LN))) {
+                l = LeakListing{};
+                return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+            }
+        } catch (std::bad_alloc const&) { l = LeakListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    }
+    size_t const LN = size_t(p->LN), nUnits = l.nUnits(), nCol = size_t(p->nCols) * LN;
+    std::vector<double> host;
+    if (leak2) {
+        hipStream_t const s = (hipStream_t)h->stream;
+        try { host.resize(nCol); } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+        // [pairs | posStart | unitFirst | colUnitPtr | records | column sums], every piece on a 256-byte boundary
+        size_t const oPairs = 0, oPos = oPairs + align256(l.pairs.size() * 4), oUnit = oPos + align256(l.posStart.size() * 4),
+                     oCol = oUnit + align256(l.unitFirst.size() * 4), oRec = oCol + align256(l.colUnitPtr.size() * 4),
+                     oSum = oRec + align256(nUnits * LN * sizeof(double)), total = oSum + align256(nCol * sizeof(double));
+        if (!p->leakDev) {                                          // the first call: upload the listing, one synchronise
+            if (auto const st = p->leakDev.reserve(std::max<size_t>(total, 256))) return st;
+            char* const dev = p->leakDev.as<char>();
+            tfqmrgpuStatus_t st = upload(dev + oPairs, l.pairs.data(), l.pairs.size() * 4, s);
+            if (!st) st = upload(dev + oPos, l.posStart.data(), l.posStart.size() * 4, s);
+            if (!st) st = upload(dev + oUnit, l.unitFirst.data(), l.unitFirst.size() * 4, s);
+            if (!st) st = upload(dev + oCol, l.colUnitPtr.data(), l.colUnitPtr.size() * 4, s);
+            if (!st && hipSuccess != hipStreamSynchronize(s)) st = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
+            if (st) { p->leakDev.release(); return st; }
+        }
+        char* const dev = p->leakDev.as<char>();
+        DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
+        // the caller's A: the buffer's, or the kept copy while the buffer holds A M^-1 ('m': its double part), pending patches included
+        void const* const A = (TFQMRGPU_PRECOND_NONE != p->precondInA) ? (void const*)kept_a(*p).a : d.A;
+        leak_launch(d, A, uint32_t(nUnits), (uint32_t const*)(dev + oPairs), (uint32_t const*)(dev + oPos), (uint32_t const*)(dev + oUnit),
+                    (uint32_t const*)(dev + oCol), (double*)(dev + oRec), (double*)(dev + oSum), s);
+        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        if (nCol) TFQ_HIP(hipMemcpyAsync(host.data(), dev + oSum, nCol * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        std::copy(host.begin(), host.end(), leak2);
+    }
+    if (columns) std::copy(p->original_bsrColIndX.begin(), p->original_bsrColIndX.end(), columns);
+    if (nLeakBlocks) *nLeakBlocks = uint64_t(l.nPositions());
+    if (nLeakPairs) *nLeakPairs = uint64_t(l.nProducts());
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// how the listing is cut: work units per compressed block column
+int64_t tfqmrgpuExt_leakUnits(tfqmrgpuBsrsvPlan_t plan, uint32_t* unitsPerColumn) {
+    auto p = asPlan(plan);
+    if (!p || !p->leak.built) return 0;
+    if (unitsPerColumn) for (uint32_t c = 0; c < p->nCols; ++c) unitsPerColumn[c] = p->leak.colUnitPtr[c + 1] - p->leak.colUnitPtr[c];
+    return int64_t(p->leak.nUnits());
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_commUniqueId(char id[128]) {

@@ -107,6 +107,30 @@ struct ChunkTable {
     std::vector<uint32_t> orderB;  // column batches (Plan::colBatch): the chunks of the batches' first columns, in the same kind of order
 };
 
+// tfqmrgpuExt_truncationLeak (tfqmrgpu_ext.h section 11): the block products A_ik X_kc that land on a block row i outside block column c
+// of X.  A leak position is one such (c, i); positions are sorted by (c, i), the products of a position by ascending k; a work unit is a
+// run of positions of ONE column (tfq_leak_host.cpp)
+struct LeakListing {
+    std::vector<uint32_t> pairs;          // [2*nProducts] (A block in the caller's order, X block in the internal order), as Plan::pairs_i
+    std::vector<uint32_t> posStart;       // [nPos+1] first product of each position
+    std::vector<uint32_t> posCol, posRow; // [nPos] compressed block column and block row of each position
+    std::vector<uint32_t> unitFirst;      // [nUnits+1] first position of each work unit
+    std::vector<uint32_t> colUnitPtr;     // [nCols+1] first work unit of each column
+    bool built = false;
+    size_t nPositions() const { return posCol.size(); }
+    size_t nProducts() const { return pairs.size() / 2; }
+    size_t nUnits() const { return unitFirst.empty() ? 0 : unitFirst.size() - 1; }
+};
+// the blocks of A grouped by block column (ascending block index inside a column), from the block column of every block
+void a_by_column(uint32_t nRows, std::vector<uint32_t> const& colOfA, std::vector<uint32_t>& cscPtr, std::vector<uint32_t>& cscBlock);
+// products per work unit at most (a position with more is a unit of its own), by the block shape
+uint32_t leak_unit_products(int LM, int LN);
+// the listing from plain index arrays (all zero based): row and column of every A block, A by block column (a_by_column), row and
+// compressed column of every X block in the caller's order, and its internal index.  false: more than 2^31 products
+bool leak_listing(LeakListing& out, uint32_t nRows, uint32_t nCols,
+    uint32_t nnzbA, uint32_t const* rowOfA, uint32_t const* colOfA, uint32_t const* cscPtr, uint32_t const* cscBlock,
+    uint32_t nnzbX, uint32_t const* rowOfX, uint32_t const* colOfX, uint32_t const* u2i, uint32_t maxProducts);
+
 struct Handle {
     void* stream = nullptr;               // hipStream_t
     // multi-GPU stopping test (tfqmrgpu_ext.h section 4)
@@ -212,6 +236,13 @@ struct Plan {
     // tfqmrgpuExt_residual (tfqmrgpu_ext.h section 10): library-owned scratch [nChunks][2][LN] + [nCols][2][LN] doubles, allocated at the
     // first call (sized by the block shape and the chunks: released by bufferSize)
     DevMem residualScratch;
+
+    // tfqmrgpuExt_truncationLeak (tfqmrgpu_ext.h section 11): the listing (built at the first call; its work units are cut by the block
+    // shape and its X indices are the internal ones: released by bufferSize) and its device copy [pairs | posStart | unitFirst |
+    // colUnitPtr | records [nUnits][LN] | column sums [nCols][LN]], uploaded at the first call that asks for leak2
+    std::vector<uint32_t> rowOfA;      // [nnzbA] block row of each block of A
+    LeakListing leak;
+    DevMem leakDev;
 
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;

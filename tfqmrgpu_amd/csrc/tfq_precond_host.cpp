@@ -110,14 +110,7 @@ tfqmrgpuStatus_t a_patched(Plan& p, int32_t const* blocks, int32_t nBlocks, bool
     p.mixedFloor = 0;
     if (!intoKept) return TFQMRGPU_STATUS_SUCCESS;
     try {
-        if (p.cscPtr.empty()) {                 // once per plan: the blocks of A grouped by block column
-            p.cscPtr.assign(size_t(p.nRows) + 1, 0u);
-            for (auto const c : p.colOfA) ++p.cscPtr[c + 1];
-            for (uint32_t c = 0; c < p.nRows; ++c) p.cscPtr[c + 1] += p.cscPtr[c];
-            p.cscBlock.resize(p.nnzbA);
-            std::vector<uint32_t> fill(p.cscPtr.begin(), p.cscPtr.end() - 1);
-            for (uint32_t q = 0; q < p.nnzbA; ++q) p.cscBlock[fill[p.colOfA[q]]++] = q;
-        }
+        if (p.cscPtr.empty()) a_by_column(p.nRows, p.colOfA, p.cscPtr, p.cscBlock);   // once per plan: the blocks of A grouped by block column
         p.dirtyRow.resize(p.nRows, uint8_t(0)); p.dirtyCol.resize(p.nRows, uint8_t(0));
     } catch (std::bad_alloc const&) { p.cscPtr.clear(); return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     for (int32_t k = 0; k < nBlocks; ++k) {

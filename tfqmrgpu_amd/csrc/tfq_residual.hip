@@ -6,7 +6,7 @@
 //                            summed per column of the block; two [LN] records per chunk
 //   k_residual_col<LN>       one work group per block column: the records of its chunks added in chunk order
 // No atomics, and every sum has one fixed order: two calls on the same data give the same bits.
-#include "tfq_spmm.hpp"
+#include "tfq_residual.hpp"
 
 namespace tfq {
 
@@ -19,19 +19,7 @@ struct ResidualArgs {
     double* col;                            // [nCols][2][LN]
 };
 
-// plane_offset with the group size as a constant in each branch (the order is uniform over the launch: a scalar branch, no division)
-__device__ __forceinline__ int res_offset(int ilv, int r, int s, int nC) {
-    switch (ilv) {
-        case 2:  return plane_offset(2, r, s, nC);
-        case 4:  return plane_offset(4, r, s, nC);
-        default: return plane_offset(0, r, s, nC);
-    }
-}
-
-// One fixed pattern of fused multiply-adds (the rule of tfq_device.hpp: fma_): y += a x (complex), r = y - b, sums of squares
-__device__ __forceinline__ void res_cmac(double& yr, double& yi, double ar, double ai, double xr, double xi) {
-    yr = fma_(-ai, xi, fma_(ar, xr, yr)); yi = fma_(ai, xr, fma_(ar, xi, yi));
-}
+// r = y - b, sums of squares (res_offset, res_cmac: tfq_residual.hpp)
 __device__ __forceinline__ void res_square(double& r2, double& b2, double yr, double yi, double br, double bi) {
     double const rr = fma_(-1., br, yr), ri = fma_(-1., bi, yi);
     epi_nrm(r2, rr, ri); epi_nrm(b2, br, bi);

@@ -37,4 +37,10 @@ void epilogue_launch(int epi, DevPlan const& d, void const* Yext, uint32_t const
 // rec [nChunks][2][LN] and col [nCols][2][LN] (the result) are the caller's scratch; nothing else is written
 void residual_launch(DevPlan const& d, void const* A, double* rec, double* col, hipStream_t s);
 
+// |.|^2 per (block column, right-hand side) of the block products of the leak listing (tfq_plan.hpp: LeakListing; all four lists in device
+// memory) of the plan's X and the operator A, as above (tfq_leak.hip; tfqmrgpuExt_truncationLeak).
+// rec [nUnits][LN] and col [nCols][LN] (the result) are the caller's scratch; nothing else is written
+void leak_launch(DevPlan const& d, void const* A, uint32_t nUnits, uint32_t const* pairs, uint32_t const* posStart,
+    uint32_t const* unitFirst, uint32_t const* colUnitPtr, double* rec, double* col, hipStream_t s);
+
 } // namespace tfq
