@@ -426,6 +426,75 @@ tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsr
  * [nCols], may be NULL); returns the number of work units of the plan, 0 while the listing has not been built. */
 int64_t tfqmrgpuExt_leakUnits(tfqmrgpuBsrsvPlan_t plan, uint32_t *unitsPerColumn);
 
+/* ---- (12) leak map: the truncation leak per position, and the pattern of X grown where it leaks ------------------------------------- */
+/* Section 11 tells per block column how much of A X the truncation cut off.  A caller who sees a large leak2[c] still cannot tell WHICH
+ * block rows to add to column c; all that is left is a larger geometric radius.  leakMap gives the leak of every single leak position
+ * -- a (block row i, block column c) outside the pattern of X that receives a product --, and growPattern turns a chosen set of positions
+ * into the BSR pattern of X for the next createPlan: solve, residual, truncationLeak, leakMap, growPattern, createPlan.  The pattern
+ * grows where the operator carries weight out of it, not isotropically.
+ *
+ * rows[p]          = the block row of leak position p, 0-based whatever the plan's indexOffset, a HOST array [capacity], may be NULL;
+ * cols[p]          = its COMPRESSED block column, as c in sections 10 and 11 (columns[] there gives the caller's index), a HOST array
+ *                    [capacity], may be NULL;
+ * pos2[p*LN + j]   = | sum over k with (i, k) in the pattern of A and (k, c) in the pattern of X of  A_ik X_kc  (:, j) |^2  for
+ *                    (i, c) = (rows[p], cols[p]), a HOST array [capacity][LN] of double, may be NULL;
+ * *nLeakBlocks     = the number of positions, nLeakBlocks of section 11, may be NULL.  All four NULL: TFQMRGPU_STATUS_NO_INFO_PASSED.
+ *                    Only the first *nLeakBlocks entries of the arrays are written.
+ *
+ * The order of the positions is part of the interface: ascending compressed block column, then ascending block row.  Position p of
+ *   leakMap is position p of growPattern.  The positions of block column c are consecutive; added up per right-hand side they are
+ *   leak2[c*LN + j] of section 11, up to the rounding of a sum in another order.
+ * Operands and arithmetic are section 11's: the caller's A -- the buffer's, or the kept copy (section 9) while the buffer holds A M^-1,
+ *   patches of setBlocks('A') that no set-up has seen yet included --; X what getMatrix('X') would return at that moment; every product
+ *   and every sum in double whatever the plan's precision ('c': float data converted on load, 'm': the plan's double copies), always
+ *   four real products per complex one.
+ * Deterministic: the [LN] record of a position is written by one wave (block shapes that are multiples of 16: the wave forms the whole
+ *   block of A X of the position and adds its rows in one fixed order) or by one work group (4- and 8-row shapes: the rows are added in
+ *   row order); no atomics, nothing is added across positions.  Two calls on the same data give the same bits.
+ * Non-destructive: the call writes nothing into the caller's buffer; a following solve, residual or truncationLeak is the one it would
+ *   have been.  bufferSize and the buffer layout do not change.
+ * Memory: the listing of the positions is section 11's, built on the host at the first call of either section and uploaded ONCE, by the
+ *   first call of either that needs it on the device.  The records, [nLeakBlocks][LN] doubles, are device memory that the library owns,
+ *   allocated by the first call that asks for pos2, released by destroyPlan and by bufferSize.  A plan that never makes the call runs
+ *   the launches it ran before and allocates nothing.
+ * Stream: asynchronous on the handle's stream up to the copy-out ([nLeakBlocks][LN] doubles), then one synchronise (one more at the
+ *   upload of the listing).  Do not call it during a solve.
+ * All checks come before the first device call, those of section 11 in its order: plan / handle pointers; no bufferSize yet:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR; all four outputs NULL: TFQMRGPU_STATUS_NO_INFO_PASSED.  rows, cols and *nLeakBlocks depend on the patterns
+ *   alone: with pos2 == NULL the call does the host analysis, launches nothing and needs the plan and bufferSize only.  With pos2: no
+ *   buffer: TFQMRGPU_POINTER_INVALID; a plan with a user-defined operator: TFQMRGPU_NO_IMPLEMENTATION; A never set whole on this buffer:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A'; the A in the buffer has been scaled by the preconditioner and the plan keeps no
+ *   copy: TFQMRGPU_NO_IMPLEMENTATION.  Then, with any of the three arrays given, capacity < the number of positions:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'X'; *nLeakBlocks (if given) HAS been filled in -- the room to come back with --
+ *   and nothing else.  After any other error nothing has been written, neither device nor host arrays.
+ * Several ranks (section 4): local to the rank's own block columns, as section 11. */
+tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    uint64_t capacity,            /* positions the three arrays have room for */
+    int32_t *rows,                /* HOST [capacity]      block row of each leak position, 0-based, may be NULL */
+    int32_t *cols,                /* HOST [capacity]      COMPRESSED block column of each position, may be NULL */
+    double  *pos2,                /* HOST [capacity][LN]  |(A X)(i,c)(:, j)|^2 per position and right-hand side, may be NULL */
+    uint64_t *nLeakBlocks);       /* may be NULL; all four NULL: TFQMRGPU_STATUS_NO_INFO_PASSED */
+
+/* The pattern of X with the leak positions take[0 .. nTake) added (indices into the order of leakMap; take == NULL: every position,
+ * nTake is ignored), in the form createPlan reads: host only, it needs the plan and bufferSize.
+ * Every block row keeps its old blocks in their old order; the added blocks of a row follow them, ascending by the caller's block column
+ *   index.  oldBlock maps the values over: new block n holds old block oldBlock[n] of the caller's order, or is new (-1: zero, or a guess).
+ *   nTake == 0 with a non-NULL list reproduces the old pattern (oldBlock = 0, 1, 2, ...).
+ * The arrays are malloc'ed by the library (tfqmrgpuExt_freeGrownPattern releases them and zeroes the struct), as in section 4.
+ * Cost: O(nnzbX + nTake + mb + nCols) behind the listing, which is built at the first call of this section or of section 11; nothing
+ *   is searched.
+ * plan or grown NULL: TFQMRGPU_POINTER_INVALID; no bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; an index >= nLeakBlocks or an index named
+ *   twice: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'X'.  After any error *grown is zeroed (NULL arrays). */
+typedef struct {
+    int32_t  mb, nnzbX;
+    int32_t *rowPtrX, *colIndX;   /* [mb+1], [nnzbX], with the plan's indexOffset and the CALLER'S block column indices */
+    int32_t *oldBlock;            /* [nnzbX] position of the block in the old plan's caller order, -1 for an added block */
+} tfqmrgpuGrownPattern_t;
+tfqmrgpuStatus_t tfqmrgpuExt_growPattern(tfqmrgpuBsrsvPlan_t plan,
+    uint64_t nTake, uint64_t const *take /* HOST, leak-map position indices; NULL: all positions (nTake ignored) */,
+    tfqmrgpuGrownPattern_t *grown);
+void tfqmrgpuExt_freeGrownPattern(tfqmrgpuGrownPattern_t *grown);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_getRefinementHistory", "tfqmrgpuExt_setThreeProductMultiply",
     "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner", "tfqmrgpuExt_setBlocks", "tfqmrgpuExt_getBlocks",
     "tfqmrgpuExt_keepOperator", "tfqmrgpuExt_residual", "tfqmrgpuExt_truncationLeak", "tfqmrgpuExt_leakUnits",
+    "tfqmrgpuExt_leakMap", "tfqmrgpuExt_growPattern", "tfqmrgpuExt_freeGrownPattern",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -68,7 +69,12 @@ class Shard(C.Structure):
                 ("firstCol", C.c_int32), ("nCols", C.c_int32)]
 
 
-REDUCE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_double), C.c_int)
+class GrownPattern(C.Structure):
+    _fields_ = [("mb", C.c_int32), ("nnzbX", C.c_int32), ("rowPtrX", C.POINTER(C.c_int32)), ("colIndX", C.POINTER(C.c_int32)),
+                ("oldBlock", C.POINTER(C.c_int32))]
+
+
+REDUCE_CB = C.CFUNCTYPE(None,C.c_void_p, C.POINTER(C.c_double), C.c_int)
 # tfqmrgpuOperator_t: (ctx, Y_d, X_d, colindx_d, nnzbX, nCols, lm, ln, precision, stream, *flops) -> status
 OPERATOR_CB = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                           C.c_int, C.c_int, C.c_char, C.c_void_p, C.POINTER(C.c_double))
@@ -147,6 +153,10 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_truncationLeak.argtypes = [P, P, P, P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.tfqmrgpuExt_leakUnits.argtypes = [P, P]
     lib.tfqmrgpuExt_leakUnits.restype = C.c_int64
+    lib.tfqmrgpuExt_leakMap.argtypes = [P, P, C.c_uint64, P, P, P, C.POINTER(C.c_uint64)]
+    lib.tfqmrgpuExt_growPattern.argtypes = [P, C.c_uint64, P, C.POINTER(GrownPattern)]
+    lib.tfqmrgpuExt_freeGrownPattern.argtypes = [C.POINTER(GrownPattern)]
+    lib.tfqmrgpuExt_freeGrownPattern.restype = None
     return lib
 
 
@@ -450,6 +460,47 @@ class Solver:
         nb, npairs = C.c_uint64(0), C.c_uint64(0)
         _check(lib.tfqmrgpuExt_truncationLeak(self.handle, self.plan, None, None, C.byref(nb), C.byref(npairs)), "tfqmrgpuExt_truncationLeak")
         return int(nb.value), int(npairs.value)
+
+    def leak_map(self, values=True):
+        """tfqmrgpu_ext.h section 12: the truncation leak per leak position, ordered by (compressed block column, block row).  Returns a
+        dict: rows, cols [n_leak_blocks] int32 (block row, 0-based; COMPRESSED block column), pos2 [n_leak_blocks, LN] float64 -- None with
+        values=False, the pattern-only form: host analysis, no launch, needs create_plan and buffer_size only -- and n_leak_blocks"""
+        n = self.leak_counts()[0]
+        rows, cols = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        pos2 = np.zeros((n, self.LN), np.float64) if values else None
+        nb = C.c_uint64(0)
+        # (an array without entries still has an address: _ptr would make it NULL, which means "not asked for")
+        addr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)      # noqa: E731
+        _check(lib.tfqmrgpuExt_leakMap(self.handle, self.plan, n, addr(rows), addr(cols), addr(pos2), C.byref(nb)), "tfqmrgpuExt_leakMap")
+        return dict(rows=rows, cols=cols, pos2=pos2, n_leak_blocks=int(nb.value))
+
+    def grow_pattern(self, take=None):
+        """tfqmrgpu_ext.h section 12: the BSR pattern of X with the leak positions `take` added (indices into the order of leak_map;
+        None: all of them, an empty list: none).  Returns (rowPtrX, colIndX, oldBlock) as int32 arrays: the form create_plan reads, and
+        for every new block the old block whose values it takes over, -1 for an added one.  Host only"""
+        g = GrownPattern()
+        if take is None:
+            st = lib.tfqmrgpuExt_growPattern(self.plan, 0, None, C.byref(g))
+        else:
+            idx = np.ascontiguousarray(take, dtype=np.uint64).reshape(-1)
+            st = lib.tfqmrgpuExt_growPattern(self.plan, len(idx), C.c_void_p(idx.ctypes.data), C.byref(g))
+        _check(st, "tfqmrgpuExt_growPattern")
+        try:
+            def arr(p, n):
+                return np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, np.int32)
+            return arr(g.rowPtrX, g.mb + 1), arr(g.colIndX, g.nnzbX), arr(g.oldBlock, g.nnzbX)
+        finally:
+            lib.tfqmrgpuExt_freeGrownPattern(C.byref(g))
+
+    def grow_problem(self, pr, take=None):
+        """the Problem with the grown pattern of X (grow_pattern) and the same A and B as `pr`, the problem of this plan; where `pr`
+        carries values of X they move to their new places, the added blocks are zero"""
+        rowPtrX, colIndX, old = self.grow_pattern(take)
+        X = None
+        if pr.X is not None:
+            X = np.zeros((len(colIndX), pr.LM, pr.LN), dtype=np.complex128)
+            X[old >= 0] = pr.X[old[old >= 0]]
+        return Problem(pr.rowPtrA, pr.colIndA, pr.A, rowPtrX, colIndX, pr.rowPtrB, pr.colIndB, pr.B, X, pr.tolerance, pr.index_offset)
 
     def bound_history(self):
         n = lib.tfqmrgpuExt_getBoundHistory(self.plan, None, 0)

@@ -290,7 +290,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     p->opScratch.release();                // sized for the previous block shape
     p->residualScratch.release();          // ... and the previous chunks
-    p->leak = LeakListing{}; p->leakDev.release();   // ... and the work units of the previous block shape
+    p->leak = LeakListing{}; p->leakDev.release(); p->leakMapRec.release();   // ... and the work units of the previous block shape
     a_new_layout(*p);
     p->precision = prec;
     p->buffer = nullptr;
@@ -788,7 +788,48 @@ tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
-// ---- truncation leak: what A X puts outside the pattern of X (tfqmrgpu_ext.h section 11) ----------------------------------------------
+// ---- truncation leak: what A X puts outside the pattern of X (tfqmrgpu_ext.h sections 11 and 12) --------------------------------------
+// the host analysis, once per plan and block shape
+static tfqmrgpuStatus_t leak_host(Plan& p) {
+    auto& l = p.leak;
+    if (l.built) return TFQMRGPU_STATUS_SUCCESS;
+    try {
+        if (p.cscPtr.empty()) a_by_column(p.nRows, p.colOfA, p.cscPtr, p.cscBlock);
+        if (!leak_listing(l, p.nRows, p.nCols, p.nnzbA, p.rowOfA.data(), p.colOfA.data(), p.cscPtr.data(), p.cscBlock.data(),
+                          p.nnzbX, p.rowOfX.data(), p.col32.data(), p.u2i.data(), leak_unit_products(p.LM, p.LN))) {
+            l = LeakListing{};
+            return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+        }
+    } catch (std::bad_alloc const&) { l = LeakListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// the listing on the device, Plan::leakDev: [pairs | posStart | unitFirst | colUnitPtr | records | column sums], every piece on a 256-byte
+// boundary.  ONE copy for truncationLeak and leakMap: whichever comes first uploads it, with one synchronise
+struct LeakDev { size_t oPairs, oPos, oUnit, oCol, oRec, oSum, total; };
+static LeakDev leak_dev_layout(Plan const& p) {
+    auto const& l = p.leak;
+    LeakDev o{};
+    o.oPairs = 0; o.oPos = o.oPairs + align256(l.pairs.size() * 4); o.oUnit = o.oPos + align256(l.posStart.size() * 4);
+    o.oCol = o.oUnit + align256(l.unitFirst.size() * 4); o.oRec = o.oCol + align256(l.colUnitPtr.size() * 4);
+    o.oSum = o.oRec + align256(l.nUnits() * size_t(p.LN) * sizeof(double));
+    o.total = o.oSum + align256(size_t(p.nCols) * size_t(p.LN) * sizeof(double));
+    return o;
+}
+static tfqmrgpuStatus_t leak_device(Plan& p, LeakDev const& o, hipStream_t s) {
+    if (p.leakDev) return TFQMRGPU_STATUS_SUCCESS;
+    auto const& l = p.leak;
+    if (auto const st = p.leakDev.reserve(std::max<size_t>(o.total, 256))) return st;
+    char* const dev = p.leakDev.as<char>();
+    tfqmrgpuStatus_t st = upload(dev + o.oPairs, l.pairs.data(), l.pairs.size() * 4, s);
+    if (!st) st = upload(dev + o.oPos, l.posStart.data(), l.posStart.size() * 4, s);
+    if (!st) st = upload(dev + o.oUnit, l.unitFirst.data(), l.unitFirst.size() * 4, s);
+    if (!st) st = upload(dev + o.oCol, l.colUnitPtr.data(), l.colUnitPtr.size() * 4, s);
+    if (!st && hipSuccess != hipStreamSynchronize(s)) st = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
+    if (st) p.leakDev.release();
+    return st;
+}
+
 tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
     double* leak2, int32_t* columns, uint64_t* nLeakBlocks, uint64_t* nLeakPairs)
 {
@@ -802,44 +843,23 @@ tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsr
         if (!p->haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
         if (TFQMRGPU_PRECOND_NONE != p->precondInA && !kept_is_callers_a(*p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone
     }
+    if (auto const st = leak_host(*p)) return st;
     auto& l = p->leak;
-    if (!l.built) {                                                 // the host analysis, once per plan and block shape
-        try {
-            if (p->cscPtr.empty()) a_by_column(p->nRows, p->colOfA, p->cscPtr, p->cscBlock);
-            if (!leak_listing(l, p->nRows, p->nCols, p->nnzbA, p->rowOfA.data(), p->colOfA.data(), p->cscPtr.data(), p->cscBlock.data(),
-                              p->nnzbX, p->rowOfX.data(), p->col32.data(), p->u2i.data(), leak_unit_products(p->LM, p->LN))) {
-                l = LeakListing{};
-                return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
-            }
-        } catch (std::bad_alloc const&) { l = LeakListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    }
     size_t const LN = size_t(p->LN), nUnits = l.nUnits(), nCol = size_t(p->nCols) * LN;
     std::vector<double> host;
     if (leak2) {
         hipStream_t const s = (hipStream_t)h->stream;
         try { host.resize(nCol); } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-        // [pairs | posStart | unitFirst | colUnitPtr | records | column sums], every piece on a 256-byte boundary
-        size_t const oPairs = 0, oPos = oPairs + align256(l.pairs.size() * 4), oUnit = oPos + align256(l.posStart.size() * 4),
-                     oCol = oUnit + align256(l.unitFirst.size() * 4), oRec = oCol + align256(l.colUnitPtr.size() * 4),
-                     oSum = oRec + align256(nUnits * LN * sizeof(double)), total = oSum + align256(nCol * sizeof(double));
-        if (!p->leakDev) {                                          // the first call: upload the listing, one synchronise
-            if (auto const st = p->leakDev.reserve(std::max<size_t>(total, 256))) return st;
-            char* const dev = p->leakDev.as<char>();
-            tfqmrgpuStatus_t st = upload(dev + oPairs, l.pairs.data(), l.pairs.size() * 4, s);
-            if (!st) st = upload(dev + oPos, l.posStart.data(), l.posStart.size() * 4, s);
-            if (!st) st = upload(dev + oUnit, l.unitFirst.data(), l.unitFirst.size() * 4, s);
-            if (!st) st = upload(dev + oCol, l.colUnitPtr.data(), l.colUnitPtr.size() * 4, s);
-            if (!st && hipSuccess != hipStreamSynchronize(s)) st = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
-            if (st) { p->leakDev.release(); return st; }
-        }
+        auto const o = leak_dev_layout(*p);
+        if (auto const st = leak_device(*p, o, s)) return st;       // the first call: upload the listing, one synchronise
         char* const dev = p->leakDev.as<char>();
         DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
         // the caller's A: the buffer's, or the kept copy while the buffer holds A M^-1 ('m': its double part), pending patches included
         void const* const A = (TFQMRGPU_PRECOND_NONE != p->precondInA) ? (void const*)kept_a(*p).a : d.A;
-        leak_launch(d, A, uint32_t(nUnits), (uint32_t const*)(dev + oPairs), (uint32_t const*)(dev + oPos), (uint32_t const*)(dev + oUnit),
-                    (uint32_t const*)(dev + oCol), (double*)(dev + oRec), (double*)(dev + oSum), s);
+        leak_launch(d, A, uint32_t(nUnits), (uint32_t const*)(dev + o.oPairs), (uint32_t const*)(dev + o.oPos), (uint32_t const*)(dev + o.oUnit),
+                    (uint32_t const*)(dev + o.oCol), (double*)(dev + o.oRec), (double*)(dev + o.oSum), s);
         TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        if (nCol) TFQ_HIP(hipMemcpyAsync(host.data(), dev + oSum, nCol * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        if (nCol) TFQ_HIP(hipMemcpyAsync(host.data(), dev + o.oSum, nCol * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
         TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
         std::copy(host.begin(), host.end(), leak2);
     }
@@ -847,6 +867,83 @@ tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsr
     if (nLeakBlocks) *nLeakBlocks = uint64_t(l.nPositions());
     if (nLeakPairs) *nLeakPairs = uint64_t(l.nProducts());
     return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// ---- leak map: the leak per position, and the pattern of X grown by chosen positions (tfqmrgpu_ext.h section 12) ------------------------
+tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    uint64_t capacity, int32_t* rows, int32_t* cols, double* pos2, uint64_t* nLeakBlocks)
+{
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
+    if (!rows && !cols && !pos2 && !nLeakBlocks) return TFQMRGPU_STATUS_NO_INFO_PASSED;
+    if (pos2) {                                                     // everything else depends on the patterns alone, as in section 11
+        if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+        if (p->opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+        if (!p->haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+        if (TFQMRGPU_PRECOND_NONE != p->precondInA && !kept_is_callers_a(*p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone
+    }
+    if (auto const st = leak_host(*p)) return st;
+    auto const& l = p->leak;
+    size_t const LN = size_t(p->LN), nPos = l.nPositions();
+    if ((rows || cols || pos2) && capacity < uint64_t(nPos)) {      // the caller learns how much room the arrays need, and nothing else
+        if (nLeakBlocks) *nLeakBlocks = uint64_t(nPos);
+        return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');
+    }
+    std::vector<double> host;
+    if (pos2 && nPos) {
+        hipStream_t const s = (hipStream_t)h->stream;
+        try { host.resize(nPos * LN); } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+        auto const o = leak_dev_layout(*p);
+        if (auto const st = leak_device(*p, o, s)) return st;       // the listing of section 11, uploaded once for both calls
+        if (auto const st = p->leakMapRec.reserve(std::max<size_t>(nPos * LN * sizeof(double), 256))) return st;
+        char* const dev = p->leakDev.as<char>();
+        DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
+        void const* const A = (TFQMRGPU_PRECOND_NONE != p->precondInA) ? (void const*)kept_a(*p).a : d.A;   // the caller's A, as in section 11
+        leak_map_launch(d, A, uint32_t(nPos), (uint32_t const*)(dev + o.oPairs), (uint32_t const*)(dev + o.oPos), p->leakMapRec.as<double>(), s);
+        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipMemcpyAsync(host.data(), p->leakMapRec.ptr, nPos * LN * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        std::copy(host.begin(), host.end(), pos2);
+    }
+    if (rows) for (size_t n = 0; n < nPos; ++n) rows[n] = int32_t(l.posRow[n]);
+    if (cols) for (size_t n = 0; n < nPos; ++n) cols[n] = int32_t(l.posCol[n]);
+    if (nLeakBlocks) *nLeakBlocks = uint64_t(nPos);
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_growPattern(tfqmrgpuBsrsvPlan_t plan, uint64_t nTake, uint64_t const* take, tfqmrgpuGrownPattern_t* grown) {
+    auto p = asPlan(plan);
+    if (!p || !grown) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    *grown = tfqmrgpuGrownPattern_t{};
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
+    if (auto const st = leak_host(*p)) return st;
+    auto const& l = p->leak;
+    GrownPattern g;
+    try {
+        int const bad = grow_pattern(g, p->nRows, p->nCols, p->nnzbX, p->rowOfX.data(), p->col32.data(), p->original_bsrColIndX.data(),
+                                     p->indexOffset, l.nPositions(), l.posRow.data(), l.posCol.data(), nTake, take);
+        if (1 == bad) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');   // an index >= nLeakBlocks, or one named twice
+        if (bad) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);        // the index arrays are 32 bit
+    } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    auto dup = [](std::vector<int32_t> const& v) {
+        auto q = (int32_t*)std::malloc(std::max<size_t>(1, v.size()) * sizeof(int32_t));
+        if (q) std::copy(v.begin(), v.end(), q);
+        return q;
+    };
+    grown->mb = int32_t(p->nRows); grown->nnzbX = int32_t(g.colInd.size());
+    grown->rowPtrX = dup(g.rowPtr); grown->colIndX = dup(g.colInd); grown->oldBlock = dup(g.oldBlock);
+    if (!grown->rowPtrX || !grown->colIndX || !grown->oldBlock) {
+        tfqmrgpuExt_freeGrownPattern(grown);
+        return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
+    }
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+void tfqmrgpuExt_freeGrownPattern(tfqmrgpuGrownPattern_t* grown) {
+    if (!grown) return;
+    std::free(grown->rowPtrX); std::free(grown->colIndX); std::free(grown->oldBlock);
+    *grown = tfqmrgpuGrownPattern_t{};
 }
 
 // how the listing is cut: work units per compressed block column

@@ -1,5 +1,6 @@
 // Truncation leak (tfqmrgpu_ext.h section 11), host side: which block products A_ik X_kc land on a block row i that block column c of X
-// does NOT hold.  Plain C++ on plain index arrays -- no Plan, no device: scripts/leak_listing_check.cpp runs it under the sanitizers.
+// does NOT hold; and the pattern of X grown by chosen ones of those positions (section 12, grow_pattern at the end of the file).  Plain C++ on
+// plain index arrays -- no Plan, no device: scripts/leak_listing_check.cpp and scripts/grow_pattern_check.cpp run it under the sanitizers.
 //
 // One pass over the block rows i of A.  Row i of X is stamped into a [nCols] array, so that "(i, c) is in the pattern of X" is one
 // comparison; for every A block (i, k) of the row, in ascending k, every X block (k, c) of row k whose column is not stamped is a product
@@ -108,6 +109,54 @@ bool leak_listing(LeakListing& out, uint32_t nRows, uint32_t nCols,
     out.unitFirst.push_back(nPos);
     out.built = true;
     return true;
+}
+
+// The grown pattern (tfqmrgpu_ext.h section 12).  The taken positions are dealt to their block rows in ascending compressed column -- the
+// order of the caller's column indices, createPlan numbers the columns that way --: all positions are in that order already, a list is
+// brought into it by one stable counting sort by column.  A position named twice arrives twice in a row at its block row: one comparison
+// with the column that row took last.  Cost: O(nnzbX + nTake + nRows + nCols), nothing is searched.
+int grow_pattern(GrownPattern& out, uint32_t nRows, uint32_t nCols, uint32_t nnzbX, uint32_t const* rowOfX, uint32_t const* colOfX,
+    int32_t const* callersCol, int indexOffset, size_t nPos, uint32_t const* posRow, uint32_t const* posCol, uint64_t nTake, uint64_t const* take)
+{
+    out = GrownPattern{};
+    size_t const nAdd = take ? size_t(nTake) : nPos;
+    if (take && nTake > nPos) return 1;                              // more indices than positions: one is out of range or named twice
+    if (size_t(nnzbX) + nAdd >= size_t(0x7fffffff)) return 2;        // (room for an index offset of 1)
+    std::vector<uint32_t> add(nAdd);                                 // the taken positions, ascending by column
+    if (take) {
+        std::vector<size_t> fill(size_t(nCols) + 1, 0);
+        for (size_t n = 0; n < nAdd; ++n) {
+            if (take[n] >= nPos) return 1;
+            ++fill[posCol[take[n]] + 1];
+        }
+        for (uint32_t c = 0; c < nCols; ++c) fill[c + 1] += fill[c];
+        for (size_t n = 0; n < nAdd; ++n) add[fill[posCol[take[n]]]++] = uint32_t(take[n]);
+    } else {
+        for (size_t n = 0; n < nAdd; ++n) add[n] = uint32_t(n);
+    }
+    GrownPattern g;
+    g.rowPtr.assign(size_t(nRows) + 1, 0);
+    for (uint32_t x = 0; x < nnzbX; ++x) ++g.rowPtr[rowOfX[x] + 1];
+    for (auto const p : add) ++g.rowPtr[posRow[p] + 1];
+    for (uint32_t r = 0; r < nRows; ++r) g.rowPtr[r + 1] += g.rowPtr[r];
+    size_t const nnzb = size_t(nnzbX) + nAdd;
+    g.colInd.resize(nnzb); g.oldBlock.resize(nnzb);
+    std::vector<int32_t> fill(g.rowPtr.begin(), g.rowPtr.end() - 1);
+    for (uint32_t x = 0; x < nnzbX; ++x) {                           // the old blocks first, in the caller's order
+        auto const at = fill[rowOfX[x]]++;
+        g.colInd[at] = callersCol[colOfX[x]]; g.oldBlock[at] = int32_t(x);
+    }
+    std::vector<uint32_t> lastCol(nRows, ~0u);                       // the column of the position that each block row took last
+    for (auto const p : add) {
+        auto const r = posRow[p], c = posCol[p];
+        if (lastCol[r] == c) return 1;                               // named twice
+        lastCol[r] = c;
+        auto const at = fill[r]++;
+        g.colInd[at] = callersCol[c]; g.oldBlock[at] = -1;
+    }
+    for (auto& v : g.rowPtr) v += indexOffset;
+    out = std::move(g);
+    return 0;
 }
 
 } // namespace tfq

@@ -131,6 +131,19 @@ bool leak_listing(LeakListing& out, uint32_t nRows, uint32_t nCols,
     uint32_t nnzbA, uint32_t const* rowOfA, uint32_t const* colOfA, uint32_t const* cscPtr, uint32_t const* cscBlock,
     uint32_t nnzbX, uint32_t const* rowOfX, uint32_t const* colOfX, uint32_t const* u2i, uint32_t maxProducts);
 
+// tfqmrgpuExt_growPattern (tfqmrgpu_ext.h section 12): the BSR pattern of X with chosen leak positions added, as the caller writes it
+struct GrownPattern {
+    std::vector<int32_t> rowPtr;          // [nRows+1] with the index offset
+    std::vector<int32_t> colInd;          // [nnzb] the caller's block column indices
+    std::vector<int32_t> oldBlock;        // [nnzb] the block of the old pattern (caller's order), -1: added
+};
+// The old pattern from plain index arrays -- row and compressed column of every X block in the caller's order, the caller's index of
+// every compressed column (ascending) -- plus the positions take[0 .. nTake) of posRow / posCol (take == nullptr: all nPos, nTake ignored).
+// Every block row keeps its old blocks in their order; the added ones follow, ascending by column.  0: done; 1: an index >= nPos or an
+// index named twice; 2: more than 2^31 blocks.  `out` is empty unless 0 is returned
+int grow_pattern(GrownPattern& out, uint32_t nRows, uint32_t nCols, uint32_t nnzbX, uint32_t const* rowOfX, uint32_t const* colOfX,
+    int32_t const* callersCol, int indexOffset, size_t nPos, uint32_t const* posRow, uint32_t const* posCol, uint64_t nTake, uint64_t const* take);
+
 struct Handle {
     void* stream = nullptr;               // hipStream_t
     // multi-GPU stopping test (tfqmrgpu_ext.h section 4)
@@ -243,6 +256,9 @@ struct Plan {
     std::vector<uint32_t> rowOfA;      // [nnzbA] block row of each block of A
     LeakListing leak;
     DevMem leakDev;
+    // tfqmrgpuExt_leakMap (tfqmrgpu_ext.h section 12): one [LN] record of doubles per leak position, allocated at the first call that asks
+    // for pos2; the listing on the device is leakDev's (sized by the block shape and the positions: released by bufferSize)
+    DevMem leakMapRec;
 
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;

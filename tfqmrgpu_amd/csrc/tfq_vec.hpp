@@ -43,4 +43,8 @@ void residual_launch(DevPlan const& d, void const* A, double* rec, double* col, 
 void leak_launch(DevPlan const& d, void const* A, uint32_t nUnits, uint32_t const* pairs, uint32_t const* posStart,
     uint32_t const* unitFirst, uint32_t const* colUnitPtr, double* rec, double* col, hipStream_t s);
 
+// the same products per leak POSITION: |.|^2 per (position, right-hand side), one [LN] record per position of the listing into
+// rec [nPos][LN], the caller's scratch; nothing else is written (tfq_leak_map.hip; tfqmrgpuExt_leakMap)
+void leak_map_launch(DevPlan const& d, void const* A, uint32_t nPos, uint32_t const* pairs, uint32_t const* posStart, double* rec, hipStream_t s);
+
 } // namespace tfq
