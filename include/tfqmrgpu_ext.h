@@ -495,6 +495,77 @@ tfqmrgpuStatus_t tfqmrgpuExt_growPattern(tfqmrgpuBsrsvPlan_t plan,
     tfqmrgpuGrownPattern_t *grown);
 void tfqmrgpuExt_freeGrownPattern(tfqmrgpuGrownPattern_t *grown);
 
+/* ---- (13) drop cost: what each block of X carries, and the pattern of X without chosen blocks ----------------------------------------- */
+/* Sections 10 to 12 let a pattern grow where the operator carries weight out of it; nothing there tells which blocks the pattern holds
+ * for nothing.  The pattern is the cost of everything: the buffer, every vector kernel and every block product scale with nnzbX.
+ * dropCost gives per block of X how much of the residual rests on it, and shrinkPattern turns a list of blocks to drop into the BSR
+ * pattern of X for the next createPlan: solve, residual, truncationLeak, leakMap, growPattern, dropCost, shrinkPattern, createPlan.
+ *
+ * For block n of X at (block row k, compressed block column c) and right-hand side j:
+ * cost2[n*LN + j]   = sum over the block rows i with (i, k) in the pattern of A and (i, c) in the pattern of X of | A_ik X_kc (:, j) |^2,
+ *                     a HOST array [nnzbX][LN] of double, may be NULL;
+ * weight2[n*LN + j] = | X_kc (:, j) |^2, a HOST array [nnzbX][LN] of double, may be NULL;
+ * *nProducts        = the number of block products, tfqmrgpuPlanView_t::nPairs, may be NULL.  All three NULL: TFQMRGPU_STATUS_NO_INFO_PASSED.
+ *
+ * The terms of cost2 are exactly the plan's own block products (tfqmrgpuPlanView_t::pairs) whose X operand is block n; every such
+ *   product lands on a different block of A X, and each is squared ON ITS OWN.
+ * What it says: let X' be X with block n set to zero.  A X' differs from A X, on the pattern, by exactly the blocks A_ik X_kc, so that
+ *   for block column c and right-hand side j
+ *       |B - A X'|  <=  sqrt(residual2[c*LN + j]) (section 10)  +  sqrt(cost2[n*LN + j]),     and
+ *       |B - A X'|^2 =  cost2[n*LN + j]  where the residual is zero.
+ *   For a SET of dropped blocks the square roots add (triangle inequality).  A caller drops block n when sqrt(cost2) is small against
+ *   threshold * sqrt(bnorm2) of section 10.
+ * What it does not say: a new solve on the shrunk pattern is a different truncated problem, not X'.  The dropped position becomes a leak
+ *   position of the new plan, and section 11 measures it there.
+ * Index and order: n is the caller's block order of X -- the order of bsrColIndX given to createPlan, whatever indexOffset was --, as in
+ *   getWorkVector and setBlocks.  Of two blocks of X on the same (block row, block column) the pair list knows the first only; the
+ *   second has no product.
+ * Operands: A is chosen as in section 11 -- the buffer's, or the kept copy (section 9) while the buffer holds A M^-1, patches of
+ *   setBlocks('A') that no set-up has seen yet included --; X what getMatrix('X') would return at that moment: after a solve the
+ *   solution (back-transformed on a preconditioned plan), after setMatrix('X') / setBlocks('X') the caller's X.  B is not read.
+ * Arithmetic: every product and every sum runs in double, whatever the plan's precision.  'z': double data.  'c': float data converted
+ *   on load.  'm': the plan's double copies of X and A.  Always four real products per complex one.
+ * Deterministic: one [LN] record per X block, written by one wave (block shapes that are multiples of 16) or by one work group (4- and
+ *   8-row shapes: the rows are added in row order); the products of a block are added in the order of the pair list; no atomics,
+ *   nothing is added across blocks.  Two calls on the same data give the same bits.
+ * An X block with no product gets exactly 0.0 in cost2: its block row holds no A block in a row of the column's pattern.
+ * Non-destructive: the call writes nothing into the caller's buffer; work vectors, bound history, residual, truncationLeak, leakMap and
+ *   a following solve are bit for bit what they would have been.  bufferSize and the buffer layout do not change.
+ * Memory: the listing -- the plan's pairs grouped by X block -- is built on the host in O(nPairs + nnzbX) by one stable counting sort at
+ *   the first call that asks for an array, and uploaded once.  Its device copy and the records (2 x [nnzbX][LN] doubles) are device
+ *   memory that the library owns, allocated by the first call that asks for an array, released by destroyPlan and by bufferSize.  The
+ *   kernel writes each record at the caller's block index, so the copy-out is a plain copy.  A plan that never makes the call runs the
+ *   launches it ran before and allocates nothing.
+ * Stream: asynchronous on the handle's stream up to the copy-out (nnzbX * LN doubles per array), then one synchronise (one more at the
+ *   upload of the listing).  Do not call it during a solve.
+ * All checks come before the first device call, in the order of section 11: plan / handle pointers; no bufferSize yet:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR; all three outputs NULL: TFQMRGPU_STATUS_NO_INFO_PASSED; both arrays NULL with nProducts given: it is filled
+ *   in from the plan alone and the call returns HERE -- no buffer and no A needed.  Then: no buffer: TFQMRGPU_POINTER_INVALID; a plan with
+ *   a user-defined operator: TFQMRGPU_NO_IMPLEMENTATION; and with cost2 given: A never set whole on this buffer:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A'; the A in the buffer has been scaled by the preconditioner and the plan keeps no
+ *   copy: TFQMRGPU_NO_IMPLEMENTATION.  With weight2 only, A is not needed and the last two checks are skipped.  After any error nothing
+ *   has been written, neither device nor host arrays nor *nProducts.
+ * Several ranks (section 4): local to the rank's plan, no collective. */
+tfqmrgpuStatus_t tfqmrgpuExt_dropCost(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double *cost2,                /* HOST [nnzbX][LN], may be NULL */
+    double *weight2,              /* HOST [nnzbX][LN], may be NULL */
+    uint64_t *nProducts);         /* = tfqmrgpuPlanView_t::nPairs, may be NULL */
+
+/* The pattern of X without the blocks drop[0 .. nDrop) (block positions of X in the caller's order, 0-based whatever indexOffset), in
+ * the form createPlan reads: host only, it needs the plan alone, not bufferSize.
+ * Every block row keeps its other blocks in their old order.  rowPtrX and colIndX carry the plan's indexOffset and the caller's block
+ *   column indices; oldBlock[n] is the old position of new block n, as in growPattern -- it is never -1 here.  Growing and shrinking
+ *   compose through the two oldBlock maps.  nDrop == 0 reproduces the old pattern (drop may be NULL then).
+ * A block column of X that loses all its blocks would vanish from the new pattern.  It would have held no B, and createPlan admits no
+ *   such column (TFQMRGPU_B_HAS_A_ZERO_COLUMN): on a plan every block column keeps at least its blocks of B.
+ * The arrays are malloc'ed by the library; tfqmrgpuExt_freeGrownPattern releases them.  Cost: O(nnzbX + nDrop + mb), no search.
+ * plan or shrunk NULL, or drop NULL with nDrop > 0: TFQMRGPU_POINTER_INVALID; an index < 0, an index >= nnzbX or an index named twice:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'X'; a listed block that carries a block of B (tfqmrgpuPlanView_t::subset):
+ *   TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'B' -- createPlan needs B's pattern inside X's.  After any error *shrunk is zeroed. */
+tfqmrgpuStatus_t tfqmrgpuExt_shrinkPattern(tfqmrgpuBsrsvPlan_t plan,
+    uint64_t nDrop, int32_t const *drop /* HOST, block positions of X in the caller's order */,
+    tfqmrgpuGrownPattern_t *shrunk);   /* released by tfqmrgpuExt_freeGrownPattern */
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,16 @@
+#!/bin/bash
+# The listing of the drop cost and the shrunk pattern (tfqmrgpu_amd/csrc/tfq_leak_host.cpp: drop_listing, shrink_pattern) under
+# AddressSanitizer and UndefinedBehaviorSanitizer, on a machine WITHOUT a GPU:   scripts/shrink_pattern_sanitize.sh [work dir]
+# Plain C++: compiled with scripts/shrink_pattern_check.cpp into ONE stand-alone program and run on the patterns that
+# scripts/leak_listing_inputs.py writes.  Host code only: never run this on a GPU machine or through Python.
+set -eu
+root=$(cd "$(dirname "$0")/.." && pwd)
+work=${1:-$(mktemp -d)}
+rocm=${ROCM:-/opt/rocm}
+cxx=${CXX:-$rocm/llvm/bin/clang++}
+[ -x "$cxx" ] || cxx=g++
+mkdir -p "$work"
+$cxx -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Wall -D__HIP_PLATFORM_AMD__ -I"$rocm/include" \
+    -I"$root/include" -I"$root/tfqmrgpu_amd/csrc" "$root/scripts/shrink_pattern_check.cpp" "$root/tfqmrgpu_amd/csrc/tfq_leak_host.cpp" -o "$work/shrink_pattern_check"
+files=$(python3 "$root/scripts/leak_listing_inputs.py" "$work/inputs")
+ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 "$work/shrink_pattern_check" $files

@@ -42,6 +42,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner", "tfqmrgpuExt_setBlocks", "tfqmrgpuExt_getBlocks",
     "tfqmrgpuExt_keepOperator", "tfqmrgpuExt_residual", "tfqmrgpuExt_truncationLeak", "tfqmrgpuExt_leakUnits",
     "tfqmrgpuExt_leakMap", "tfqmrgpuExt_growPattern", "tfqmrgpuExt_freeGrownPattern",
+    "tfqmrgpuExt_dropCost", "tfqmrgpuExt_shrinkPattern",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -156,6 +157,8 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_leakMap.argtypes = [P, P, C.c_uint64, P, P, P, C.POINTER(C.c_uint64)]
     lib.tfqmrgpuExt_growPattern.argtypes = [P, C.c_uint64, P, C.POINTER(GrownPattern)]
     lib.tfqmrgpuExt_freeGrownPattern.argtypes = [C.POINTER(GrownPattern)]
+    lib.tfqmrgpuExt_dropCost.argtypes = [P, P, P, P, C.POINTER(C.c_uint64)]
+    lib.tfqmrgpuExt_shrinkPattern.argtypes = [P, C.c_uint64, P, C.POINTER(GrownPattern)]
     lib.tfqmrgpuExt_freeGrownPattern.restype = None
     return lib
 
@@ -500,6 +503,41 @@ class Solver:
         if pr.X is not None:
             X = np.zeros((len(colIndX), pr.LM, pr.LN), dtype=np.complex128)
             X[old >= 0] = pr.X[old[old >= 0]]
+        return Problem(pr.rowPtrA, pr.colIndA, pr.A, rowPtrX, colIndX, pr.rowPtrB, pr.colIndB, pr.B, X, pr.tolerance, pr.index_offset)
+
+    def drop_cost(self, cost=True, weight=True):
+        """tfqmrgpu_ext.h section 13: what every block of X carries.  Returns a dict: cost2 [nnzbX, LN] float64, per block of X in the
+        caller's order and right-hand side the sum of |A_ik X_kc (:, j)|^2 over the plan's products with that block -- dropping the
+        block adds at most sqrt(cost2) to the residual norm of its column --, weight2 [nnzbX, LN] = |X_kc (:, j)|^2, and n_products
+        (plan_view()["nPairs"]).  cost=False / weight=False: that array is None and is not computed; both False: the count alone,
+        which needs create_plan and buffer_size only"""
+        n = int(self.plan_view()["nnzbX"])
+        cost2 = np.zeros((n, self.LN), np.float64) if cost else None
+        weight2 = np.zeros((n, self.LN), np.float64) if weight else None
+        count = C.c_uint64(0)
+        addr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)      # noqa: E731
+        _check(lib.tfqmrgpuExt_dropCost(self.handle, self.plan, addr(cost2), addr(weight2), C.byref(count)), "tfqmrgpuExt_dropCost")
+        return dict(cost2=cost2, weight2=weight2, n_products=int(count.value))
+
+    def shrink_pattern(self, drop):
+        """tfqmrgpu_ext.h section 13: the BSR pattern of X without the blocks `drop` (block positions of X in the caller's order,
+        0-based).  Returns (rowPtrX, colIndX, oldBlock) as int32 arrays: the form create_plan reads, and for every new block the old
+        block whose values it takes over.  Host only, needs create_plan alone"""
+        g = GrownPattern()
+        idx = np.ascontiguousarray(drop, dtype=np.int32).reshape(-1)
+        _check(lib.tfqmrgpuExt_shrinkPattern(self.plan, len(idx), C.c_void_p(idx.ctypes.data), C.byref(g)), "tfqmrgpuExt_shrinkPattern")
+        try:
+            def arr(p, n):
+                return np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, np.int32)
+            return arr(g.rowPtrX, g.mb + 1), arr(g.colIndX, g.nnzbX), arr(g.oldBlock, g.nnzbX)
+        finally:
+            lib.tfqmrgpuExt_freeGrownPattern(C.byref(g))
+
+    def shrink_problem(self, pr, drop):
+        """the Problem with the shrunk pattern of X (shrink_pattern) and the same A and B as `pr`, the problem of this plan; where `pr`
+        carries values of X the kept blocks keep theirs"""
+        rowPtrX, colIndX, old = self.shrink_pattern(drop)
+        X = None if pr.X is None else pr.X[old]
         return Problem(pr.rowPtrA, pr.colIndA, pr.A, rowPtrX, colIndX, pr.rowPtrB, pr.colIndB, pr.B, X, pr.tolerance, pr.index_offset)
 
     def bound_history(self):

@@ -291,6 +291,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     p->opScratch.release();                // sized for the previous block shape
     p->residualScratch.release();          // ... and the previous chunks
     p->leak = LeakListing{}; p->leakDev.release(); p->leakMapRec.release();   // ... and the work units of the previous block shape
+    p->dropDev.release();                  // ... and the records of the previous block shape
     a_new_layout(*p);
     p->precision = prec;
     p->buffer = nullptr;
@@ -743,6 +744,22 @@ tfqmrgpuStatus_t tfqmrgpuExt_applyOperator(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
+// ---- sections 10 to 13 grade the caller's system on the device: their checks in front of the first device call, in the documented order, and
+// the operand they read.  needA: the call reads A (the patterns-only forms and the weights of section 13 do not)
+static tfqmrgpuStatus_t operands_ready(Plan const& p, bool const needA) {
+    if (nullptr == p.buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (p.opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);         // a user-defined operator is the caller's to apply
+    if (!needA) return TFQMRGPU_STATUS_SUCCESS;
+    if (!p.haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+    if (TFQMRGPU_PRECOND_NONE != p.precondInA && !kept_is_callers_a(p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone; keepOperator keeps it
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+// the caller's A: the buffer's, or the kept copy while the buffer holds A M^-1 ('m': its double part) -- a patch of setBlocks('A') that no
+// set-up has seen yet is in the copy already
+static void const* callers_a(Plan const& p, DevPlan const& d) {
+    return (TFQMRGPU_PRECOND_NONE != p.precondInA) ? (void const*)kept_a(p).a : d.A;
+}
+
 // ---- per-right-hand-side residual of the caller's system (tfqmrgpu_ext.h section 10) --------------------------------------------------
 tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
     double* residual2, double* bnorm2, int32_t* columns, double* worst)
@@ -751,11 +768,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
     if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
     if (!residual2 && !bnorm2 && !columns && !worst) return TFQMRGPU_STATUS_NO_INFO_PASSED;
-    if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (p->opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);        // a user-defined operator is the caller's to apply
-    if (!p->haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
-    bool const scaled = (TFQMRGPU_PRECOND_NONE != p->precondInA);
-    if (scaled && !kept_is_callers_a(*p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone; keepOperator keeps it
+    if (auto const st = operands_ready(*p, true)) return st;
 
     hipStream_t const s = (hipStream_t)h->stream;
     DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X, B and A
@@ -764,10 +777,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
     try { host.resize(nCol); } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     if (auto const st = p->residualScratch.reserve(std::max<size_t>((nRec + nCol) * sizeof(double), 256))) return st;
     double* const rec = p->residualScratch.as<double>();
-    // the caller's A: the buffer's, or the kept copy while the buffer holds A M^-1 ('m': its double part) -- a patch of setBlocks('A')
-    // that no set-up has seen yet is in the copy already
-    void const* const A = scaled ? (void const*)kept_a(*p).a : d.A;
-    residual_launch(d, A, rec, rec + nRec, s);
+    residual_launch(d, callers_a(*p, d), rec, rec + nRec, s);
     TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
     if (nCol) TFQ_HIP(hipMemcpyAsync(host.data(), rec + nRec, nCol * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
     TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
@@ -837,12 +847,8 @@ tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsr
     if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
     if (!leak2 && !columns && !nLeakBlocks && !nLeakPairs) return TFQMRGPU_STATUS_NO_INFO_PASSED;
-    if (leak2) {                                                    // everything else depends on the patterns alone: plan and bufferSize suffice
-        if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-        if (p->opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);    // a user-defined operator is the caller's to apply
-        if (!p->haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
-        if (TFQMRGPU_PRECOND_NONE != p->precondInA && !kept_is_callers_a(*p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone
-    }
+    // everything but leak2 depends on the patterns alone: plan and bufferSize suffice
+    if (leak2) if (auto const st = operands_ready(*p, true)) return st;
     if (auto const st = leak_host(*p)) return st;
     auto& l = p->leak;
     size_t const LN = size_t(p->LN), nUnits = l.nUnits(), nCol = size_t(p->nCols) * LN;
@@ -854,9 +860,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsr
         if (auto const st = leak_device(*p, o, s)) return st;       // the first call: upload the listing, one synchronise
         char* const dev = p->leakDev.as<char>();
         DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
-        // the caller's A: the buffer's, or the kept copy while the buffer holds A M^-1 ('m': its double part), pending patches included
-        void const* const A = (TFQMRGPU_PRECOND_NONE != p->precondInA) ? (void const*)kept_a(*p).a : d.A;
-        leak_launch(d, A, uint32_t(nUnits), (uint32_t const*)(dev + o.oPairs), (uint32_t const*)(dev + o.oPos), (uint32_t const*)(dev + o.oUnit),
+        leak_launch(d, callers_a(*p, d), uint32_t(nUnits), (uint32_t const*)(dev + o.oPairs), (uint32_t const*)(dev + o.oPos), (uint32_t const*)(dev + o.oUnit),
                     (uint32_t const*)(dev + o.oCol), (double*)(dev + o.oRec), (double*)(dev + o.oSum), s);
         TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
         if (nCol) TFQ_HIP(hipMemcpyAsync(host.data(), dev + o.oSum, nCol * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
@@ -877,12 +881,8 @@ tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_
     if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
     if (!rows && !cols && !pos2 && !nLeakBlocks) return TFQMRGPU_STATUS_NO_INFO_PASSED;
-    if (pos2) {                                                     // everything else depends on the patterns alone, as in section 11
-        if (nullptr == p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-        if (p->opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
-        if (!p->haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
-        if (TFQMRGPU_PRECOND_NONE != p->precondInA && !kept_is_callers_a(*p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone
-    }
+    // everything but pos2 depends on the patterns alone, as in section 11
+    if (pos2) if (auto const st = operands_ready(*p, true)) return st;
     if (auto const st = leak_host(*p)) return st;
     auto const& l = p->leak;
     size_t const LN = size_t(p->LN), nPos = l.nPositions();
@@ -899,8 +899,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_
         if (auto const st = p->leakMapRec.reserve(std::max<size_t>(nPos * LN * sizeof(double), 256))) return st;
         char* const dev = p->leakDev.as<char>();
         DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
-        void const* const A = (TFQMRGPU_PRECOND_NONE != p->precondInA) ? (void const*)kept_a(*p).a : d.A;   // the caller's A, as in section 11
-        leak_map_launch(d, A, uint32_t(nPos), (uint32_t const*)(dev + o.oPairs), (uint32_t const*)(dev + o.oPos), p->leakMapRec.as<double>(), s);
+        leak_map_launch(d, callers_a(*p, d), uint32_t(nPos), (uint32_t const*)(dev + o.oPairs), (uint32_t const*)(dev + o.oPos), p->leakMapRec.as<double>(), s);
         TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
         TFQ_HIP(hipMemcpyAsync(host.data(), p->leakMapRec.ptr, nPos * LN * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
         TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
@@ -909,6 +908,22 @@ tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_
     if (rows) for (size_t n = 0; n < nPos; ++n) rows[n] = int32_t(l.posRow[n]);
     if (cols) for (size_t n = 0; n < nPos; ++n) cols[n] = int32_t(l.posCol[n]);
     if (nLeakBlocks) *nLeakBlocks = uint64_t(nPos);
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// a pattern of sections 12 and 13 into malloc'ed arrays for the caller (tfqmrgpuExt_freeGrownPattern releases them)
+static tfqmrgpuStatus_t export_pattern(Plan const& p, GrownPattern const& g, tfqmrgpuGrownPattern_t* to) {
+    auto dup = [](std::vector<int32_t> const& v) {
+        auto q = (int32_t*)std::malloc(std::max<size_t>(1, v.size()) * sizeof(int32_t));
+        if (q) std::copy(v.begin(), v.end(), q);
+        return q;
+    };
+    to->mb = int32_t(p.nRows); to->nnzbX = int32_t(g.colInd.size());
+    to->rowPtrX = dup(g.rowPtr); to->colIndX = dup(g.colInd); to->oldBlock = dup(g.oldBlock);
+    if (!to->rowPtrX || !to->colIndX || !to->oldBlock) {
+        tfqmrgpuExt_freeGrownPattern(to);
+        return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
+    }
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
@@ -926,24 +941,84 @@ tfqmrgpuStatus_t tfqmrgpuExt_growPattern(tfqmrgpuBsrsvPlan_t plan, uint64_t nTak
         if (1 == bad) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');   // an index >= nLeakBlocks, or one named twice
         if (bad) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);        // the index arrays are 32 bit
     } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    auto dup = [](std::vector<int32_t> const& v) {
-        auto q = (int32_t*)std::malloc(std::max<size_t>(1, v.size()) * sizeof(int32_t));
-        if (q) std::copy(v.begin(), v.end(), q);
-        return q;
-    };
-    grown->mb = int32_t(p->nRows); grown->nnzbX = int32_t(g.colInd.size());
-    grown->rowPtrX = dup(g.rowPtr); grown->colIndX = dup(g.colInd); grown->oldBlock = dup(g.oldBlock);
-    if (!grown->rowPtrX || !grown->colIndX || !grown->oldBlock) {
-        tfqmrgpuExt_freeGrownPattern(grown);
-        return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
-    }
-    return TFQMRGPU_STATUS_SUCCESS;
+    return export_pattern(*p, g, grown);
 }
 
 void tfqmrgpuExt_freeGrownPattern(tfqmrgpuGrownPattern_t* grown) {
     if (!grown) return;
     std::free(grown->rowPtrX); std::free(grown->colIndX); std::free(grown->oldBlock);
     *grown = tfqmrgpuGrownPattern_t{};
+}
+
+// ---- drop cost: what each block of X carries, and the pattern of X without chosen blocks (tfqmrgpu_ext.h section 13) ------------------
+// the listing on the device, Plan::dropDev: [start | aOf | xOf | cost records | weight records], every piece on a 256-byte boundary
+struct DropDev { size_t oStart, oA, oX, oCost, oWeight, total; };
+static DropDev drop_dev_layout(Plan const& p) {
+    auto const& l = p.drop;
+    size_t const rec = align256(size_t(p.nnzbX) * size_t(p.LN) * sizeof(double));
+    DropDev o{};
+    o.oStart = 0; o.oA = o.oStart + align256(l.start.size() * 4); o.oX = o.oA + align256(l.aOf.size() * 4);
+    o.oCost = o.oX + align256(l.xOf.size() * 4); o.oWeight = o.oCost + rec; o.total = o.oWeight + rec;
+    return o;
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_dropCost(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double* cost2, double* weight2, uint64_t* nProducts) {
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
+    if (!cost2 && !weight2 && !nProducts) return TFQMRGPU_STATUS_NO_INFO_PASSED;
+    if (!cost2 && !weight2) { *nProducts = uint64_t(p->nPairs()); return TFQMRGPU_STATUS_SUCCESS; }   // the plan alone: no buffer, no A
+    if (auto const st = operands_ready(*p, nullptr != cost2)) return st;    // the weights do not read A
+
+    size_t const n = size_t(p->nnzbX) * size_t(p->LN);
+    std::vector<double> hostCost, hostWeight;                       // through host vectors: a failed copy leaves the caller's arrays untouched
+    try {
+        if (cost2) hostCost.resize(n);
+        if (weight2) hostWeight.resize(n);
+        if (!p->drop.built) drop_listing(p->drop, p->nnzbX, p->nPairs(), p->pairs.data(), p->u2i.data());
+    } catch (std::bad_alloc const&) { p->drop = DropListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    hipStream_t const s = (hipStream_t)h->stream;
+    auto const& l = p->drop;
+    auto const o = drop_dev_layout(*p);
+    if (!p->dropDev) {                                              // the first call: upload the listing, one synchronise
+        if (auto const st = p->dropDev.reserve(std::max<size_t>(o.total, 256))) return st;
+        char* const dev = p->dropDev.as<char>();
+        tfqmrgpuStatus_t st = upload(dev + o.oStart, l.start.data(), l.start.size() * 4, s);
+        if (!st) st = upload(dev + o.oA, l.aOf.data(), l.aOf.size() * 4, s);
+        if (!st) st = upload(dev + o.oX, l.xOf.data(), l.xOf.size() * 4, s);
+        if (!st && hipSuccess != hipStreamSynchronize(s)) st = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
+        if (st) { p->dropDev.release(); return st; }
+    }
+    char* const dev = p->dropDev.as<char>();
+    DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
+    // the kernel writes the record of a block at the caller's index of that block: the copy-out is a plain copy
+    drop_cost_launch(d, cost2 ? callers_a(*p, d) : nullptr, p->nnzbX, (uint32_t const*)(dev + o.oStart), (uint32_t const*)(dev + o.oA),
+                     (uint32_t const*)(dev + o.oX), cost2 ? (double*)(dev + o.oCost) : nullptr, weight2 ? (double*)(dev + o.oWeight) : nullptr, s);
+    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    if (cost2 && n) TFQ_HIP(hipMemcpyAsync(hostCost.data(), dev + o.oCost, n * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    if (weight2 && n) TFQ_HIP(hipMemcpyAsync(hostWeight.data(), dev + o.oWeight, n * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    if (cost2) std::copy(hostCost.begin(), hostCost.end(), cost2);
+    if (weight2) std::copy(hostWeight.begin(), hostWeight.end(), weight2);
+    if (nProducts) *nProducts = uint64_t(p->nPairs());
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_shrinkPattern(tfqmrgpuBsrsvPlan_t plan, uint64_t nDrop, int32_t const* drop, tfqmrgpuGrownPattern_t* shrunk) {
+    auto p = asPlan(plan);
+    if (!p || !shrunk) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    *shrunk = tfqmrgpuGrownPattern_t{};
+    if (nDrop > 0 && !drop) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    GrownPattern g;
+    try {
+        std::vector<uint8_t> hasB(p->nnzbX, uint8_t(0));
+        for (auto const x : p->subset) hasB[x] = 1;
+        int const bad = shrink_pattern(g, p->nRows, p->nnzbX, p->rowOfX.data(), p->col32.data(), p->original_bsrColIndX.data(),
+                                       p->indexOffset, hasB.data(), nDrop, drop);
+        if (1 == bad) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');   // an index outside [0, nnzbX), or one named twice
+        if (bad) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'B');        // the block carries a block of B
+    } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    return export_pattern(*p, g, shrunk);
 }
 
 // how the listing is cut: work units per compressed block column

@@ -1,6 +1,8 @@
 // Truncation leak (tfqmrgpu_ext.h section 11), host side: which block products A_ik X_kc land on a block row i that block column c of X
-// does NOT hold; and the pattern of X grown by chosen ones of those positions (section 12, grow_pattern at the end of the file).  Plain C++ on
-// plain index arrays -- no Plan, no device: scripts/leak_listing_check.cpp and scripts/grow_pattern_check.cpp run it under the sanitizers.
+// does NOT hold; the pattern of X grown by chosen ones of those positions (section 12, grow_pattern); and, at the end of the file, the
+// plan's products grouped by X block and the pattern of X without chosen blocks (section 13, drop_listing and shrink_pattern).  Plain C++ on
+// plain index arrays -- no Plan, no device: scripts/leak_listing_check.cpp, scripts/grow_pattern_check.cpp and
+// scripts/shrink_pattern_check.cpp run it under the sanitizers.
 //
 // One pass over the block rows i of A.  Row i of X is stamped into a [nCols] array, so that "(i, c) is in the pattern of X" is one
 // comparison; for every A block (i, k) of the row, in ascending k, every X block (k, c) of row k whose column is not stamped is a product
@@ -154,6 +156,48 @@ int grow_pattern(GrownPattern& out, uint32_t nRows, uint32_t nCols, uint32_t nnz
         auto const at = fill[r]++;
         g.colInd[at] = callersCol[c]; g.oldBlock[at] = -1;
     }
+    for (auto& v : g.rowPtr) v += indexOffset;
+    out = std::move(g);
+    return 0;
+}
+
+// The listing of the drop cost (tfqmrgpu_ext.h section 13): the plan's pair list comes grouped by the block of A X that a product lands
+// on; one stable counting sort by the X operand groups it by X block and keeps the order of the pair list inside a block
+void drop_listing(DropListing& out, uint32_t nnzbX, size_t nPairs, uint32_t const* pairs, uint32_t const* u2i) {
+    out = DropListing{};
+    out.start.assign(size_t(nnzbX) + 1, 0u);
+    for (size_t q = 0; q < nPairs; ++q) ++out.start[pairs[2 * q + 1] + 1];
+    for (uint32_t x = 0; x < nnzbX; ++x) out.start[x + 1] += out.start[x];
+    out.aOf.resize(nPairs);
+    std::vector<uint32_t> fill(out.start.begin(), out.start.end() - 1);
+    for (size_t q = 0; q < nPairs; ++q) out.aOf[fill[pairs[2 * q + 1]]++] = pairs[2 * q];
+    out.xOf.assign(u2i, u2i + nnzbX);
+    out.built = true;
+}
+
+// The shrunk pattern (section 13): one mark per old block, so that a block named twice is one comparison; the blocks that stay are
+// written in the caller's order, which is the order inside every block row.  Cost: O(nnzbX + nDrop + nRows), nothing is searched
+int shrink_pattern(GrownPattern& out, uint32_t nRows, uint32_t nnzbX, uint32_t const* rowOfX, uint32_t const* colOfX,
+    int32_t const* callersCol, int indexOffset, uint8_t const* hasB, uint64_t nDrop, int32_t const* drop)
+{
+    out = GrownPattern{};
+    if (nDrop > uint64_t(nnzbX)) return 1;                           // more indices than blocks: one is out of range or named twice
+    std::vector<uint8_t> gone(nnzbX, uint8_t(0));
+    for (uint64_t n = 0; n < nDrop; ++n) {
+        if (drop[n] < 0 || uint32_t(drop[n]) >= nnzbX || gone[drop[n]]) return 1;
+        gone[drop[n]] = 1;
+    }
+    for (uint64_t n = 0; n < nDrop; ++n) if (hasB[drop[n]]) return 2;  // (behind the look at every index: a bad list is a bad list first)
+    GrownPattern g;
+    g.rowPtr.assign(size_t(nRows) + 1, 0);
+    size_t const nnzb = size_t(nnzbX) - size_t(nDrop);
+    g.colInd.reserve(nnzb); g.oldBlock.reserve(nnzb);
+    for (uint32_t x = 0; x < nnzbX; ++x) {
+        if (gone[x]) continue;
+        ++g.rowPtr[rowOfX[x] + 1];
+        g.colInd.push_back(callersCol[colOfX[x]]); g.oldBlock.push_back(int32_t(x));
+    }
+    for (uint32_t r = 0; r < nRows; ++r) g.rowPtr[r + 1] += g.rowPtr[r];
     for (auto& v : g.rowPtr) v += indexOffset;
     out = std::move(g);
     return 0;

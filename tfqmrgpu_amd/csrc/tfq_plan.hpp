@@ -144,6 +144,25 @@ struct GrownPattern {
 int grow_pattern(GrownPattern& out, uint32_t nRows, uint32_t nCols, uint32_t nnzbX, uint32_t const* rowOfX, uint32_t const* colOfX,
     int32_t const* callersCol, int indexOffset, size_t nPos, uint32_t const* posRow, uint32_t const* posCol, uint64_t nTake, uint64_t const* take);
 
+// tfqmrgpuExt_dropCost (tfqmrgpu_ext.h section 13): the plan's own block products (Plan::pairs) grouped by their X operand.  Everything
+// is indexed by the caller's block order of X, so that the kernel writes its record where the caller reads it; xOf says where the values
+// of a block lie in the buffer.  The products of a block keep the order of the pair list (tfq_leak_host.cpp: drop_listing)
+struct DropListing {
+    std::vector<uint32_t> start;          // [nnzbX+1] first product of each X block
+    std::vector<uint32_t> aOf;            // [nPairs] the A block of each product, in the caller's order of A
+    std::vector<uint32_t> xOf;            // [nnzbX] internal index of each X block
+    bool built = false;
+};
+// from the pair list (A block, X block in the caller's order) and the internal index of every X block: one stable counting sort by
+// X block, O(nPairs + nnzbX)
+void drop_listing(DropListing& out, uint32_t nnzbX, size_t nPairs, uint32_t const* pairs, uint32_t const* u2i);
+
+// tfqmrgpuExt_shrinkPattern (section 13): the old pattern, as for grow_pattern, without the blocks drop[0 .. nDrop) (the caller's block
+// order); hasB[x] != 0: block x carries a block of B.  Every block row keeps its other blocks in their order; oldBlock is never -1.
+// 0: done; 1: an index < 0 or >= nnzbX or an index named twice; 2: a listed block carries B.  `out` is empty unless 0 is returned
+int shrink_pattern(GrownPattern& out, uint32_t nRows, uint32_t nnzbX, uint32_t const* rowOfX, uint32_t const* colOfX,
+    int32_t const* callersCol, int indexOffset, uint8_t const* hasB, uint64_t nDrop, int32_t const* drop);
+
 struct Handle {
     void* stream = nullptr;               // hipStream_t
     // multi-GPU stopping test (tfqmrgpu_ext.h section 4)
@@ -259,6 +278,11 @@ struct Plan {
     // tfqmrgpuExt_leakMap (tfqmrgpu_ext.h section 12): one [LN] record of doubles per leak position, allocated at the first call that asks
     // for pos2; the listing on the device is leakDev's (sized by the block shape and the positions: released by bufferSize)
     DevMem leakMapRec;
+    // tfqmrgpuExt_dropCost (tfqmrgpu_ext.h section 13): the pairs grouped by X block (built at the first call that needs it; patterns
+    // only, it outlives bufferSize) and its device copy [start | aOf | xOf | cost records [nnzbX][LN] | weight records [nnzbX][LN]],
+    // allocated and uploaded by the first call that asks for an array (sized by the block shape: released by bufferSize)
+    DropListing drop;
+    DevMem dropDev;
 
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;

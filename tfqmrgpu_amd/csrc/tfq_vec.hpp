@@ -47,4 +47,11 @@ void leak_launch(DevPlan const& d, void const* A, uint32_t nUnits, uint32_t cons
 // rec [nPos][LN], the caller's scratch; nothing else is written (tfq_leak_map.hip; tfqmrgpuExt_leakMap)
 void leak_map_launch(DevPlan const& d, void const* A, uint32_t nPos, uint32_t const* pairs, uint32_t const* posStart, double* rec, hipStream_t s);
 
+// per block n of the plan's X (the caller's block order, nX blocks) and right-hand side: cost [nX][LN] = the sum over the products
+// start[n] .. start[n + 1] of the listing (tfq_plan.hpp: DropListing, all three lists in device memory) of |A_aOf[q] X_n (:, j)|^2, every
+// product squared on its own, and weight [nX][LN] = |X_n (:, j)|^2, in double (tfq_drop_cost.hip; tfqmrgpuExt_dropCost).  cost or weight
+// may be nullptr (cost == nullptr: A is not read); both are the caller's scratch; nothing else is written
+void drop_cost_launch(DevPlan const& d, void const* A, uint32_t nX, uint32_t const* start, uint32_t const* aOf, uint32_t const* xOf,
+    double* cost, double* weight, hipStream_t s);
+
 } // namespace tfq
