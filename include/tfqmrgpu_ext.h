@@ -566,6 +566,47 @@ tfqmrgpuStatus_t tfqmrgpuExt_shrinkPattern(tfqmrgpuBsrsvPlan_t plan,
     uint64_t nDrop, int32_t const *drop /* HOST, block positions of X in the caller's order */,
     tfqmrgpuGrownPattern_t *shrunk);   /* released by tfqmrgpuExt_freeGrownPattern */
 
+/* ---- (14) warm start: solve from the X in the plan --------------------------------------------------------------------------------- */
+/* tfqmrgpu_bsrsv_solve zeroes X, as the reference does (tfqmrgpu_core.hxx:125): whatever setMatrix('X') brought, or the last solve left,
+ * is ignored.  The loops that sections 8 to 13 serve all end in a solve that has a good X at hand: the re-solve on a grown or shrunk
+ * pattern (sections 12, 13: the old values mapped through oldBlock), the next energy of a loop that patches the diagonal blocks of A
+ * (sections 8, 9), and a solve that ended at TFQMRGPU_STATUS_MAX_ITERATIONS.  solveFrom solves A X = B starting from X0, the X in the
+ * plan; tfqmrgpu_bsrsv_solve itself is unchanged and still ignores X.
+ *
+ * X0 is what getMatrix('X') would return at that moment: after a solve the solution (back-transformed on a preconditioned plan,
+ *   section 7), after setMatrix('X') / setBlocks('X') the caller's X.
+ * It runs as a correction solve: R = B - A X0, truncated to the pattern of X as every product is and formed in the
+ *   plan's precision; tfQMR solves A D = R from zero with the kernels and the driver of tfqmrgpu_bsrsv_solve; then X = X0 + D.
+ * threshold and getInfo keep their meaning: every residual is RELATIVE TO |B| per right-hand side, not to |R|; the bound of the
+ *   recurrence starts at |r|^2 / |b|^2 instead of 1.  A solve from a converged X0 stops after its first iteration, whose probe confirms it.
+ * Afterwards getBoundHistory, getInfo and getWorkVector(.., 1) are as after solve: the iterations are those of the correction solve,
+ *   flops_performed includes the product A X0, the residual pass and the update.  getWorkVector(.., 4 ... 9) return the vectors of the
+ *   CORRECTION solve A D = R, started from D = 0 with R as its right-hand side: they belong to D, not to X.
+ * A right-hand side whose R is exactly zero keeps its X0 bit for bit: it is neither a breakdown nor a NaN, and takes no part in the
+ *   status (it is treated as a zero column of B is in solve).  A right-hand side with b = 0 has nothing to be relative to and is graded
+ *   against |r|, as in a cold solve of the correction system.
+ * maxIterations <= 0: X = X0 is left untouched; the status is TFQMRGPU_STATUS_MAX_ITERATIONS, as solve returns for it.
+ * tfqmrgpu_bsrsv_solve on the same plan, before or after, is bit for bit the solve it was: the same launches, the same buffer.
+ * Precisions: 'z' and 'c'.  'm': TFQMRGPU_NO_IMPLEMENTATION -- the refinement has a cycle 0 and a |b|^2 bookkeeping of its own; a follow-up.
+ * Preconditioner (section 7): supported.  R needs the caller's A: the buffer's while it has not been scaled -- R is formed first, then
+ *   the set-up scales A --, the kept copy (section 9) once it has, patches of setBlocks('A') that no set-up has seen yet included, as in
+ *   section 10.  The correction solve runs on A M^-1; its result is back-transformed into D before X0 is added.  Scaled and no copy kept:
+ *   TFQMRGPU_NO_IMPLEMENTATION, as residual.
+ * A user-defined operator (section 5): TFQMRGPU_NO_IMPLEMENTATION.  Several ranks (section 4): TFQMRGPU_NO_IMPLEMENTATION on every rank,
+ *   through the collective in front of a solve, so that all ranks leave together.
+ * Deterministic: one work group per chunk and per block column of the plan's own tables, every sum in a fixed order, no atomics.  Two
+ *   calls from the same X0 give the same bits.
+ * Memory: X0 and R, two X-shaped vectors in the plan's precision, are device memory that the library owns, allocated by the first call,
+ *   released by destroyPlan, bufferSize and setBuffer.  A X0 lives in work vector v9, which the driver writes before it reads.  bufferSize
+ *   and the buffer layout do not change; a plan that never makes the call allocates nothing and runs the launches it ran before.
+ * Stream: asynchronous on the handle's stream; it synchronises where solve does.  Do not call it during a solve.
+ * All checks come before the first device call, in the order of section 10: plan / handle pointers: TFQMRGPU_POINTER_INVALID; no
+ *   bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; no buffer: TFQMRGPU_POINTER_INVALID; a user-defined operator: TFQMRGPU_NO_IMPLEMENTATION;
+ *   an 'm' plan: TFQMRGPU_NO_IMPLEMENTATION; A never set whole on this buffer: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A'; A
+ *   scaled and no copy kept: TFQMRGPU_NO_IMPLEMENTATION.  After any error nothing has been written: not X, not the results of the last solve. */
+tfqmrgpuStatus_t tfqmrgpuExt_solveFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double threshold, int maxIterations);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner", "tfqmrgpuExt_setBlocks", "tfqmrgpuExt_getBlocks",
     "tfqmrgpuExt_keepOperator", "tfqmrgpuExt_residual", "tfqmrgpuExt_truncationLeak", "tfqmrgpuExt_leakUnits",
     "tfqmrgpuExt_leakMap", "tfqmrgpuExt_growPattern", "tfqmrgpuExt_freeGrownPattern",
-    "tfqmrgpuExt_dropCost", "tfqmrgpuExt_shrinkPattern",
+    "tfqmrgpuExt_dropCost", "tfqmrgpuExt_shrinkPattern", "tfqmrgpuExt_solveFrom",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -160,6 +160,7 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_dropCost.argtypes = [P, P, P, P, C.POINTER(C.c_uint64)]
     lib.tfqmrgpuExt_shrinkPattern.argtypes = [P, C.c_uint64, P, C.POINTER(GrownPattern)]
     lib.tfqmrgpuExt_freeGrownPattern.restype = None
+    lib.tfqmrgpuExt_solveFrom.argtypes = [P, P, C.c_double, I]
     return lib
 
 
@@ -377,6 +378,13 @@ class Solver:
         """returns the raw status: 0 converged, 9 max iterations, 6 breakdown (tfqmrgpu_core.hxx:170,258,297)"""
         st = lib.tfqmrgpu_bsrsv_solve(self.handle, self.plan, threshold, max_iterations)
         return _check(st, "tfqmrgpu_bsrsv_solve", allowed=(0, 6, 9))
+
+    def solve_from(self, threshold, max_iterations):
+        """tfqmrgpu_ext.h section 14: the same solve started from the X in the plan -- the last solution, or what set_matrix('X') /
+        set_blocks('X') brought -- where solve() ignores it and starts from zero.  threshold and get_info stay relative to |B|.
+        Returns the raw status as solve does"""
+        st = lib.tfqmrgpuExt_solveFrom(self.handle, self.plan, threshold, max_iterations)
+        return _check(st, "tfqmrgpuExt_solveFrom", allowed=(0, 6, 9))
 
     def set_operator(self, multiply):
         """user-defined operator (tfqmrgpu_ext.h section 5): multiply(Y_ptr, X_ptr, colindx_ptr, nnzbX, nCols, lm, ln,

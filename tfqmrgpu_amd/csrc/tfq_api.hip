@@ -38,7 +38,7 @@ DevPlan resolve(Plan const& p) {
     d.aOnce = (p.aOnce && antEnv) ? 1 : 0;   // (lab builds, TFQMRGPU_A_STREAM=0: A operands always through the caches)
     d.m3 = p.threeProducts ? 1 : 0;
     d.fold = 0; d.foldCount = (uint32_t*)at(p.wFold); d.self = (DevPlan const*)at(p.wSelf);
-    d.R = ('m' == p.precision) ? at(p.wR) : nullptr;
+    d.R = ('m' == p.precision) ? at(p.wR) : p.warmR;          // (warmR: the R of a warm solve while it runs, tfq_solve.cpp: run_solve_from; null otherwise)
     d.x = at(p.wX); d.v4 = at(p.wV4); d.v5 = at(p.wV5); d.v6 = at(p.wV6); d.v7 = at(p.wV7);
     d.v8 = at(p.wV8); d.v9 = at(p.wV9); d.B = at(p.wB); d.A = at(p.wA); d.v3 = (float*)at(p.wV3);
     d.rho = at(p.wRho); d.alfa = at(p.wAlfa); d.beta = at(p.wBeta); d.c67 = at(p.wC67); d.eta = at(p.wEta);
@@ -292,6 +292,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     p->residualScratch.release();          // ... and the previous chunks
     p->leak = LeakListing{}; p->leakDev.release(); p->leakMapRec.release();   // ... and the work units of the previous block shape
     p->dropDev.release();                  // ... and the records of the previous block shape
+    p->warm.release();                     // ... and X0 and R of the previous block shape
     a_new_layout(*p);
     p->precision = prec;
     p->buffer = nullptr;
@@ -308,6 +309,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     hipStream_t const s = (hipStream_t)h->stream;
     p->buffer = (char*)pBuffer;
     a_new_buffer(*p);
+    p->warm.release();                     // (X0 and R of a warm solve belong to the X of the old buffer)
     auto at = [&](Window const& w) { return (void*)(p->buffer + w.offset); };
     for (auto const& l : indexLists(*p))   // (tfq_plan.cpp: the windows were sized from the same list)
         if (auto const st = upload(at(*l.window), l.data, l.bytes, s)) return st;
@@ -796,6 +798,19 @@ tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
     }
     if (worst) *worst = any ? std::sqrt(wmax) : std::nan("");
     return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// ---- warm start: solve from the X in the plan (tfqmrgpu_ext.h section 14) ------------------------------------------------------------
+tfqmrgpuStatus_t tfqmrgpuExt_solveFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double const threshold, int const maxIterations) {
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
+    // the order of section 10, with the precision between the operator and A: no buffer | user-defined operator | 'm' | A never set | A scaled and not kept
+    tfqmrgpuStatus_t early = operands_ready(*p, false);
+    if (!early && 'm' == p->precision) early = TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // run_mixed has its own cycle 0 and |b|^2: a follow-up
+    if (!early) early = operands_ready(*p, true);
+    void const* const a = early ? nullptr : callers_a(*p, resolve(*p));
+    return run_solve_from(*h, *p, threshold, maxIterations, a, early);
 }
 
 // ---- truncation leak: what A X puts outside the pattern of X (tfqmrgpu_ext.h sections 11 and 12) --------------------------------------

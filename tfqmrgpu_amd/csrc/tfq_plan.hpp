@@ -283,6 +283,10 @@ struct Plan {
     // allocated and uploaded by the first call that asks for an array (sized by the block shape: released by bufferSize)
     DropListing drop;
     DevMem dropDev;
+    // tfqmrgpuExt_solveFrom (tfqmrgpu_ext.h section 14): library-owned [X0 | R], two X-shaped vectors of the plan's storage type, allocated
+    // by the first call (sized by the block shape, and holding values of the buffer they were taken from: released by bufferSize and setBuffer)
+    DevMem warm;
+    void* warmR = nullptr;             // not null only while a warm solve runs: resolve() hands it to the driver as DevPlan::R
 
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;

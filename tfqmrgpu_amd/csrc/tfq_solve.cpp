@@ -501,10 +501,70 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt) {
     return result;
 }
 
-tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt) {
+// what a solve leaves for getInfo, getBoundHistory and the profile, as it is before the solve starts
+static void reset_results(Plan& p, int maxIt) {
     for (int k = 0; k < TFQMRGPU_PROFILE_CLASSES; ++k) { p.profLaunches[k] = 0; p.profMs[k] = 0; p.profGatedLaunches[k] = 0; p.profGatedMs[k] = 0; p.profFirstLaunches[k] = 0; p.profFirstMs[k] = 0; }
     p.boundHistory.clear(); p.cycleResidual.clear(); p.cycleIterations.clear(); p.refinementCycles = 0;
     p.iterations_needed = maxIt; p.flops_performed = 0;
+}
+
+// Warm start (tfqmrgpu_ext.h section 14): the driver above, untouched, wrapped in a correction solve the way run_mixed wraps it.
+//   Y = A X0 (the caller's A, one spmm_apply into v9) | X0 := x, R := B - Y, tau = |r|^2, 1 / |b|^2 (tfq_warm.hip) | [A := A M^-1] |
+//   run_tfqmr on A D = R from zero, R its X-shaped right-hand side (DevPlan::R) | [D := M^-1 D] | x := X0 + D
+// v9 holds Y: before its first iteration the driver reads neither x nor v4 ... v9 -- the kernels of that iteration take x, v4, v6, v7, v8 as
+// zero and v5 as the right-hand side (DevPlan::first), and v9 is written by the first multiply before k_v5_nrm reads it -- and the
+// residual pass has consumed Y by then.  X0 cannot live there: the first iteration writes every work vector, and x itself.
+tfqmrgpuStatus_t run_solve_from(Handle& h, Plan& p, double tol, int maxIt, void const* callersA, tfqmrgpuStatus_t early) {
+    SolveOutcome o;
+    // several ranks: refused (the residual pass has no reduction over ranks yet).  Through the vote, so that every rank leaves together
+    if (several_ranks(h)) return run_tfqmr(h, p, tol, maxIt, early ? early : TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION), 1., o);
+    if (early) return early;
+    if ('z' != p.precision && 'c' != p.precision) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+    reset_results(p, maxIt);
+    if (maxIt <= 0) {   // no iteration at all: X0 is the answer, untouched; status and getInfo of a cold solve that was given no iteration
+        p.flops_performed_all += p.flops_performed;
+        p.residuum_reached = std::sqrt(1e300);
+        return TFQMRGPU_STATUS_MAX_ITERATIONS;
+    }
+    hipStream_t const s = (hipStream_t)h.stream;
+    size_t const S = align256(p.S);
+    if (auto const st = p.warm.reserve(std::max<size_t>(2 * S, 256))) return st;
+    char* const X0 = p.warm.as<char>();
+    char* const R = X0 + S;
+    DevPlan const d = resolve(p);
+    {   // R from the caller's A, before precond_prepare scales the A in the buffer (or brings it up to date with pending patches: the kept copy has them)
+        DevPlan dA = d; dA.A = const_cast<void*>(callersA);
+        spmm_apply(dA, d.x, d.v9, s);
+        if (!warm_residual_launch(d, d.v9, X0, R, tol, maxIt, s)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    }
+    if (auto const st = precond_prepare(h, p)) return st;           // (x has not been written yet)
+    p.warmR = R;                                                    // resolve(): DevPlan::R for this solve
+    auto const st = run_tfqmr(h, p, tol, maxIt, TFQMRGPU_STATUS_SUCCESS, 1., o);
+    p.warmR = nullptr;
+    if (st) {   // the driver failed on the way: x is a partial correction at best.  X0 goes back, as far as the device still takes a copy
+        (void)hipMemcpyAsync(d.x, X0, p.S, hipMemcpyDeviceToDevice, s);
+        return st;
+    }
+    Ctl const& last = o.last;
+    FlopModel const fm(p);
+    // the correction solve (its set-up norm is |r|^2 of the residual pass) + the product A X0 + |b|^2 + the subtraction and the update
+    p.flops_performed = fm.solve(last) + fm.fMult + fm.fNrm + 4. * p.nnzbX * p.LM * p.LN;
+    if (auto const st2 = precond_back(h, p)) return st2;            // D := M^-1 Y, also after max iterations or a breakdown
+    if (!warm_update_launch(d, X0, s)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    p.flops_performed_all += p.flops_performed;
+    p.residuum_reached = std::sqrt(last.residual2_reached);
+    p.iterations_needed = (1 == last.state) ? last.iterations_needed : maxIt;
+    switch (last.state) {
+        case 1: return TFQMRGPU_STATUS_SUCCESS;
+        case 2: return TFQMRGPU_STATUS_BREAKDOWN;
+        default: return TFQMRGPU_STATUS_MAX_ITERATIONS;
+    }
+}
+
+tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt) {
+    reset_results(p, maxIt);
     if ('m' == p.precision) return run_mixed(h, p, tol, maxIt);
     // what this rank can tell before it touches the device
     tfqmrgpuStatus_t early = TFQMRGPU_STATUS_SUCCESS;

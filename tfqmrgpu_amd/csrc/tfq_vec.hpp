@@ -54,4 +54,11 @@ void leak_map_launch(DevPlan const& d, void const* A, uint32_t nPos, uint32_t co
 void drop_cost_launch(DevPlan const& d, void const* A, uint32_t nX, uint32_t const* start, uint32_t const* aOf, uint32_t const* xOf,
     double* cost, double* weight, hipStream_t s);
 
+// warm start (tfq_warm.hip; tfqmrgpuExt_solveFrom).  X0, R: X-shaped vectors of the plan's storage type, block and element order; Y = A * x.
+// In front of the correction solve: X0 := x, R := (B under X, or 0) - Y, and the set-up that VEC_SETUP leaves to whoever brings d.R: tau = |r|^2,
+// 1 / |b|^2, rho = 1, every other scalar 0, the fold counters and the control block.  Writes d.pz (chunk records), the scalars, X0 and R
+bool warm_residual_launch(DevPlan const& d, void const* Y, void* X0, void* R, double tol, int maxIt, hipStream_t s);
+// behind it: x := X0 + x.  false (both): no instance for this block shape
+bool warm_update_launch(DevPlan const& d, void const* X0, hipStream_t s);
+
 } // namespace tfq
