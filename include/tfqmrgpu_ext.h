@@ -607,6 +607,47 @@ tfqmrgpuStatus_t tfqmrgpuExt_shrinkPattern(tfqmrgpuBsrsvPlan_t plan,
 tfqmrgpuStatus_t tfqmrgpuExt_solveFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
     double threshold, int maxIterations);
 
+/* ---- (15) carry A, B and X from one plan to another on the device ------------------------------------------------------------------- */
+/* Every turn of the loop of sections 10 to 14 -- residual, truncationLeak, leakMap and growPattern, dropCost and shrinkPattern,
+ * createPlan, solveFrom -- ends in a NEW plan, while the operands sit in the old plan's buffer.  carry copies one operand of `src` into
+ * `dst` device to device, through a block map, and zero-fills the blocks that are new: no host transfer of values, no scratch memory of
+ * the caller's, every byte moved once.
+ *
+ * The map: block n of operand `var` of dst becomes block oldBlock[n] of the same operand of src; oldBlock[n] == -1 makes it a zero
+ *   block.  n counts in dst's caller block order (the order of the bsrColInd array given to createPlan), oldBlock[n] in src's; both are
+ *   0-based whatever indexOffset: exactly what tfqmrgpuGrownPattern_t::oldBlock of growPattern and shrinkPattern holds.  nBlocks must be
+ *   dst's nnzb of that operand.  oldBlock == NULL is the identity and needs equal nnzb in both plans (A and B: their patterns do not
+ *   change in the loop).  A source block may be named more than once.  The map is the caller's claim: block rows and block columns are
+ *   not compared.
+ * Source values.  'X': what getMatrix('X') of src would return at that moment -- the back-transformed solution after a preconditioned
+ *   solve, or the caller's X after setMatrix('X') / setBlocks('X').  'B': what the last setMatrix('B') / setBlocks('B') left.  'A': the
+ *   caller's A, chosen as in section 10: the buffer's A, or the kept copy of section 9 while the buffer holds A M^-1; patches of
+ *   setBlocks('A') that no set-up has seen yet are included.
+ * Effects on dst: exactly those of a whole setMatrix(var).  For 'A': A counts as set, the preconditioner is stale (the next solve sets it
+ *   up again), the float floor of an 'm' plan and pending patches are forgotten, and an 'm' plan gets both its copies of A, the double
+ *   one and the float one.  src is only read.
+ * Precisions: 'z', 'c' and 'm' on either side, in every combination.  The operand is read and written in each plan's storage precision
+ *   (an 'm' plan stores X, B and A in double): float -> double is exact, double -> float rounds to nearest, once.  So a cheap 'c' solve on
+ *   a coarse pattern can seed a 'z' plan for solveFrom.  Each plan keeps its own element order inside a block; the call translates.
+ * LM and LN must be the same in both plans.
+ * Stream: asynchronous on the handle's stream; work of src that is pending on another stream is the caller's to wait for.  Uploading the
+ *   list synchronises that stream once (A and B without a list upload nothing).  Do not call it during a solve of either plan.
+ * Memory: the device copy of the list is library-owned memory of dst, grown on demand and released by destroyPlan.  bufferSize and the
+ *   buffer layout do not change; a plan that never makes the call allocates nothing and runs the launches it ran before.
+ * Deterministic: a copy.  Two calls give the same bits.
+ * All checks come before the first device call, in this order: handle, dst or src NULL, or dst == src: TFQMRGPU_POINTER_INVALID; either
+ *   plan without bufferSize: TFQMRGPU_UNDOCUMENTED_ERROR; an unknown var: the status of setMatrix (TFQMRGPU_VARIABLENAME_UNKNOWN with the
+ *   key character var); LM or LN differ: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'L'; nBlocks is not dst's nnzb, the list is
+ *   NULL and the two nnzb differ, an entry is below -1, or an entry is at or above src's nnzb: TFQMRGPU_UNDOCUMENTED_ERROR with the key
+ *   character var; (nBlocks == 0 with nnzb 0 returns success HERE and touches nothing;) either plan without a buffer:
+ *   TFQMRGPU_POINTER_INVALID; for 'A' the source checks of section 10 on src: a user-defined operator: TFQMRGPU_NO_IMPLEMENTATION; A never
+ *   set whole: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A'; A scaled and no copy kept: TFQMRGPU_NO_IMPLEMENTATION.  After any
+ *   error nothing has been written, not in either buffer and not in the plan state.
+ * Several ranks (section 4): local to the rank's own two plans, no collective. */
+tfqmrgpuStatus_t tfqmrgpuExt_carry(tfqmrgpuHandle_t handle,
+    tfqmrgpuBsrsvPlan_t dst, tfqmrgpuBsrsvPlan_t src, char var /* 'A', 'B', 'X' */,
+    int32_t nBlocks, int32_t const *oldBlock /* HOST [nBlocks], or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_setPreconditioner", "tfqmrgpuExt_getPreconditioner", "tfqmrgpuExt_setBlocks", "tfqmrgpuExt_getBlocks",
     "tfqmrgpuExt_keepOperator", "tfqmrgpuExt_residual", "tfqmrgpuExt_truncationLeak", "tfqmrgpuExt_leakUnits",
     "tfqmrgpuExt_leakMap", "tfqmrgpuExt_growPattern", "tfqmrgpuExt_freeGrownPattern",
-    "tfqmrgpuExt_dropCost", "tfqmrgpuExt_shrinkPattern", "tfqmrgpuExt_solveFrom",
+    "tfqmrgpuExt_dropCost", "tfqmrgpuExt_shrinkPattern", "tfqmrgpuExt_solveFrom", "tfqmrgpuExt_carry",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -161,6 +161,7 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_shrinkPattern.argtypes = [P, C.c_uint64, P, C.POINTER(GrownPattern)]
     lib.tfqmrgpuExt_freeGrownPattern.restype = None
     lib.tfqmrgpuExt_solveFrom.argtypes = [P, P, C.c_double, I]
+    lib.tfqmrgpuExt_carry.argtypes = [P, P, P, C.c_char, C.c_int32, P]
     return lib
 
 
@@ -385,6 +386,27 @@ class Solver:
         Returns the raw status as solve does"""
         st = lib.tfqmrgpuExt_solveFrom(self.handle, self.plan, threshold, max_iterations)
         return _check(st, "tfqmrgpuExt_solveFrom", allowed=(0, 6, 9))
+
+    # -- operands from another plan (tfqmrgpu_ext.h section 15) ---------------------------------------------
+    def carry_from(self, src, var, old_block=None):
+        """operand `var` ('A', 'B' or 'X') of this plan := that of the Solver `src`, device to device: block n becomes block
+        old_block[n] of src (both in the caller's block orders, 0-based), -1 a zero block -- the oldBlock of grow_pattern and
+        shrink_pattern; None: the identity, which needs as many blocks on either side.  Acts on this plan as set_matrix(var) does; the
+        two plans may differ in precision.  Asynchronous on this Solver's stream; returns the raw status"""
+        n = {"a": self.problem.nnzbA, "b": self.problem.nnzbB, "x": self.problem.nnzbX}.get(var.lower(), 0)
+        idx = None
+        if old_block is not None:
+            idx = _i32(old_block).reshape(-1)
+            n = len(idx)
+        st = lib.tfqmrgpuExt_carry(self.handle, self.plan, src.plan, var.encode(), n, None if idx is None else C.c_void_p(idx.ctypes.data))
+        return _check(st, "tfqmrgpuExt_carry('%s')" % var)
+
+    def adopt(self, src, old_block_x=None):
+        """A, B and X of the Solver `src` into this plan without a host transfer of values: A and B block for block (their patterns
+        are those of src), X through old_block_x (carry_from).  What follows a grown or shrunk pattern and precedes solve_from"""
+        self.carry_from(src, "A")
+        self.carry_from(src, "B")
+        return self.carry_from(src, "X", old_block_x)
 
     def set_operator(self, multiply):
         """user-defined operator (tfqmrgpu_ext.h section 5): multiply(Y_ptr, X_ptr, colindx_ptr, nnzbX, nCols, lm, ln,

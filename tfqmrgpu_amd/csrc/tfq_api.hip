@@ -17,6 +17,7 @@
 #include "tfq_order.hpp"
 #include "tfq_vec.hpp"
 #include "tfq_switch.hpp"
+#include "tfq_carry.hpp"
 
 using namespace tfq;
 
@@ -1116,6 +1117,55 @@ tfqmrgpuStatus_t tfqmrgpuExt_getBlocks(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPla
     int32_t const nBlocks, int32_t const* blocks, void* values, char const precision, char const trans, tfqmrgpuDataLayout_t const layout)
 {
     return operand_transfer(handle, plan, var, true, nBlocks, blocks, values, precision, trans, layout, true);
+}
+
+// ---- carry an operand from one plan to another, device to device (tfqmrgpu_ext.h section 15) ---------------------------------------------
+// The checks and the composed list are host code (tfq_carry_host.cpp), the copy is one launch of k_carry (tfq_carry.hip) over the
+// destination window -- two for the A of an 'm' destination, which keeps a double and a float copy.  What the call does to the
+// destination plan is what a whole setMatrix(var) does
+tfqmrgpuStatus_t tfqmrgpuExt_carry(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t dst, tfqmrgpuBsrsvPlan_t src, char const var,
+    int32_t const nBlocks, int32_t const* oldBlock)
+{
+    auto d = asPlan(dst); auto sp = asPlan(src); auto h = (Handle*)handle;
+    if (!h || !d || !sp || d == sp) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == d->LM || 0 == sp->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);   // bufferSize has not been called
+    Operand od{}, os{};
+    if (!operand_of(*d, var, od) || !operand_of(*sp, var, os)) return err(TFQMRGPU_VARIABLENAME_UNKNOWN, __LINE__ % 10000, var);
+    if (d->LM != sp->LM || d->LN != sp->LN) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'L');
+    if (!carry_map_ok(nBlocks, oldBlock, od.nnzb, os.nnzb)) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
+    if (0 == od.nnzb) return TFQMRGPU_STATUS_SUCCESS;               // nothing to carry: nothing is touched
+    if (nullptr == d->buffer || nullptr == sp->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    bool const isA = (0 == od.which), isX = (2 == od.which);
+    if (isA) if (auto const st = operands_ready(*sp, true)) return st;   // the source checks of section 10, in its order
+
+    // the list in the stored block orders: X-shaped vectors lie in each plan's internal order, A and B in the caller's.  A and B without a
+    // list are the identity there too and need no list on the device
+    hipStream_t const s = (hipStream_t)h->stream;
+    uint32_t const* list = nullptr;
+    if (oldBlock || isX) {
+        std::vector<uint32_t> composed;
+        try { carry_compose(composed, od.nnzb, oldBlock, isX ? d->i2u.data() : nullptr, isX ? sp->u2i.data() : nullptr); }
+        catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+        if (auto const st = d->carryList.reserve(composed.size() * 4)) return st;
+        // stream order keeps this copy behind the launches of an earlier call; `composed` is a local: wait for the copy
+        TFQ_HIP(hipMemcpyAsync(d->carryList.ptr, composed.data(), composed.size() * 4, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        list = d->carryList.as<uint32_t>();
+    }
+
+    // where the operand lives on either side: the buffer ('m': its double side), for the source A the caller's A (callers_a)
+    bool const dMixed = ('m' == d->precision);
+    DevPlan const dd = dMixed ? resolveZ(*d) : resolve(*d);
+    DevPlan const ds = ('m' == sp->precision) ? resolveZ(*sp) : resolve(*sp);
+    CarrySide const from{ isA ? const_cast<void*>(callers_a(*sp, ds)) : isX ? ds.x : ds.B, ds.dbl, ds.ilv };
+    CarrySide const to{ isA ? dd.A : isX ? dd.x : dd.B, dd.dbl, dd.ilv };
+    if (isA) a_named(*d);
+    bool ok = carry_launch(to, from, list, od.nnzb, d->LM, od.nC, s);
+    if (ok && isA && dMixed) ok = carry_launch(CarrySide{d->buffer + d->wA.offset, false, d->ilv}, from, list, od.nnzb, d->LM, od.nC, s);   // the float A of the inner solves
+    tfqmrgpuStatus_t st = ok ? TFQMRGPU_STATUS_SUCCESS : TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+    if (ok && hipSuccess != hipGetLastError()) st = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
+    if (isA) a_set_whole(*d, !st);
+    return st;
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_setReduceCallback(tfqmrgpuHandle_t handle, tfqmrgpuReduceMax_t fn, void* ctx) {

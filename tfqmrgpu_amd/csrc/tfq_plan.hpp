@@ -163,6 +163,16 @@ void drop_listing(DropListing& out, uint32_t nnzbX, size_t nPairs, uint32_t cons
 int shrink_pattern(GrownPattern& out, uint32_t nRows, uint32_t nnzbX, uint32_t const* rowOfX, uint32_t const* colOfX,
     int32_t const* callersCol, int indexOffset, uint8_t const* hasB, uint64_t nDrop, int32_t const* drop);
 
+// tfqmrgpuExt_carry (tfqmrgpu_ext.h section 15): the caller's block map between two plans (tfq_carry_host.cpp)
+constexpr uint32_t kCarryZero = 0xffffffffu;   // an entry of the composed list: this block of the destination becomes zero
+// nBlocks is the destination's block count; without a list (the identity) both operands have as many blocks; every entry is -1 (a zero
+// block) or a block of the source
+bool carry_map_ok(int64_t nBlocks, int32_t const* oldBlock, uint32_t nnzbDst, uint32_t nnzbSrc);
+// out[n] = the STORED block of the source that stored block n of the destination takes, or kCarryZero.  dstI2U: the caller's index of
+// every stored block of the destination, srcU2I: the stored index of every block of the source in the caller's order (nullptr: stored
+// in the caller's order, as A and B are); oldBlock == nullptr: the identity.  The map has passed carry_map_ok
+void carry_compose(std::vector<uint32_t>& out, uint32_t nnzbDst, int32_t const* oldBlock, uint32_t const* dstI2U, uint32_t const* srcU2I);
+
 struct Handle {
     void* stream = nullptr;               // hipStream_t
     // multi-GPU stopping test (tfqmrgpu_ext.h section 4)
@@ -287,6 +297,9 @@ struct Plan {
     // by the first call (sized by the block shape, and holding values of the buffer they were taken from: released by bufferSize and setBuffer)
     DevMem warm;
     void* warmR = nullptr;             // not null only while a warm solve runs: resolve() hands it to the driver as DevPlan::R
+    // tfqmrgpuExt_carry (tfqmrgpu_ext.h section 15), on the DESTINATION plan: library-owned device copy of the composed block list
+    // (tfq_carry_host.cpp: carry_compose), grown on demand
+    DevMem carryList;
 
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;
