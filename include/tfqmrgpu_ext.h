@@ -587,7 +587,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_shrinkPattern(tfqmrgpuBsrsvPlan_t plan,
  *   against |r|, as in a cold solve of the correction system.
  * maxIterations <= 0: X = X0 is left untouched; the status is TFQMRGPU_STATUS_MAX_ITERATIONS, as solve returns for it.
  * tfqmrgpu_bsrsv_solve on the same plan, before or after, is bit for bit the solve it was: the same launches, the same buffer.
- * Precisions: 'z' and 'c'.  'm': TFQMRGPU_NO_IMPLEMENTATION -- the refinement has a cycle 0 and a |b|^2 bookkeeping of its own; a follow-up.
+ * Precisions: 'z' and 'c'.  'm': TFQMRGPU_NO_IMPLEMENTATION -- the refinement has a cycle 0 and a |b|^2 bookkeeping of its own: section 16.
  * Preconditioner (section 7): supported.  R needs the caller's A: the buffer's while it has not been scaled -- R is formed first, then
  *   the set-up scales A --, the kept copy (section 9) once it has, patches of setBlocks('A') that no set-up has seen yet included, as in
  *   section 10.  The correction solve runs on A M^-1; its result is back-transformed into D before X0 is added.  Scaled and no copy kept:
@@ -647,6 +647,57 @@ tfqmrgpuStatus_t tfqmrgpuExt_solveFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPla
 tfqmrgpuStatus_t tfqmrgpuExt_carry(tfqmrgpuHandle_t handle,
     tfqmrgpuBsrsvPlan_t dst, tfqmrgpuBsrsvPlan_t src, char var /* 'A', 'B', 'X' */,
     int32_t nBlocks, int32_t const *oldBlock /* HOST [nBlocks], or NULL */);
+
+/* ---- (16) mixed-precision warm start: refine from the X in the plan ------------------------------------------------------------------ */
+/* The loop of sections 8 to 15 ends every turn in a solve that has a good X at hand, and the fastest solver, the mixed-precision plan
+ * ('m': float tfQMR inside a refinement in double), was the one that could not take part: solveFrom refuses it (section 14), and solve
+ * starts the refinement from zero and throws away the digits X already has.  refineFrom runs the refinement from X0, the X in the plan.
+ *
+ * 'z' and 'c' plans: the call IS tfqmrgpuExt_solveFrom (section 14), call for call -- the same statuses, the same bits --, so that one
+ *   call serves a loop in any precision.  What follows describes 'm' plans.
+ * X0 is what getMatrix('X') would return at that moment: the last solution (back-transformed on a preconditioned plan, section 7), or
+ *   what setMatrix('X') / setBlocks('X') / carry (section 15) brought.  It is read from the plan's double copy.
+ * It runs as a correction refinement: R = B - A X0, truncated to the pattern of X as every product is, formed ONCE, in double, from the
+ *   caller's A in its double copy; then the refinement of solve on A D = R from D = 0 -- per cycle r = R - A D in double (cycle 0: r = R),
+ *   A d = r by the float tfQMR driver and its kernels, unchanged, D += d in double --; then X = X0 + D in double.
+ * threshold and getInfo keep the meaning they have after solve on an 'm' plan: max over the right-hand sides of |B - A X| / |B| in
+ *   double.  |B|^2 per right-hand side comes from B, not from the first cycle's |r|^2.  A right-hand side with b = 0 has nothing to be
+ *   relative to and is graded against its own |r0|, as in section 14.  getInfo: iterations is the sum of the float iterations,
+ *   residuum_reached the final residual; flops_performed additionally counts the product A X0, the residual pass and the update.
+ * getRefinementHistory: residual[0] is |B - A X0| / |B| in front of the first float solve -- no longer 1 --, the last entry is the
+ *   final residual, iterations[i] are as after solve.  getBoundHistory holds the bounds of the float solves, as after solve.
+ * X0 already converged -- the first residual is at or below threshold --: TFQMRGPU_STATUS_SUCCESS with 0 iterations, and X keeps X0
+ *   bit for bit: no float solve, no back transform, no update.
+ * maxIterations <= 0: X = X0 is left untouched bit for bit; the status is TFQMRGPU_STATUS_MAX_ITERATIONS and getInfo is as solveFrom
+ *   leaves it in that case.
+ * A right-hand side whose R is exactly zero keeps its X0 bit for bit through every cycle: a right-hand side only ever sees itself, so
+ *   its D stays exactly zero, and the update keeps X0's bits where D is 0.  It is neither a breakdown nor a NaN and takes no part in
+ *   the status.
+ * Stagnation and breakdown are reported as solve reports them on an 'm' plan: two cycles without a factor 2 end the refinement with
+ *   TFQMRGPU_STATUS_MAX_ITERATIONS (TFQMRGPU_STATUS_BREAKDOWN if the last float solve broke down).  X is then X0 + the D reached.
+ * tfqmrgpu_bsrsv_solve on the same plan, before or after, is bit for bit the solve it was: the same launches, the same buffer layout,
+ *   the same bufferSize.  refineFrom reads the float floor that solve remembers per plan for its first cycle and does NOT write it: a
+ *   later solve does not depend on whether a refineFrom ran in between.
+ * Preconditioner (section 7): supported, in the order of section 14.  R is formed first and needs the caller's A: the buffer's double A
+ *   while it has not been scaled, the double part of the kept copy (section 9) once it has, patches of setBlocks('A') that no set-up
+ *   has seen yet included, as in section 10.  Then the set-up; the cycles run on A M^-1; D is back-transformed before X0 is added.
+ *   Scaled and no copy kept: TFQMRGPU_NO_IMPLEMENTATION, as residual.
+ * A user-defined operator (section 5): TFQMRGPU_NO_IMPLEMENTATION.  Several ranks (section 4): TFQMRGPU_NO_IMPLEMENTATION on every
+ *   rank, through the mixed solve's own first collective -- the max-reduction of three doubles with the third value set; exactly one
+ *   collective, so that all ranks leave together.  ('z' and 'c' plans: the vote of section 14, by forwarding.)
+ * Deterministic: one work group per chunk and per block column of the plan's own tables, every sum in a fixed order, no atomics.  Two
+ *   calls from the same X0 give the same bits.
+ * Memory: X0 and R, two X-shaped vectors of doubles, are device memory that the library owns -- the allocation of section 14, sized
+ *   for doubles --, allocated by the first call, released by destroyPlan, bufferSize and setBuffer.  A X0 lives in the work vectors
+ *   that the refinement uses for A x (v4 ... v7).  A plan that never makes the call allocates nothing and runs the launches it ran before.
+ * Stream: asynchronous on the handle's stream; it synchronises where solve does on an 'm' plan.  Do not call it during a solve.
+ * All checks come before the first device call, in the order of section 14: plan / handle pointers: TFQMRGPU_POINTER_INVALID; no
+ *   bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; no buffer: TFQMRGPU_POINTER_INVALID; a user-defined operator:
+ *   TFQMRGPU_NO_IMPLEMENTATION; A never set whole on this buffer: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A'; A scaled and no
+ *   copy kept: TFQMRGPU_NO_IMPLEMENTATION.  After any error nothing has been written: not X, not the results of the last solve, not
+ *   the float floor. */
+tfqmrgpuStatus_t tfqmrgpuExt_refineFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double threshold, int maxIterations);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_keepOperator", "tfqmrgpuExt_residual", "tfqmrgpuExt_truncationLeak", "tfqmrgpuExt_leakUnits",
     "tfqmrgpuExt_leakMap", "tfqmrgpuExt_growPattern", "tfqmrgpuExt_freeGrownPattern",
     "tfqmrgpuExt_dropCost", "tfqmrgpuExt_shrinkPattern", "tfqmrgpuExt_solveFrom", "tfqmrgpuExt_carry",
+    "tfqmrgpuExt_refineFrom",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -162,6 +163,7 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_freeGrownPattern.restype = None
     lib.tfqmrgpuExt_solveFrom.argtypes = [P, P, C.c_double, I]
     lib.tfqmrgpuExt_carry.argtypes = [P, P, P, C.c_char, C.c_int32, P]
+    lib.tfqmrgpuExt_refineFrom.argtypes = [P, P, C.c_double, I]
     return lib
 
 
@@ -386,6 +388,13 @@ class Solver:
         Returns the raw status as solve does"""
         st = lib.tfqmrgpuExt_solveFrom(self.handle, self.plan, threshold, max_iterations)
         return _check(st, "tfqmrgpuExt_solveFrom", allowed=(0, 6, 9))
+
+    def refine_from(self, threshold, max_iterations):
+        """tfqmrgpu_ext.h section 16: on a mixed-precision plan ('m') the refinement started from the X in the plan -- the float solves
+        work on the correction to it, refinement_history()[0] is the residual of that X instead of 1; on a 'z' or 'c' plan it is
+        solve_from.  Returns the raw status as solve does"""
+        st = lib.tfqmrgpuExt_refineFrom(self.handle, self.plan, threshold, max_iterations)
+        return _check(st, "tfqmrgpuExt_refineFrom", allowed=(0, 6, 9))
 
     # -- operands from another plan (tfqmrgpu_ext.h section 15) ---------------------------------------------
     def carry_from(self, src, var, old_block=None):

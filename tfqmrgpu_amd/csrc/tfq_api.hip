@@ -808,10 +808,22 @@ tfqmrgpuStatus_t tfqmrgpuExt_solveFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPla
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
     // the order of section 10, with the precision between the operator and A: no buffer | user-defined operator | 'm' | A never set | A scaled and not kept
     tfqmrgpuStatus_t early = operands_ready(*p, false);
-    if (!early && 'm' == p->precision) early = TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // run_mixed has its own cycle 0 and |b|^2: a follow-up
+    if (!early && 'm' == p->precision) early = TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // run_mixed has its own cycle 0 and |b|^2: tfqmrgpuExt_refineFrom
     if (!early) early = operands_ready(*p, true);
     void const* const a = early ? nullptr : callers_a(*p, resolve(*p));
     return run_solve_from(*h, *p, threshold, maxIterations, a, early);
+}
+
+// ---- mixed-precision warm start: refine from the X in the plan (tfqmrgpu_ext.h section 16) ---------------------------------------------
+tfqmrgpuStatus_t tfqmrgpuExt_refineFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double const threshold, int const maxIterations) {
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
+    if ('m' != p->precision) return tfqmrgpuExt_solveFrom(handle, plan, threshold, maxIterations);   // 'z', 'c': section 14, call for call
+    // the order of section 14 without its precision check: no buffer | user-defined operator | A never set | A scaled and not kept
+    tfqmrgpuStatus_t const early = operands_ready(*p, true);
+    void const* const a = early ? nullptr : callers_a(*p, resolveZ(*p));   // the double A: the buffer's, or the double part of the kept copy
+    return run_refine_from(*h, *p, threshold, maxIterations, a, early);
 }
 
 // ---- truncation leak: what A X puts outside the pattern of X (tfqmrgpu_ext.h sections 11 and 12) --------------------------------------

@@ -84,7 +84,9 @@ struct RefineArgs {
     int cycle;                                 // 0: x = 0, r = b (Yz is not read)
     double innerTol; int innerMaxIt;
 };
-void launch_refine_residual(RefineArgs const& r, hipStream_t s);   // r = b - A x -> R (float), |r|^2 records, inner solve set up, refine[]
+// warm (tfqmrgpuExt_refineFrom, tfq_solve.cpp: run_refine_from): the refinement runs on the correction system A D = R.  Bz is then the
+// X-shaped double vector R (block for block under xz, which holds D; no bOfX), and bn2z has been preset (tfq_warm.hip) and is only read
+void launch_refine_residual(RefineArgs const& r, hipStream_t s, bool warm = false);   // r = b - A x -> R (float), |r|^2 records, inner solve set up, refine[]
 void launch_refine_update(RefineArgs const& r, hipStream_t s);     // x (double) += x (float) of the inner solve
 
 // ---- shadow vector -------------------------------------------------------------------------------

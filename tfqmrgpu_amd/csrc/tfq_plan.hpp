@@ -294,7 +294,8 @@ struct Plan {
     DropListing drop;
     DevMem dropDev;
     // tfqmrgpuExt_solveFrom (tfqmrgpu_ext.h section 14): library-owned [X0 | R], two X-shaped vectors of the plan's storage type, allocated
-    // by the first call (sized by the block shape, and holding values of the buffer they were taken from: released by bufferSize and setBuffer)
+    // by the first call (sized by the block shape, and holding values of the buffer they were taken from: released by bufferSize and setBuffer).
+    // tfqmrgpuExt_refineFrom (section 16) on an 'm' plan: the same two vectors, of doubles
     DevMem warm;
     void* warmR = nullptr;             // not null only while a warm solve runs: resolve() hands it to the driver as DevPlan::R
     // tfqmrgpuExt_carry (tfqmrgpu_ext.h section 15), on the DESTINATION plan: library-owned device copy of the composed block list

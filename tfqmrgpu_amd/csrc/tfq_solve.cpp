@@ -405,35 +405,48 @@ static CycleAsk next_cycle(double tol, double res2, int cycle, double bestGain, 
 // A d = r solved by the complex<float> tfQMR (its kernels unchanged; the right-hand side is the X-shaped R), x += d in double.  The
 // float iteration moves half the bytes of the double one; a cycle gains the digits a float solve delivers, the refinement's own
 // stopping test is max_rhs |b - A x| / |b| <= threshold in double.  maxIterations bounds the SUM of the inner iterations.
-static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt) {
+// ONE failure protocol for several ranks: the first collective of a mixed-precision solve is the refinement's
+// max-reduction of {max |r|^2/|b|^2, a value is not finite, a rank failed} (3 doubles) -- not the vote of run_tfqmr (2 doubles).  A
+// rank that cannot start (no buffer; a user-defined operator, which 'm' plans refuse) therefore takes part in THAT reduction with
+// the third value set: its peers read it in their cycle 0 and every rank leaves at the same collective, the refusing one with
+// its own status, the others with "a peer failed".  A rank that fails later, between two collectives, hands its failure to the
+// next one it would have entered: the vote of the inner solve (`early`), or the next refinement reduction (`mine`).
+static tfqmrgpuStatus_t leave_marked(Handle& h, tfqmrgpuStatus_t st) {
+    hipStream_t const s = (hipStream_t)h.stream;
+    if (!several_ranks(h)) return st;
+    if (!h.voteBuf) return st;                           // (allocated with the communicator / callback; without it no collective can be entered)
+    double const mark[3] = { 0., 0., 1. };
+    if (hipSuccess != hipMemcpyAsync(h.voteBuf.ptr, mark, sizeof mark, hipMemcpyHostToDevice, s)) return st;
+    if (hipSuccess != hipStreamSynchronize(s)) return st;
+    (void)reduce_over_ranks(h, h.voteBuf.as<double>(), 3, s);
+    (void)hipStreamSynchronize(s);
+    return st;
+}
+
+// The warm form of the refinement (tfqmrgpuExt_refineFrom; run_refine_from below has formed R, saved X0, preset |b|^2 in wBn2z and run
+// precond_prepare): it runs on the correction system A D = R.  x holds X0 until the first update writes D over it -- cycle 0's update does not
+// read x --, so a refinement that leaves before any update leaves X0 where it is and skips the back transform.  Plan::mixedFloor is read, not written.
+struct MixedWarm {
+    double const* R;          // the X-shaped right-hand side, double, element order ilvZ
+    bool updated = false;     // an update has run: x holds D (in Y space on a preconditioned plan until precond_back)
+    bool finished = false;    // the refinement has come to its own end (any status): x is X0 or a D that can be added to it
+};
+
+static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt, MixedWarm* const warm = nullptr) {
     hipStream_t const s = (hipStream_t)h.stream;
     SolveOutcome o;
     bool const multi = several_ranks(h);
-    // ONE failure protocol for several ranks: the first collective of a mixed-precision solve is the refinement's
-    // max-reduction of {max |r|^2/|b|^2, a value is not finite, a rank failed} (3 doubles) -- not the vote of run_tfqmr (2 doubles).  A
-    // rank that cannot start (no buffer; a user-defined operator, which 'm' plans refuse) therefore takes part in THAT reduction with
-    // the third value set: its peers read it in their cycle 0 and every rank leaves at the same collective, the refusing one with
-    // its own status, the others with "a peer failed".  A rank that fails later, between two collectives, hands its failure to the
-    // next one it would have entered: the vote of the inner solve (`early`), or the next refinement reduction (`mine`).
-    auto const leave_marked = [&](tfqmrgpuStatus_t st) -> tfqmrgpuStatus_t {
-        if (!multi) return st;
-        if (!h.voteBuf) return st;                           // (allocated with the communicator / callback; without it no collective can be entered)
-        double const mark[3] = { 0., 0., 1. };
-        if (hipSuccess != hipMemcpyAsync(h.voteBuf.ptr, mark, sizeof mark, hipMemcpyHostToDevice, s)) return st;
-        if (hipSuccess != hipStreamSynchronize(s)) return st;
-        (void)reduce_over_ranks(h, h.voteBuf.as<double>(), 3, s);
-        (void)hipStreamSynchronize(s);
-        return st;
-    };
-    if (!p.buffer)  return leave_marked(TFQ_ERR(TFQMRGPU_POINTER_INVALID));
-    if (p.opFn)     return leave_marked(TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION));  // user-defined operators: 'z' and 'c' only
-    if (auto const st = precond_prepare(h, p)) return leave_marked(st);
+    if (!warm) {
+        if (!p.buffer)  return leave_marked(h, TFQ_ERR(TFQMRGPU_POINTER_INVALID));
+        if (p.opFn)     return leave_marked(h, TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION));  // user-defined operators: 'z' and 'c' only
+        if (auto const st = precond_prepare(h, p)) return leave_marked(h, st);
+    }
     DevPlan const d = resolve(p), dz = resolveZ(p);
     FlopModel const fm(p);
     RefineArgs a{};
-    a.d = d; a.xz = (double*)dz.x; a.Bz = (double const*)dz.B; a.Yz = (double const*)d.v4;   // A x lives in v4 ... v7, free between two inner solves
+    a.d = d; a.xz = (double*)dz.x; a.Bz = warm ? warm->R : (double const*)dz.B; a.Yz = (double const*)d.v4;   // A x lives in v4 ... v7, free between two inner solves
     a.bn2z = (double*)(p.buffer + p.wBn2z.offset); a.refine = (double*)(p.buffer + p.wRefine.offset); a.ilvZ = p.ilvZ;
-    if (maxIt <= 0) TFQ_HIP(hipMemsetAsync(a.xz, 0, p.wXz.bytes, s), TFQMRGPU_STATUS_LAUNCH_FAILED)   // no iteration at all: x = 0 is the answer
+    if (maxIt <= 0 && !warm) TFQ_HIP(hipMemsetAsync(a.xz, 0, p.wXz.bytes, s), TFQMRGPU_STATUS_LAUNCH_FAILED)   // no iteration at all: x = 0 is the answer
     int used = 0, strikes = 0, lastIts = 0;
     bool brokeDown = false, firstStalled = false;
     double res2 = 1e300, prev2 = 1e300, bestGain = 1.;
@@ -444,7 +457,7 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt) {
     for (int cycle = 0; ; ++cycle) {
         if (cycle > 0) { spmm_apply(dz, dz.x, (void*)a.Yz, s); p.flops_performed += fm.fMult; }
         a.cycle = cycle; a.innerTol = 1e-4; a.innerMaxIt = std::max(0, maxIt - used);
-        launch_refine_residual(a, s);
+        launch_refine_residual(a, s, nullptr != warm);
         p.flops_performed += fm.fNrm;
         if (!mine && hipSuccess != hipGetLastError()) mine = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
         // (k_refine_max has written {.., .., 0}: this rank's mark behind it, on the same stream)
@@ -465,7 +478,7 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt) {
         if (cycle > 0 && prev2 > 0. && prev2 < 1e299) { lastGain = std::sqrt(res2 / prev2); bestGain = std::min(bestGain, lastGain); }   // what the last cycle delivered
         // (r04) the float floor of THIS plan: where its first float solve gave up by itself (Ctl::stallStop).  The next solve of the plan -- same A, new B, the
         // use the reference's README names (:97-104) -- asks its first cycle for twice that instead of searching for it again (P2: 9 -> 7 iterations)
-        if (1 == cycle && firstStalled && lastGain < 1.) p.mixedFloor = lastGain;
+        if (1 == cycle && firstStalled && lastGain < 1. && !warm) p.mixedFloor = lastGain;   // (the floor belongs to cold solves: a later solve must not depend on a refineFrom in between)
         if (cycle > 0) {   // two cycles in a row gained less than a factor 2: give up (a breakdown of the last float solve is reported as one)
             strikes = (res2 > 0.25 * prev2) ? strikes + 1 : 0;
             if (strikes >= 2) { if (brokeDown) result = TFQMRGPU_STATUS_BREAKDOWN; break; }
@@ -491,13 +504,16 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt) {
         brokeDown = (2 == o.last.state);                                    // every right-hand side of this float solve broke down
         p.flops_performed += fm.solve(o.last) - fm.fNrm;                    // (|r|^2 of the set-up is the refinement's, counted above)
         launch_refine_update(a, s);
+        if (warm) warm->updated = true;
         p.flops_performed += 2. * p.nnzbX * p.LM * p.LN;
     }
+    if (!warm || warm->updated)                          // (warm and no update: x still holds X0, in X space)
     if (auto const st = precond_back(h, p)) return st;   // (every rank gets here: errors that one rank alone could see have left above, behind a collective)
     TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
     p.flops_performed_all += p.flops_performed;
     p.residuum_reached = std::sqrt(std::max(res2, 1.4e-76 * 1.4e-76));
     p.iterations_needed = (TFQMRGPU_STATUS_SUCCESS == result) ? used : maxIt;
+    if (warm) warm->finished = true;
     return result;
 }
 
@@ -561,6 +577,52 @@ tfqmrgpuStatus_t run_solve_from(Handle& h, Plan& p, double tol, int maxIt, void 
         case 2: return TFQMRGPU_STATUS_BREAKDOWN;
         default: return TFQMRGPU_STATUS_MAX_ITERATIONS;
     }
+}
+
+// The same for an 'm' plan (tfqmrgpu_ext.h section 16): the refinement of run_mixed, its float driver untouched, on the correction system.
+//   Y = A X0 (the caller's double A, one spmm_apply into v4 ... v7) | X0 := x, R := B - Y, |b|^2 -> wBn2z (tfq_warm.hip, all in double) | [A := A M^-1] |
+//   run_mixed on A D = R from D = 0: per cycle r = R - A D in double (cycle 0: r = R), A d = r in float, D += d in double | [D := M^-1 D] | x := X0 + D
+// D lives in the plan's double x: cycle 0's update writes it without reading what is there, which is X0 -- saved by then.  A refinement that ends
+// before any update (X0 meets the threshold) leaves x alone: no back transform, no update.
+tfqmrgpuStatus_t run_refine_from(Handle& h, Plan& p, double tol, int maxIt, void const* callersA, tfqmrgpuStatus_t early) {
+    // several ranks: refused (the residual pass has no reduction over ranks).  Through the mixed solve's own first collective, so that every rank leaves together
+    if (several_ranks(h)) return leave_marked(h, early ? early : TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION));
+    if (early) return early;
+    if ('m' != p.precision) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+    reset_results(p, maxIt);
+    if (maxIt <= 0) {   // no iteration at all: X0 is the answer, untouched; status and getInfo as run_solve_from leaves them
+        p.flops_performed_all += p.flops_performed;
+        p.residuum_reached = std::sqrt(1e300);
+        return TFQMRGPU_STATUS_MAX_ITERATIONS;
+    }
+    hipStream_t const s = (hipStream_t)h.stream;
+    size_t const Z = align256(p.wXz.bytes);
+    if (auto const st = p.warm.reserve(std::max<size_t>(2 * Z, 256))) return st;
+    char* const X0 = p.warm.as<char>();
+    char* const R = X0 + Z;
+    DevPlan const dz = resolveZ(p);
+    FlopModel const fm(p);
+    double const nReal = 2. * p.nnzbX * p.LM * p.LN;
+    {   // R from the caller's A, before precond_prepare scales the A in the buffer (or brings it up to date with pending patches: the kept copy has them)
+        DevPlan dA = dz; dA.A = const_cast<void*>(callersA);
+        spmm_apply(dA, dz.x, dz.v4, s);
+        if (!warm_refine_residual_launch(dz, dz.v4, X0, R, (double*)(p.buffer + p.wBn2z.offset), s)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        p.flops_performed += fm.fMult + fm.fNrm + nReal;            // the product A X0, |b|^2 and the subtraction (|r|^2: cycle 0 of the refinement counts it)
+    }
+    if (auto const st = precond_prepare(h, p)) return st;           // (x has not been written yet)
+    MixedWarm w{ (double const*)R };
+    auto const st = run_mixed(h, p, tol, maxIt, &w);
+    if (!w.finished) {   // it failed on the way: x is a partial correction at best.  X0 goes back, as far as the device still takes a copy
+        (void)hipMemcpyAsync(dz.x, X0, p.wXz.bytes, hipMemcpyDeviceToDevice, s);
+        return st;
+    }
+    if (w.updated) {     // x holds D, back-transformed: x := X0 + D
+        if (!warm_update_launch(dz, X0, s)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
+        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+        p.flops_performed += nReal; p.flops_performed_all += nReal;
+    }
+    return st;
 }
 
 tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt) {

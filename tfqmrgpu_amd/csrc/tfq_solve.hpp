@@ -31,6 +31,10 @@ tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt);
 // travels through the ranks' vote like every refusal of a solve
 tfqmrgpuStatus_t run_solve_from(Handle& h, Plan& p, double tol, int maxIt, void const* callersA, tfqmrgpuStatus_t early);
 
+// the same on an 'm' plan (tfqmrgpu_ext.h section 16): R in double from the caller's double A, the refinement of the mixed solve on A D = R,
+// X = X0 + D in double.  Several ranks are refused through the mixed solve's own first collective (three doubles, the third one set)
+tfqmrgpuStatus_t run_refine_from(Handle& h, Plan& p, double tol, int maxIt, void const* callersA, tfqmrgpuStatus_t early);
+
 // small systems: the column operations and the decisions run in the producers' tails (tfq_colops.hpp).  One rank, built-in operator:
 // a reduction over ranks or a foreign multiply sits between the producer and the decision otherwise
 inline bool several_ranks(Handle const& h) { return h.comm != nullptr || h.reduceFn != nullptr; }

@@ -428,7 +428,9 @@ __global__ __launch_bounds__(256) void k_init_col(DevPlan d, double tol, int max
 // LN, so a thread keeps its column (right-hand side) j = t % LN
 // the same for plans whose float side keeps quads of rows interleaved (16 x 16, 8 x 8 | 32 | 64, 16 | 32 x 32): an item is one 16-byte piece of R
 // = rows 4 g .. 4 g + 3 of one column; on the double side that is two 16-byte row pairs (ILVZ == 2) or four elements LN apart (native order)
-template <int LM, int LN, int ILVZ>
+// WARM (all three forms of the residual; tfq_device.hpp: launch_refine_residual): the right-hand side is the X-shaped vector R in a.Bz, read block for
+// block under x -- r = R - Y, in cycle 0 r = R -- with the arithmetic and the sum order of the cold form, whose code the parameter leaves as it was
+template <int LM, int LN, int ILVZ, bool WARM = false>
 __global__ __launch_bounds__(256) void k_refine_residual_q(RefineArgs a) {
     constexpr int P = LM * LN, T = (256 / LN) * LN, Q = LM / 4, IPB = 2 * Q * LN;   // items per block
     using f4v = float __attribute__((ext_vector_type(4)));
@@ -452,9 +454,9 @@ __global__ __launch_bounds__(256) void k_refine_residual_q(RefineArgs a) {
     if (t < T) for (uint32_t w = t; w < (last - first) * IPB; w += T) {
         uint32_t const blk = first + w / IPB;
         int const e = int(w % IPB), c = e / (Q * LN), g = (e % (Q * LN)) / LN, q = e % LN;
-        uint32_t const bq = d.bOfX[blk];
+        uint32_t const bq = WARM ? blk : d.bOfX[blk];
         double v[4] = {0, 0, 0, 0}, y[4] = {0, 0, 0, 0};
-        if (0xffffffffu != bq) quad(a.Bz + size_t(bq) * 2 * P + size_t(c) * P, g, q, v);
+        if (WARM || 0xffffffffu != bq) quad(a.Bz + size_t(bq) * 2 * P + size_t(c) * P, g, q, v);
         if (a.cycle > 0) quad(a.Yz + size_t(blk) * 2 * P + size_t(c) * P, g, q, y);
         f4v r;
 #pragma unroll
@@ -496,7 +498,7 @@ __global__ __launch_bounds__(256) void k_refine_update_q(RefineArgs a) {
     }
 }
 
-template <int LM, int LN>
+template <int LM, int LN, bool WARM = false>
 __global__ __launch_bounds__(256) void k_refine_residual(RefineArgs a) {
     constexpr int P = LM * LN, T = (256 / LN) * LN;
     __shared__ double s[256];
@@ -510,8 +512,8 @@ __global__ __launch_bounds__(256) void k_refine_residual(RefineArgs a) {
         uint32_t const blk = first + w / (2 * P);
         int const e = int(w % (2 * P)), c = e / P, r = (e % P) / LN, q = e % LN;
         size_t const zoff = size_t(c) * P + plane_offset(a.ilvZ, r, q, LN);
-        uint32_t const bq = d.bOfX[blk];
-        double v = (0xffffffffu == bq) ? 0. : a.Bz[size_t(bq) * 2 * P + zoff];
+        uint32_t const bq = WARM ? blk : d.bOfX[blk];
+        double v = (!WARM && 0xffffffffu == bq) ? 0. : a.Bz[size_t(bq) * 2 * P + zoff];
         if (a.cycle > 0) v -= a.Yz[size_t(blk) * 2 * P + zoff];
         acc = __builtin_fma(v, v, acc);
         R[size_t(blk) * 2 * P + size_t(c) * P + plane_offset(d.ilv, r, q, LN)] = float(v);
@@ -526,8 +528,9 @@ __global__ __launch_bounds__(256) void k_refine_residual(RefineArgs a) {
 }
 
 // per block column: |r|^2 per right-hand side from the chunk records -> the set-up of the inner solve (what k_init_col does from B:
-// tau = |r|^2, 1 / |r|^2, rho = 1, everything else 0) and max_rhs |r|^2 / |b|^2 for the refinement's own stopping test
-template <int LN>
+// tau = |r|^2, 1 / |r|^2, rho = 1, everything else 0) and max_rhs |r|^2 / |b|^2 for the refinement's own stopping test.
+// WARM: |b|^2 is that of B, preset by k_warm_bn2_col (tfq_warm.hip), where cycle 0 of a cold solve takes its own |r|^2 = |b|^2
+template <int LN, bool WARM = false>
 __global__ __launch_bounds__(256) void k_refine_init_col(RefineArgs a) {
     using R = float;
     __shared__ double s[256];
@@ -540,7 +543,7 @@ __global__ __launch_bounds__(256) void k_refine_init_col(RefineArgs a) {
     if (t < LN) {
         double const n2 = dd[0];
         size_t const ir = (size_t(col) * 2 + 0) * LN + t, ii = ir + LN, i1 = size_t(col) * LN + t;
-        if (0 == a.cycle) a.bn2z[i1] = n2;
+        if (!WARM && 0 == a.cycle) a.bn2z[i1] = n2;
         double const b2 = a.bn2z[i1];
         rec[t] = (b2 > 0.) ? n2 / b2 : 0.;      // a right-hand side that is zero is solved by x = 0
         d.tau[i1] = n2; d.invBn2[i1] = 1. / n2; d.var[i1] = 0; d.d[i1] = 0; d.status[i1] = 0;
@@ -633,18 +636,23 @@ hipError_t vec_launch(int op, DevPlan const& d, double tol, int maxIt, hipStream
     return hipErrorInvalidValue;
 }
 
-template <int LM, int LN>
-static void refine_run(int what, RefineArgs const& a, hipStream_t s) {
+template <int LM, int LN, bool WARM>
+static void refine_residual_run(RefineArgs const& a, bool quads, hipStream_t s) {
     dim3 const grid(a.d.nChunks), cols(a.d.nCols), blk(256);
+    if constexpr (LM % 4 == 0) {
+        if (quads && 2 == a.ilvZ) k_refine_residual_q<LM, LN, 2, WARM><<<grid, blk, 0, s>>>(a);
+        else if (quads) k_refine_residual_q<LM, LN, 0, WARM><<<grid, blk, 0, s>>>(a);
+        else k_refine_residual<LM, LN, WARM><<<grid, blk, 0, s>>>(a);
+    } else k_refine_residual<LM, LN, WARM><<<grid, blk, 0, s>>>(a);
+    k_refine_init_col<LN, WARM><<<cols, blk, 0, s>>>(a);
+    k_refine_max<<<1, blk, 0, s>>>(a);
+}
+template <int LM, int LN>
+static void refine_run(int what, RefineArgs const& a, hipStream_t s, bool warm) {
+    dim3 const grid(a.d.nChunks), blk(256);
     bool const quads = (4 == a.d.ilv) && (0 == a.ilvZ || 2 == a.ilvZ);   // 16-byte pieces on the float side (same arithmetic, same sums)
     if (0 == what) {
-        if constexpr (LM % 4 == 0) {
-            if (quads && 2 == a.ilvZ) k_refine_residual_q<LM, LN, 2><<<grid, blk, 0, s>>>(a);
-            else if (quads) k_refine_residual_q<LM, LN, 0><<<grid, blk, 0, s>>>(a);
-            else k_refine_residual<LM, LN><<<grid, blk, 0, s>>>(a);
-        } else k_refine_residual<LM, LN><<<grid, blk, 0, s>>>(a);
-        k_refine_init_col<LN><<<cols, blk, 0, s>>>(a);
-        k_refine_max<<<1, blk, 0, s>>>(a);
+        if (warm) refine_residual_run<LM, LN, true>(a, quads, s); else refine_residual_run<LM, LN, false>(a, quads, s);
     } else {
         if constexpr (LM % 4 == 0) {
             if (quads && 2 == a.ilvZ) k_refine_update_q<LM, LN, 2><<<grid, blk, 0, s>>>(a);
@@ -653,14 +661,14 @@ static void refine_run(int what, RefineArgs const& a, hipStream_t s) {
         } else k_refine_update<LM, LN><<<grid, blk, 0, s>>>(a);
     }
 }
-static void refine_dispatch(int what, RefineArgs const& a, hipStream_t s) {
+static void refine_dispatch(int what, RefineArgs const& a, hipStream_t s, bool warm) {
     int const key = a.d.LM * 1000 + a.d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: refine_run<LM, LN>(what, a, s); break;
+#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: refine_run<LM, LN>(what, a, s, warm); break;
     switch (key) { TFQ_SIZES(TFQ_CASE, float) default: break; }
 #undef TFQ_CASE
 }
-void launch_refine_residual(RefineArgs const& a, hipStream_t s) { refine_dispatch(0, a, s); }
-void launch_refine_update(RefineArgs const& a, hipStream_t s)   { refine_dispatch(1, a, s); }
+void launch_refine_residual(RefineArgs const& a, hipStream_t s, bool warm) { refine_dispatch(0, a, s, warm); }
+void launch_refine_update(RefineArgs const& a, hipStream_t s)   { refine_dispatch(1, a, s, false); }
 
 void launch_decide(DevPlan const& d, int phase, hipStream_t s)       { k_decide<<<1, 256, 0, s>>>(d, 0, phase); }
 void launch_probe_decide(DevPlan const& d, int phase, hipStream_t s) { k_decide<<<1, 256, 0, s>>>(d, 1, phase); }

@@ -60,5 +60,9 @@ void drop_cost_launch(DevPlan const& d, void const* A, uint32_t nX, uint32_t con
 bool warm_residual_launch(DevPlan const& d, void const* Y, void* X0, void* R, double tol, int maxIt, hipStream_t s);
 // behind it: x := X0 + x.  false (both): no instance for this block shape
 bool warm_update_launch(DevPlan const& d, void const* X0, hipStream_t s);
+// the residual pass for the refinement of an 'm' plan (tfqmrgpuExt_refineFrom): dz is the plan's double side (resolveZ), X0, R and Y = A * x
+// X-shaped vectors of doubles in element order ilvZ.  X0 := x, R := (B under X, or 0) - Y, bn2z [nCols][LN] := |b|^2, or |r|^2 where b = 0.
+// Writes dz.pz (chunk records), bn2z, X0 and R; no scalar of the float solves.  false: no instance for this block shape, or dz is no double side
+bool warm_refine_residual_launch(DevPlan const& dz, void const* Y, void* X0, void* R, double* bn2z, hipStream_t s);
 
 } // namespace tfq

@@ -3,6 +3,9 @@
 //   k_warm_init_col   per block column: the records summed in chunk order -> tau = |r|^2, 1 / |b|^2, rho = 1, everything else 0, the
 //                                       fold counters and the control block: what k_init_col (tfq_vec.hip) does from B
 //   k_warm_update     per chunk:        x := X0 + x
+// and for tfqmrgpuExt_refineFrom (section 16) on an 'm' plan, whose refinement then runs on A D = R: k_warm_residual and k_warm_update in double
+// on the plan's double side (resolveZ: x, B, element order ilvZ; the chunk tables and the record scratch pz are the plan's own), and
+//   k_warm_bn2_col    per block column: the records summed in chunk order -> |b|^2 of the refinement's stopping test
 // The driver then solves A D = R from zero with R as its X-shaped right-hand side (DevPlan::R, as the inner solves of the mixed
 // precision do) and never learns about X0.  Work groups, chunk tables, element order and access width are those of the vector kernels
 // (tfq_vec.hip): one work group per chunk, every lane moves 16 bytes per access and keeps its right-hand side on every trip, one [LN]
@@ -144,6 +147,20 @@ __global__ __launch_bounds__(256) void k_warm_init_col(DevPlan d, double tol, in
     if (0 == col && 0 == t) w_reset_ctl(d.ctl, tol, maxIterations);
 }
 
+// ---- per block column, 'm' plans (tfqmrgpu_ext.h section 16): |b|^2 of the refinement -------------------------------------------------------------
+// The records of k_warm_residual<double> on the plan's double side, summed in chunk order -> bn2z = |b|^2, or |r0|^2 where b = 0 (graded against
+// its own r0, as above).  Cycle 0 of a cold refinement takes its |r|^2 for this (k_refine_init_col, tfq_vec.hip), which here would be |r0|^2
+// for every right-hand side.  The scalars of the float solves stay with k_refine_init_col, which also forms the first residual |r0|^2 / bn2z
+template <int LN>
+__global__ __launch_bounds__(256) void k_warm_bn2_col(DevPlan d, double* bn2z) {
+    __shared__ double s[512];
+    uint32_t const col = blockIdx.x;
+    int const t = threadIdx.x;
+    double dd[2];
+    column_sum<LN, 2>(d.pz, d.colChunkPtr[col], d.colChunkPtr[col + 1], s, dd);
+    if (t < LN) bn2z[size_t(col) * LN + t] = (dd[1] > 0.) ? dd[1] : dd[0];
+}
+
 // ---- per chunk: x := X0 + x ------------------------------------------------------------------------------------------------------------
 // a correction that is exactly zero leaves X0 as it is, bit for bit (-0.0 + 0.0 would be +0.0)
 template <typename R, int LM, int LN>
@@ -164,18 +181,22 @@ __global__ __launch_bounds__(256) void k_warm_update(DevPlan d, void const* X0_)
     }
 }
 
+// what: 0 the residual pass and the set-up of the correction solve, 1 the update, 2 the residual pass and |b|^2 of an 'm' plan's refinement (bn2z)
 template <typename R, int LM, int LN>
-void warm_run(int what, DevPlan const& d, void const* Y, void* X0, void* Rv, double tol, int maxIt, hipStream_t s) {
+void warm_run(int what, DevPlan const& d, void const* Y, void* X0, void* Rv, double* bn2z, double tol, int maxIt, hipStream_t s) {
     dim3 const grid(d.nChunks), cols(d.nCols), blk(256);
     if (0 == what) {
         k_warm_residual<R, LM, LN><<<grid, blk, 0, s>>>(d, Y, X0, Rv);
         k_warm_init_col<R, LN><<<cols, blk, 0, s>>>(d, tol, maxIt);
+    } else if (2 == what) {
+        k_warm_residual<R, LM, LN><<<grid, blk, 0, s>>>(d, Y, X0, Rv);
+        k_warm_bn2_col<LN><<<cols, blk, 0, s>>>(d, bn2z);
     } else k_warm_update<R, LM, LN><<<grid, blk, 0, s>>>(d, X0);
 }
 
-bool warm_dispatch(int what, DevPlan const& d, void const* Y, void* X0, void* Rv, double tol, int maxIt, hipStream_t s) {
+bool warm_dispatch(int what, DevPlan const& d, void const* Y, void* X0, void* Rv, double* bn2z, double tol, int maxIt, hipStream_t s) {
     int const key = d.LM * 1000 + d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: warm_run<R, LM, LN>(what, d, Y, X0, Rv, tol, maxIt, s); return true;
+#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: warm_run<R, LM, LN>(what, d, Y, X0, Rv, bn2z, tol, maxIt, s); return true;
     if (d.dbl) { switch (key) { TFQ_SIZES(TFQ_CASE, double) default: break; } }
     else       { switch (key) { TFQ_SIZES(TFQ_CASE, float)  default: break; } }
 #undef TFQ_CASE
@@ -185,10 +206,14 @@ bool warm_dispatch(int what, DevPlan const& d, void const* Y, void* X0, void* Rv
 } // namespace
 
 bool warm_residual_launch(DevPlan const& d, void const* Y, void* X0, void* R, double tol, int maxIt, hipStream_t s) {
-    return warm_dispatch(0, d, Y, X0, R, tol, maxIt, s);
+    return warm_dispatch(0, d, Y, X0, R, nullptr, tol, maxIt, s);
 }
 bool warm_update_launch(DevPlan const& d, void const* X0, hipStream_t s) {
-    return warm_dispatch(1, d, nullptr, const_cast<void*>(X0), nullptr, 0., 0, s);
+    return warm_dispatch(1, d, nullptr, const_cast<void*>(X0), nullptr, nullptr, 0., 0, s);
+}
+bool warm_refine_residual_launch(DevPlan const& dz, void const* Y, void* X0, void* R, double* bn2z, hipStream_t s) {
+    if (!dz.dbl || !bn2z) return false;     // the double side of an 'm' plan (resolveZ) and nothing else
+    return warm_dispatch(2, dz, Y, X0, R, bn2z, 0., 0, s);
 }
 
 } // namespace tfq
