@@ -1,6 +1,6 @@
 // The block map of tfqmrgpuExt_carry (tfqmrgpu_amd/csrc/tfq_carry_host.cpp: carry_map_ok, carry_compose; tfqmrgpu_ext.h section 15) as a
 // stand-alone host program, for a sanitizer build:
-//   carry_map_check <file> [<file> ...]            (scripts/carry_map_sanitize.sh builds it with -fsanitize=address,undefined and runs it)
+//   carry_map_check <file> [<file> ...]            (scripts/check_sanitize.sh carry_map builds it with -fsanitize=address,undefined and runs it)
 // The files are those of scripts/leak_listing_check.cpp (scripts/leak_listing_inputs.py writes them).  For every file the source plan is
 // the file's pattern of X with its internal order (u2i); the destination is that pattern grown by all leak positions (grow_pattern, so the
 // map has -1 entries), by none, and a destination of arbitrary size whose map is random with repeats and -1 entries, and all -1.

@@ -1,6 +1,6 @@
 // The grown pattern (tfqmrgpu_amd/csrc/tfq_leak_host.cpp: grow_pattern, tfqmrgpu_ext.h section 12) as a stand-alone host program, for a
 // sanitizer build:
-//   grow_pattern_check <file> [<file> ...]         (scripts/grow_pattern_sanitize.sh builds it with -fsanitize=address,undefined and runs it)
+//   grow_pattern_check <file> [<file> ...]         (scripts/check_sanitize.sh grow_pattern builds it with -fsanitize=address,undefined and runs it)
 // The files are those of scripts/leak_listing_check.cpp (scripts/leak_listing_inputs.py writes them).  For every file the listing is
 // built and the pattern grown by: no position, all (NULL list), all (as a list, backwards), every third position backwards; and refused
 // for an index out of range, an index named twice, and more indices than positions.

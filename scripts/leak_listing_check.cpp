@@ -1,5 +1,5 @@
 // The leak listing (tfqmrgpu_amd/csrc/tfq_leak_host.cpp, tfqmrgpu_ext.h section 11) as a stand-alone host program, for a sanitizer build:
-//   leak_listing_check <file> [<file> ...]         (scripts/leak_sanitize.sh builds it with -fsanitize=address,undefined and runs it)
+//   leak_listing_check <file> [<file> ...]         (scripts/check_sanitize.sh leak_listing builds it with -fsanitize=address,undefined and runs it)
 // A file holds plain index arrays, all zero based, white-space separated (scripts/leak_listing_inputs.py writes them):
 //   nRows nCols nnzbA nnzbX maxProducts expectedLeakBlocks expectedLeakPairs
 //   rowOfA[nnzbA]  colOfA[nnzbA]  rowOfX[nnzbX]  colOfX[nnzbX] (compressed)  u2i[nnzbX]

@@ -1,6 +1,6 @@
 // The listing of the drop cost and the shrunk pattern (tfqmrgpu_amd/csrc/tfq_leak_host.cpp: drop_listing, shrink_pattern; tfqmrgpu_ext.h
 // section 13) as a stand-alone host program, for a sanitizer build:
-//   shrink_pattern_check <file> [<file> ...]       (scripts/shrink_pattern_sanitize.sh builds it with -fsanitize=address,undefined and runs it)
+//   shrink_pattern_check <file> [<file> ...]       (scripts/check_sanitize.sh shrink_pattern builds it with -fsanitize=address,undefined and runs it)
 // The files are those of scripts/leak_listing_check.cpp (scripts/leak_listing_inputs.py writes them).  For every file the pair list of
 // the plan is written down by brute force -- per block (i, c) of X in the caller's order, per A block (i, k) of that row, the X block
 // (k, c) --, the listing is built from it and compared with the pairs picked out per X block; the pattern is shrunk by: no block (NULL

@@ -2,7 +2,7 @@
 // Mirrors the entry points of real-space/tfQMRgpu tfQMRgpu/source/tfqmrgpu.cu (same names,
 // argument meaning and status codes); the implementation behind them is this library's own.
 // The solve itself -- the tfQMR driver, the refinement -- is tfq_solve.cpp; the preconditioner's set-up and the state of the A in the
-// buffer are tfq_precond_host.cpp.
+// buffer are tfq_precond_host.cpp; the calls that grade the caller's system (tfqmrgpu_ext.h sections 10 to 13) are tfq_grade_host.cpp.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -67,6 +67,8 @@ DevPlan resolveZ(Plan const& p) {
     d.x = b + p.wXz.offset; d.B = b + p.wBz.offset; d.A = b + p.wAz.offset;
     return d;
 }
+
+DevPlan resolve_callers(Plan const& p) { return ('m' == p.precision) ? resolveZ(p) : resolve(p); }
 
 // glibc rand() (TYPE_3 additive feedback generator, seed 1) restated so that the shadow vector of
 // the reference CPU path (tfqmrgpu_linalg.hxx:799-802) can be reproduced in any process state
@@ -152,7 +154,7 @@ static tfqmrgpuStatus_t transfer_x_vector(Plan& p, DevPlan const& d, hipStream_t
     return transfer_blocks(p, s, direction, dbl, Target{native, dbl, p.ilv}, user, d.u2i, p.nnzbX, p.LM, p.LN, TFQMRGPU_LAYOUT_RRRRIIII, false, false, own);
 }
 
-static tfqmrgpuStatus_t upload(void* dst, void const* src, size_t bytes, hipStream_t s) {
+tfqmrgpuStatus_t upload(void* dst, void const* src, size_t bytes, hipStream_t s) {
     if (0 == bytes || !src) return TFQMRGPU_STATUS_SUCCESS;
     TFQ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
     return TFQMRGPU_STATUS_SUCCESS;
@@ -432,7 +434,7 @@ static tfqmrgpuStatus_t operand_transfer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvP
 
     // where the operand lives: the buffer ('m': its double side, and for A the float copy of the inner solves beside it), or the kept copy
     hipStream_t const s = (hipStream_t)h->stream;
-    DevPlan const d = mixed ? resolveZ(*p) : resolve(*p);
+    DevPlan const d = resolve_callers(*p);
     Target to{ isA ? d.A : (1 == o.which) ? d.B : d.x, d.dbl, d.ilv };
     Target floatA{ p->buffer + p->wA.offset, false, p->ilv };
     if (intoKept) { auto const kept = kept_a(*p); to.native = kept.a; floatA.native = kept.aFloat; }
@@ -738,66 +740,12 @@ tfqmrgpuStatus_t tfqmrgpuExt_applyOperator(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     if (p->opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);       // a user-defined operator is the caller's to apply
     hipStream_t const s = (hipStream_t)h->stream;
     bool const mixed = ('m' == p->precision);
-    DevPlan const d = mixed ? resolveZ(*p) : resolve(*p);           // mixed: the double side (x, A), the product in v4 ... v7
+    DevPlan const d = resolve_callers(*p);                          // mixed: the double side (x, A), the product in v4 ... v7
     void* const y = mixed ? d.v4 : d.v9;                            // the work vectors are free outside of a solve
     for (int r = 0; r < std::max(1, std::abs(repetitions)); ++r) spmm_apply(d, d.x, y, s);
     // repetitions < 0: |repetitions| launches and nothing else (timing: X stays as it is, the product is left in the work vector)
     if (repetitions >= 0) TFQ_HIP(hipMemcpyAsync(d.x, y, mixed ? p->wXz.bytes : p->S, hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
     TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-// ---- sections 10 to 13 grade the caller's system on the device: their checks in front of the first device call, in the documented order, and
-// the operand they read.  needA: the call reads A (the patterns-only forms and the weights of section 13 do not)
-static tfqmrgpuStatus_t operands_ready(Plan const& p, bool const needA) {
-    if (nullptr == p.buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (p.opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);         // a user-defined operator is the caller's to apply
-    if (!needA) return TFQMRGPU_STATUS_SUCCESS;
-    if (!p.haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
-    if (TFQMRGPU_PRECOND_NONE != p.precondInA && !kept_is_callers_a(p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone; keepOperator keeps it
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-// the caller's A: the buffer's, or the kept copy while the buffer holds A M^-1 ('m': its double part) -- a patch of setBlocks('A') that no
-// set-up has seen yet is in the copy already
-static void const* callers_a(Plan const& p, DevPlan const& d) {
-    return (TFQMRGPU_PRECOND_NONE != p.precondInA) ? (void const*)kept_a(p).a : d.A;
-}
-
-// ---- per-right-hand-side residual of the caller's system (tfqmrgpu_ext.h section 10) --------------------------------------------------
-tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
-    double* residual2, double* bnorm2, int32_t* columns, double* worst)
-{
-    auto p = asPlan(plan); auto h = (Handle*)handle;
-    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
-    if (!residual2 && !bnorm2 && !columns && !worst) return TFQMRGPU_STATUS_NO_INFO_PASSED;
-    if (auto const st = operands_ready(*p, true)) return st;
-
-    hipStream_t const s = (hipStream_t)h->stream;
-    DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X, B and A
-    size_t const nRec = size_t(d.nChunks) * 2 * p->LN, nCol = size_t(p->nCols) * 2 * p->LN;
-    std::vector<double> host;
-    try { host.resize(nCol); } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    if (auto const st = p->residualScratch.reserve(std::max<size_t>((nRec + nCol) * sizeof(double), 256))) return st;
-    double* const rec = p->residualScratch.as<double>();
-    residual_launch(d, callers_a(*p, d), rec, rec + nRec, s);
-    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    if (nCol) TFQ_HIP(hipMemcpyAsync(host.data(), rec + nRec, nCol * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-
-    size_t const LN = size_t(p->LN);
-    double wmax = 0; bool any = false;                             // NaN entries (r = b = 0) are left out of the maximum
-    for (size_t c = 0; c < p->nCols; ++c) {
-        for (size_t j = 0; j < LN; ++j) {
-            double const r2 = host[(2 * c) * LN + j], b2 = host[(2 * c + 1) * LN + j];
-            if (residual2) residual2[c * LN + j] = r2;
-            if (bnorm2) bnorm2[c * LN + j] = b2;
-            double const quot = r2 / b2;
-            if (quot == quot) { wmax = any ? std::max(wmax, quot) : quot; any = true; }
-        }
-        if (columns) columns[c] = p->original_bsrColIndX[c];
-    }
-    if (worst) *worst = any ? std::sqrt(wmax) : std::nan("");
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
@@ -824,237 +772,6 @@ tfqmrgpuStatus_t tfqmrgpuExt_refineFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPl
     tfqmrgpuStatus_t const early = operands_ready(*p, true);
     void const* const a = early ? nullptr : callers_a(*p, resolveZ(*p));   // the double A: the buffer's, or the double part of the kept copy
     return run_refine_from(*h, *p, threshold, maxIterations, a, early);
-}
-
-// ---- truncation leak: what A X puts outside the pattern of X (tfqmrgpu_ext.h sections 11 and 12) --------------------------------------
-// the host analysis, once per plan and block shape
-static tfqmrgpuStatus_t leak_host(Plan& p) {
-    auto& l = p.leak;
-    if (l.built) return TFQMRGPU_STATUS_SUCCESS;
-    try {
-        if (p.cscPtr.empty()) a_by_column(p.nRows, p.colOfA, p.cscPtr, p.cscBlock);
-        if (!leak_listing(l, p.nRows, p.nCols, p.nnzbA, p.rowOfA.data(), p.colOfA.data(), p.cscPtr.data(), p.cscBlock.data(),
-                          p.nnzbX, p.rowOfX.data(), p.col32.data(), p.u2i.data(), leak_unit_products(p.LM, p.LN))) {
-            l = LeakListing{};
-            return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
-        }
-    } catch (std::bad_alloc const&) { l = LeakListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-// the listing on the device, Plan::leakDev: [pairs | posStart | unitFirst | colUnitPtr | records | column sums], every piece on a 256-byte
-// boundary.  ONE copy for truncationLeak and leakMap: whichever comes first uploads it, with one synchronise
-struct LeakDev { size_t oPairs, oPos, oUnit, oCol, oRec, oSum, total; };
-static LeakDev leak_dev_layout(Plan const& p) {
-    auto const& l = p.leak;
-    LeakDev o{};
-    o.oPairs = 0; o.oPos = o.oPairs + align256(l.pairs.size() * 4); o.oUnit = o.oPos + align256(l.posStart.size() * 4);
-    o.oCol = o.oUnit + align256(l.unitFirst.size() * 4); o.oRec = o.oCol + align256(l.colUnitPtr.size() * 4);
-    o.oSum = o.oRec + align256(l.nUnits() * size_t(p.LN) * sizeof(double));
-    o.total = o.oSum + align256(size_t(p.nCols) * size_t(p.LN) * sizeof(double));
-    return o;
-}
-static tfqmrgpuStatus_t leak_device(Plan& p, LeakDev const& o, hipStream_t s) {
-    if (p.leakDev) return TFQMRGPU_STATUS_SUCCESS;
-    auto const& l = p.leak;
-    if (auto const st = p.leakDev.reserve(std::max<size_t>(o.total, 256))) return st;
-    char* const dev = p.leakDev.as<char>();
-    tfqmrgpuStatus_t st = upload(dev + o.oPairs, l.pairs.data(), l.pairs.size() * 4, s);
-    if (!st) st = upload(dev + o.oPos, l.posStart.data(), l.posStart.size() * 4, s);
-    if (!st) st = upload(dev + o.oUnit, l.unitFirst.data(), l.unitFirst.size() * 4, s);
-    if (!st) st = upload(dev + o.oCol, l.colUnitPtr.data(), l.colUnitPtr.size() * 4, s);
-    if (!st && hipSuccess != hipStreamSynchronize(s)) st = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
-    if (st) p.leakDev.release();
-    return st;
-}
-
-tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
-    double* leak2, int32_t* columns, uint64_t* nLeakBlocks, uint64_t* nLeakPairs)
-{
-    auto p = asPlan(plan); auto h = (Handle*)handle;
-    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
-    if (!leak2 && !columns && !nLeakBlocks && !nLeakPairs) return TFQMRGPU_STATUS_NO_INFO_PASSED;
-    // everything but leak2 depends on the patterns alone: plan and bufferSize suffice
-    if (leak2) if (auto const st = operands_ready(*p, true)) return st;
-    if (auto const st = leak_host(*p)) return st;
-    auto& l = p->leak;
-    size_t const LN = size_t(p->LN), nUnits = l.nUnits(), nCol = size_t(p->nCols) * LN;
-    std::vector<double> host;
-    if (leak2) {
-        hipStream_t const s = (hipStream_t)h->stream;
-        try { host.resize(nCol); } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-        auto const o = leak_dev_layout(*p);
-        if (auto const st = leak_device(*p, o, s)) return st;       // the first call: upload the listing, one synchronise
-        char* const dev = p->leakDev.as<char>();
-        DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
-        leak_launch(d, callers_a(*p, d), uint32_t(nUnits), (uint32_t const*)(dev + o.oPairs), (uint32_t const*)(dev + o.oPos), (uint32_t const*)(dev + o.oUnit),
-                    (uint32_t const*)(dev + o.oCol), (double*)(dev + o.oRec), (double*)(dev + o.oSum), s);
-        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        if (nCol) TFQ_HIP(hipMemcpyAsync(host.data(), dev + o.oSum, nCol * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        std::copy(host.begin(), host.end(), leak2);
-    }
-    if (columns) std::copy(p->original_bsrColIndX.begin(), p->original_bsrColIndX.end(), columns);
-    if (nLeakBlocks) *nLeakBlocks = uint64_t(l.nPositions());
-    if (nLeakPairs) *nLeakPairs = uint64_t(l.nProducts());
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-// ---- leak map: the leak per position, and the pattern of X grown by chosen positions (tfqmrgpu_ext.h section 12) ------------------------
-tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
-    uint64_t capacity, int32_t* rows, int32_t* cols, double* pos2, uint64_t* nLeakBlocks)
-{
-    auto p = asPlan(plan); auto h = (Handle*)handle;
-    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
-    if (!rows && !cols && !pos2 && !nLeakBlocks) return TFQMRGPU_STATUS_NO_INFO_PASSED;
-    // everything but pos2 depends on the patterns alone, as in section 11
-    if (pos2) if (auto const st = operands_ready(*p, true)) return st;
-    if (auto const st = leak_host(*p)) return st;
-    auto const& l = p->leak;
-    size_t const LN = size_t(p->LN), nPos = l.nPositions();
-    if ((rows || cols || pos2) && capacity < uint64_t(nPos)) {      // the caller learns how much room the arrays need, and nothing else
-        if (nLeakBlocks) *nLeakBlocks = uint64_t(nPos);
-        return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');
-    }
-    std::vector<double> host;
-    if (pos2 && nPos) {
-        hipStream_t const s = (hipStream_t)h->stream;
-        try { host.resize(nPos * LN); } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-        auto const o = leak_dev_layout(*p);
-        if (auto const st = leak_device(*p, o, s)) return st;       // the listing of section 11, uploaded once for both calls
-        if (auto const st = p->leakMapRec.reserve(std::max<size_t>(nPos * LN * sizeof(double), 256))) return st;
-        char* const dev = p->leakDev.as<char>();
-        DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
-        leak_map_launch(d, callers_a(*p, d), uint32_t(nPos), (uint32_t const*)(dev + o.oPairs), (uint32_t const*)(dev + o.oPos), p->leakMapRec.as<double>(), s);
-        TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        TFQ_HIP(hipMemcpyAsync(host.data(), p->leakMapRec.ptr, nPos * LN * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        std::copy(host.begin(), host.end(), pos2);
-    }
-    if (rows) for (size_t n = 0; n < nPos; ++n) rows[n] = int32_t(l.posRow[n]);
-    if (cols) for (size_t n = 0; n < nPos; ++n) cols[n] = int32_t(l.posCol[n]);
-    if (nLeakBlocks) *nLeakBlocks = uint64_t(nPos);
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-// a pattern of sections 12 and 13 into malloc'ed arrays for the caller (tfqmrgpuExt_freeGrownPattern releases them)
-static tfqmrgpuStatus_t export_pattern(Plan const& p, GrownPattern const& g, tfqmrgpuGrownPattern_t* to) {
-    auto dup = [](std::vector<int32_t> const& v) {
-        auto q = (int32_t*)std::malloc(std::max<size_t>(1, v.size()) * sizeof(int32_t));
-        if (q) std::copy(v.begin(), v.end(), q);
-        return q;
-    };
-    to->mb = int32_t(p.nRows); to->nnzbX = int32_t(g.colInd.size());
-    to->rowPtrX = dup(g.rowPtr); to->colIndX = dup(g.colInd); to->oldBlock = dup(g.oldBlock);
-    if (!to->rowPtrX || !to->colIndX || !to->oldBlock) {
-        tfqmrgpuExt_freeGrownPattern(to);
-        return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
-    }
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-tfqmrgpuStatus_t tfqmrgpuExt_growPattern(tfqmrgpuBsrsvPlan_t plan, uint64_t nTake, uint64_t const* take, tfqmrgpuGrownPattern_t* grown) {
-    auto p = asPlan(plan);
-    if (!p || !grown) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    *grown = tfqmrgpuGrownPattern_t{};
-    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
-    if (auto const st = leak_host(*p)) return st;
-    auto const& l = p->leak;
-    GrownPattern g;
-    try {
-        int const bad = grow_pattern(g, p->nRows, p->nCols, p->nnzbX, p->rowOfX.data(), p->col32.data(), p->original_bsrColIndX.data(),
-                                     p->indexOffset, l.nPositions(), l.posRow.data(), l.posCol.data(), nTake, take);
-        if (1 == bad) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');   // an index >= nLeakBlocks, or one named twice
-        if (bad) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);        // the index arrays are 32 bit
-    } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    return export_pattern(*p, g, grown);
-}
-
-void tfqmrgpuExt_freeGrownPattern(tfqmrgpuGrownPattern_t* grown) {
-    if (!grown) return;
-    std::free(grown->rowPtrX); std::free(grown->colIndX); std::free(grown->oldBlock);
-    *grown = tfqmrgpuGrownPattern_t{};
-}
-
-// ---- drop cost: what each block of X carries, and the pattern of X without chosen blocks (tfqmrgpu_ext.h section 13) ------------------
-// the listing on the device, Plan::dropDev: [start | aOf | xOf | cost records | weight records], every piece on a 256-byte boundary
-struct DropDev { size_t oStart, oA, oX, oCost, oWeight, total; };
-static DropDev drop_dev_layout(Plan const& p) {
-    auto const& l = p.drop;
-    size_t const rec = align256(size_t(p.nnzbX) * size_t(p.LN) * sizeof(double));
-    DropDev o{};
-    o.oStart = 0; o.oA = o.oStart + align256(l.start.size() * 4); o.oX = o.oA + align256(l.aOf.size() * 4);
-    o.oCost = o.oX + align256(l.xOf.size() * 4); o.oWeight = o.oCost + rec; o.total = o.oWeight + rec;
-    return o;
-}
-
-tfqmrgpuStatus_t tfqmrgpuExt_dropCost(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double* cost2, double* weight2, uint64_t* nProducts) {
-    auto p = asPlan(plan); auto h = (Handle*)handle;
-    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
-    if (!cost2 && !weight2 && !nProducts) return TFQMRGPU_STATUS_NO_INFO_PASSED;
-    if (!cost2 && !weight2) { *nProducts = uint64_t(p->nPairs()); return TFQMRGPU_STATUS_SUCCESS; }   // the plan alone: no buffer, no A
-    if (auto const st = operands_ready(*p, nullptr != cost2)) return st;    // the weights do not read A
-
-    size_t const n = size_t(p->nnzbX) * size_t(p->LN);
-    std::vector<double> hostCost, hostWeight;                       // through host vectors: a failed copy leaves the caller's arrays untouched
-    try {
-        if (cost2) hostCost.resize(n);
-        if (weight2) hostWeight.resize(n);
-        if (!p->drop.built) drop_listing(p->drop, p->nnzbX, p->nPairs(), p->pairs.data(), p->u2i.data());
-    } catch (std::bad_alloc const&) { p->drop = DropListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    hipStream_t const s = (hipStream_t)h->stream;
-    auto const& l = p->drop;
-    auto const o = drop_dev_layout(*p);
-    if (!p->dropDev) {                                              // the first call: upload the listing, one synchronise
-        if (auto const st = p->dropDev.reserve(std::max<size_t>(o.total, 256))) return st;
-        char* const dev = p->dropDev.as<char>();
-        tfqmrgpuStatus_t st = upload(dev + o.oStart, l.start.data(), l.start.size() * 4, s);
-        if (!st) st = upload(dev + o.oA, l.aOf.data(), l.aOf.size() * 4, s);
-        if (!st) st = upload(dev + o.oX, l.xOf.data(), l.xOf.size() * 4, s);
-        if (!st && hipSuccess != hipStreamSynchronize(s)) st = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
-        if (st) { p->dropDev.release(); return st; }
-    }
-    char* const dev = p->dropDev.as<char>();
-    DevPlan const d = ('m' == p->precision) ? resolveZ(*p) : resolve(*p);   // 'm': the double copies of X and A
-    // the kernel writes the record of a block at the caller's index of that block: the copy-out is a plain copy
-    drop_cost_launch(d, cost2 ? callers_a(*p, d) : nullptr, p->nnzbX, (uint32_t const*)(dev + o.oStart), (uint32_t const*)(dev + o.oA),
-                     (uint32_t const*)(dev + o.oX), cost2 ? (double*)(dev + o.oCost) : nullptr, weight2 ? (double*)(dev + o.oWeight) : nullptr, s);
-    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    if (cost2 && n) TFQ_HIP(hipMemcpyAsync(hostCost.data(), dev + o.oCost, n * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    if (weight2 && n) TFQ_HIP(hipMemcpyAsync(hostWeight.data(), dev + o.oWeight, n * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    if (cost2) std::copy(hostCost.begin(), hostCost.end(), cost2);
-    if (weight2) std::copy(hostWeight.begin(), hostWeight.end(), weight2);
-    if (nProducts) *nProducts = uint64_t(p->nPairs());
-    return TFQMRGPU_STATUS_SUCCESS;
-}
-
-tfqmrgpuStatus_t tfqmrgpuExt_shrinkPattern(tfqmrgpuBsrsvPlan_t plan, uint64_t nDrop, int32_t const* drop, tfqmrgpuGrownPattern_t* shrunk) {
-    auto p = asPlan(plan);
-    if (!p || !shrunk) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    *shrunk = tfqmrgpuGrownPattern_t{};
-    if (nDrop > 0 && !drop) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    GrownPattern g;
-    try {
-        std::vector<uint8_t> hasB(p->nnzbX, uint8_t(0));
-        for (auto const x : p->subset) hasB[x] = 1;
-        int const bad = shrink_pattern(g, p->nRows, p->nnzbX, p->rowOfX.data(), p->col32.data(), p->original_bsrColIndX.data(),
-                                       p->indexOffset, hasB.data(), nDrop, drop);
-        if (1 == bad) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');   // an index outside [0, nnzbX), or one named twice
-        if (bad) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'B');        // the block carries a block of B
-    } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    return export_pattern(*p, g, shrunk);
-}
-
-// how the listing is cut: work units per compressed block column
-int64_t tfqmrgpuExt_leakUnits(tfqmrgpuBsrsvPlan_t plan, uint32_t* unitsPerColumn) {
-    auto p = asPlan(plan);
-    if (!p || !p->leak.built) return 0;
-    if (unitsPerColumn) for (uint32_t c = 0; c < p->nCols; ++c) unitsPerColumn[c] = p->leak.colUnitPtr[c + 1] - p->leak.colUnitPtr[c];
-    return int64_t(p->leak.nUnits());
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_commUniqueId(char id[128]) {
@@ -1167,8 +884,8 @@ tfqmrgpuStatus_t tfqmrgpuExt_carry(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t 
 
     // where the operand lives on either side: the buffer ('m': its double side), for the source A the caller's A (callers_a)
     bool const dMixed = ('m' == d->precision);
-    DevPlan const dd = dMixed ? resolveZ(*d) : resolve(*d);
-    DevPlan const ds = ('m' == sp->precision) ? resolveZ(*sp) : resolve(*sp);
+    DevPlan const dd = resolve_callers(*d);
+    DevPlan const ds = resolve_callers(*sp);
     CarrySide const from{ isA ? const_cast<void*>(callers_a(*sp, ds)) : isX ? ds.x : ds.B, ds.dbl, ds.ilv };
     CarrySide const to{ isA ? dd.A : isX ? dd.x : dd.B, dd.dbl, dd.ilv };
     if (isA) a_named(*d);

@@ -73,6 +73,7 @@ struct DevPlan {
 
 DevPlan resolve(Plan const& p);
 DevPlan resolveZ(Plan const& p) __attribute__((visibility("hidden")));   // 'm': the double-precision side as a plan of its own (tfq_api.hip)
+DevPlan resolve_callers(Plan const& p) __attribute__((visibility("hidden")));   // where the caller's X, B and A are: resolveZ for 'm', resolve otherwise
 
 // mixed precision 'm': the double-precision side of the plan (x, B, A, the product A x) next to the float plan `d` of the inner solves
 struct RefineArgs {

@@ -1,8 +1,8 @@
 // Drop cost: per block n of X and right-hand side j, cost2 = the sum over the plan's own block products A_ik X_kc whose X operand is block n
 // of |A_ik X_kc (:, j)|^2 -- every product squared ON ITS OWN -- and weight2 = |X_kc (:, j)|^2, in double whatever the plan's precision
 // (tfqmrgpu_ext.h section 13).  Not part of a solve: it reads A and X where the plan keeps them and writes only into memory that the
-// library owns.  Not k_leak_map over another listing: there the products of a work item are added and squared once, with a new X block
-// for every product; here the X block of a work item is fixed and each product is squared.
+// library owns.  What is this kernel's own: the X block of a work item is fixed and each of its products is squared on its own; two record
+// planes (cost, weight).  The products and the lane geometry are tfq_grade.hpp's.
 //   k_drop_cost<RA, LM, LN>   one work group per run of kDropRun consecutive X blocks of the caller's order (DropListing, tfq_plan.hpp)
 //     LM, LN multiples of 16: one X block per wave, the four waves of the group take four consecutive blocks at a time (wave w: the
 //                            blocks w, w + 4, ... of the run).  The wave converts its X operands to double ONCE and keeps them in
@@ -15,14 +15,14 @@
 //                            order.  The round count is a constant, so that every wave reaches every barrier; the work is predicated
 // A work item reads start[n], start[n + 1] and xOf[n] and writes the records of block n, for n < nX only.
 // No atomics, and every sum has one fixed order: two calls on the same data give the same bits.
-#include "tfq_residual.hpp"
+#include "tfq_grade.hpp"
 
 namespace tfq {
 
 constexpr uint32_t kDropRun = 32;           // X blocks per work group
 
 struct DropArgs {
-    void const *A, *X;                      // as LeakArgs (tfq_leak.hip); A is not read where cost == nullptr
+    void const *A, *X;                      // storage type RA; A blocks transposed ([k][i]) in the caller's block order, X in the internal order; A is not read where cost == nullptr
     uint32_t const *start, *aOf, *xOf;      // the listing's: products per X block; the A block of every product; where the X block lies
     uint32_t nX;
     int ilv;
@@ -44,13 +44,12 @@ __global__ __launch_bounds__(256) void k_drop_cost(DropArgs a) {
         constexpr int NT = LN / 16, KT = LM / 4;
         constexpr bool KEEP = (KT * NT * 4 <= 128);        // X of the lane in at most 128 VGPRs (all shapes but 64 x 64)
         constexpr int KR = KEEP ? KT : 1;
-        using T4 = typename Acc<double>::T;
         int const lane = t & 63, wave = t >> 6, lr = lane >> 4, lc = lane & 15;
         for (uint32_t y = first + uint32_t(wave); y < last; y += 4) {      // y is the same for the whole wave: the shuffles below see all 64 lanes
             uint32_t const q0 = a.start[y], q1 = withCost ? a.start[y + 1] : q0;
             RA const* const Xb = X + size_t(a.xOf[y]) * 2 * P;
             // lane (lr, lc) feeds X[k][16 n + lc], k = 4 kt + lr
-            double xr[KR][NT], xi[KR][NT], l2[NT], w2[NT];
+            double xrk[KR][NT], xik[KR][NT], l2[NT], w2[NT];
 #pragma unroll
             for (int n = 0; n < NT; ++n) { l2[n] = 0; w2[n] = 0; }
             auto load_x = [&](int const kt) {
@@ -58,7 +57,7 @@ __global__ __launch_bounds__(256) void k_drop_cost(DropArgs a) {
                 for (int n = 0; n < NT; ++n) {
                     int const ox = res_offset(ilv, 4 * kt + lr, 16 * n + lc, LN);
                     double const r = double(Xb[ox]), i = double(Xb[P + ox]);
-                    if constexpr (KEEP) { xr[kt][n] = r; xi[kt][n] = i; }
+                    if constexpr (KEEP) { xrk[kt][n] = r; xik[kt][n] = i; }
                     epi_nrm(w2[n], r, i);
                 }
             };
@@ -73,22 +72,14 @@ __global__ __launch_bounds__(256) void k_drop_cost(DropArgs a) {
                 RA const* Ab = A + size_t(a.aOf[q]) * 2 * LM * LM;
 #pragma unroll 1
                 for (int i0 = 0; i0 < LM; i0 += 16) {
-                    T4 cre[NT], cim[NT];
+                    GradeAcc cre[NT], cim[NT];
 #pragma unroll
-                    for (int n = 0; n < NT; ++n) { cre[n] = T4{0, 0, 0, 0}; cim[n] = T4{0, 0, 0, 0}; }
-                    auto k_step = [&](int const kt) {      // lane (lr, lc) feeds A[k][i0 + lc], as k_leak_map
-                        int const k = 4 * kt + lr, oa = res_offset(ilv, k, i0 + lc, LM);
-                        double const ar = double(Ab[oa]), ai = double(Ab[LM * LM + oa]);
-#pragma unroll
-                        for (int n = 0; n < NT; ++n) {
-                            double vr, vi;
-                            if constexpr (KEEP) { vr = xr[kt][n]; vi = xi[kt][n]; }
-                            else { int const ox = res_offset(ilv, k, 16 * n + lc, LN); vr = double(Xb[ox]); vi = double(Xb[P + ox]); }
-                            cre[n] = Acc<double>::mma(ar, vr, cre[n]);
-                            cim[n] = Acc<double>::mma(ar, vi, cim[n]);
-                            cre[n] = Acc<double>::mma(-ai, vi, cre[n]);
-                            cim[n] = Acc<double>::mma(ai, vr, cim[n]);
-                        }
+                    for (int n = 0; n < NT; ++n) { cre[n] = GradeAcc{0, 0, 0, 0}; cim[n] = GradeAcc{0, 0, 0, 0}; }
+                    auto k_step = [&](int const kt) {      // the X operand from the lane's registers where it keeps them
+                        TFQ_GRADE_STRIP_STEP(4 * kt + lr,
+                            double xr, xi;
+                            if constexpr (KEEP) { xr = xrk[kt][n]; xi = xik[kt][n]; }
+                            else { int const ox = res_offset(ilv, k, 16 * n + lc, LN); xr = double(Xb[ox]); xi = double(Xb[P + ox]); })
                     };
                     if constexpr (KEEP) {                  // (the registers of X are indexed by kt: unrolled in full)
 #pragma unroll
@@ -97,10 +88,7 @@ __global__ __launch_bounds__(256) void k_drop_cost(DropArgs a) {
 #pragma unroll 4
                         for (int kt = 0; kt < KT; ++kt) k_step(kt);
                     }
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) epi_nrm(l2[n], cre[n][r], cim[n][r]);   // register r of the lane: row lr + 4 r of the strip, column 16 n + lc
+                    TFQ_GRADE_STRIP_SQUARE(l2)        // register r of the lane: row lr + 4 r of the strip, column 16 n + lc
                 }
             }
             // the four lanes (lr, lc) of a column, added in ascending lr; every lane computes the sums, the lanes lr == 0 store them
@@ -116,16 +104,14 @@ __global__ __launch_bounds__(256) void k_drop_cost(DropArgs a) {
             }
         }
     } else {
-        constexpr int NACC = (P >= 256) ? P / 256 : 1;   // elements per lane
-        constexpr int GRP = (P >= 256) ? 1 : 256 / P;    // X blocks in flight per round
-        static_assert(P < 256 || (P % 256 == 0 && 256 % LN == 0), "block does not tile the work group");
+        using L = GradeLanes<LM, LN>;
+        constexpr int NACC = L::NACC, GRP = L::GRP;
         constexpr int ROUNDS = (int(kDropRun) + GRP - 1) / GRP;
-        constexpr int RANKS = (P >= 256) ? 256 / LN : LM;     // lanes that share a column of a block
+        constexpr int RANKS = L::RANKS_ITEM;     // lanes that share a column of a block
         static_assert(GRP * LN <= 256, "one lane per entry of the records of a round");
         __shared__ double s[2][GRP * LN * RANKS];
-        int const g = (P >= 256) ? 0 : t / P;
-        int const e0 = (P >= 256) ? t : t % P;
-        int const j = e0 % LN;                           // the same for all NACC elements of a lane (256 % LN == 0)
+        L const l = TFQ_GRADE_LANES(t);
+        int const g = l.g, e0 = l.e0, j = l.j;
         int const rank = (P >= 256) ? t / LN : e0 / LN;  // P < 256: the row of the element
 #pragma unroll 1
         for (int round = 0; round < ROUNDS; ++round) {
@@ -145,16 +131,7 @@ __global__ __launch_bounds__(256) void k_drop_cost(DropArgs a) {
                     double yr[NACC], yi[NACC];
 #pragma unroll
                     for (int n = 0; n < NACC; ++n) { yr[n] = 0; yi[n] = 0; }
-#pragma unroll
-                    for (int k = 0; k < LM; ++k) {
-                        int const ox = res_offset(ilv, k, j, LN);
-                        double const xr = double(Xb[ox]), xi = double(Xb[P + ox]);
-#pragma unroll
-                        for (int n = 0; n < NACC; ++n) {
-                            int const oa = res_offset(ilv, k, (e0 + n * 256) / LN, LM);
-                            res_cmac(yr[n], yi[n], double(Ab[oa]), double(Ab[LM * LM + oa]), xr, xi);
-                        }
-                    }
+                    TFQ_GRADE_LANE_PAIR
 #pragma unroll
                     for (int n = 0; n < NACC; ++n) epi_nrm(l2, yr[n], yi[n]);
                 }
@@ -188,11 +165,7 @@ void drop_cost_launch(DevPlan const& d, void const* A, uint32_t nX, uint32_t con
     a.A = A; a.X = d.x;
     a.start = start; a.aOf = aOf; a.xOf = xOf; a.nX = nX;
     a.ilv = d.ilv; a.cost = cost; a.weight = weight;
-    int const key = d.LM * 1000 + d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: drop_cost_run<R, LM, LN>(a, s); break;
-    if (d.dbl) { switch (key) { TFQ_SIZES(TFQ_CASE, double) default: break; } }
-    else       { switch (key) { TFQ_SIZES(TFQ_CASE, float)  default: break; } }
-#undef TFQ_CASE
+    for_shape(d.dbl, d.LM, d.LN, [&](auto sh) { using S = decltype(sh); drop_cost_run<typename S::real, S::LM, S::LN>(a, s); });
 }
 
 } // namespace tfq

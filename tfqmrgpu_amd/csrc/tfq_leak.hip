@@ -1,12 +1,13 @@
 // Truncation leak: the part of A X that falls on block rows OUTSIDE a block column's pattern, |.|^2 per (block column, right-hand side),
 // summed in double whatever the plan's precision (tfqmrgpu_ext.h section 11).  Not part of a solve: it reads A and X where the plan keeps
-// them and writes only into memory that the library owns.  The structure is k_residual's (tfq_residual.hip) without B, over the leak
-// listing (tfq_leak_host.cpp) instead of the plan's pair list:
+// them and writes only into memory that the library owns.  What is this kernel's own: it walks the leak listing (tfq_leak_host.cpp) by
+// work units, adds the products of a position before it squares them, subtracts nothing, and ends in the per-unit tail with one record
+// plane.  The products and that tail are tfq_grade.hpp's.
 //   k_leak<RA, LM, LN>   one work group per work unit (a run of leak positions of ONE block column): the product sum of every position,
 //                        squared and summed per column of the block; one [LN] record per unit
 //   k_leak_col<LN>       one work group per block column: the records of its units added in unit order; a column without units gets 0
 // No atomics, and every sum has one fixed order: two calls on the same data give the same bits.
-#include "tfq_residual.hpp"
+#include "tfq_grade.hpp"
 
 namespace tfq {
 
@@ -32,7 +33,6 @@ __global__ __launch_bounds__(256) void k_leak(LeakArgs a) {
     if constexpr (MFMA) {
         // v_mfma_f64_16x16x4_f64 on operands converted to double in registers: a wave keeps a strip of 16 rows of a position, all its columns
         constexpr int MT = LM / 16, NT = LN / 16;
-        using T4 = typename Acc<double>::T;
         int const lane = t & 63, wave = t >> 6, lr = lane >> 4, lc = lane & 15;
         double l2[NT];
 #pragma unroll
@@ -41,44 +41,22 @@ __global__ __launch_bounds__(256) void k_leak(LeakArgs a) {
         for (uint32_t u = uint32_t(wave); u < strips; u += 4) {
             uint32_t const y = first + u / MT;
             int const i0 = int(u % MT) * 16;
-            T4 cre[NT], cim[NT];
+            GradeAcc cre[NT], cim[NT];
 #pragma unroll
-            for (int n = 0; n < NT; ++n) { cre[n] = T4{0, 0, 0, 0}; cim[n] = T4{0, 0, 0, 0}; }
+            for (int n = 0; n < NT; ++n) { cre[n] = GradeAcc{0, 0, 0, 0}; cim[n] = GradeAcc{0, 0, 0, 0}; }
             for (uint32_t q = a.posStart[y]; q < a.posStart[y + 1]; ++q) {
                 RA const* Ab = A + size_t(a.pairs[2 * size_t(q)]) * 2 * LM * LM;
                 RA const* Xb = X + size_t(a.pairs[2 * size_t(q) + 1]) * 2 * P;
-#pragma unroll 4
-                for (int k0 = 0; k0 < LM; k0 += 4) {      // lane (lr, lc) feeds A[k][i0 + lc] and X[k][16 n + lc], k = k0 + lr
-                    int const k = k0 + lr, oa = res_offset(ilv, k, i0 + lc, LM);
-                    double const ar = double(Ab[oa]), ai = double(Ab[LM * LM + oa]);
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        int const ox = res_offset(ilv, k, 16 * n + lc, LN);
-                        double const xr = double(Xb[ox]), xi = double(Xb[P + ox]);
-                        cre[n] = Acc<double>::mma(ar, xr, cre[n]);
-                        cim[n] = Acc<double>::mma(ar, xi, cim[n]);
-                        cre[n] = Acc<double>::mma(-ai, xi, cre[n]);
-                        cim[n] = Acc<double>::mma(ai, xr, cim[n]);
-                    }
-                }
+TFQ_GRADE_STRIP_PAIR      // lane (lr, lc) feeds A[k][i0 + lc] and X[k][16 n + lc], k = k0 + lr
             }
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) epi_nrm(l2[n], cre[n][r], cim[n][r]);   // register r of the lane: a row of the strip, column 16 n + lc
+            TFQ_GRADE_STRIP_SQUARE(l2)        // register r of the lane: row lr + 4 r of the strip, column 16 n + lc
         }
         // lanes that share a column: rank = (wave, lr); summed in rank order
         __shared__ double s[LN * 16];
         int const rank = wave * 4 + lr;
 #pragma unroll
         for (int n = 0; n < NT; ++n) s[(16 * n + lc) * 16 + rank] = l2[n];
-        __syncthreads();
-        for (int e = t; e < LN; e += 256) {
-            double sum = 0;
-#pragma unroll 1
-            for (int r = 0; r < 16; ++r) sum += s[e * 16 + r];
-            a.rec[size_t(unit) * LN + e] = sum;
-        }
+        TFQ_GRADE_UNIT_TAIL(LN, 16, a.rec[size_t(unit) * LN + e])
     } else {
         // one lane per element of a position's block, the 4- and 8-row shapes
         constexpr int NACC = (P >= 256) ? P / 256 : 1;   // elements per lane
@@ -96,16 +74,7 @@ __global__ __launch_bounds__(256) void k_leak(LeakArgs a) {
             for (uint32_t q = a.posStart[y]; q < a.posStart[y + 1]; ++q) {
                 RA const* Ab = A + size_t(a.pairs[2 * size_t(q)]) * 2 * LM * LM;
                 RA const* Xb = X + size_t(a.pairs[2 * size_t(q) + 1]) * 2 * P;
-#pragma unroll
-                for (int k = 0; k < LM; ++k) {
-                    int const ox = res_offset(ilv, k, j, LN);
-                    double const xr = double(Xb[ox]), xi = double(Xb[P + ox]);
-#pragma unroll
-                    for (int n = 0; n < NACC; ++n) {
-                        int const oa = res_offset(ilv, k, (e0 + n * 256) / LN, LM);
-                        res_cmac(yr[n], yi[n], double(Ab[oa]), double(Ab[LM * LM + oa]), xr, xi);
-                    }
-                }
+                TFQ_GRADE_LANE_PAIR
             }
 #pragma unroll
             for (int n = 0; n < NACC; ++n) epi_nrm(l2, yr[n], yi[n]);
@@ -115,13 +84,7 @@ __global__ __launch_bounds__(256) void k_leak(LeakArgs a) {
         __shared__ double s[LN * RANKS];
         int const rank = (P >= 256) ? t / LN : g * LM + e0 / LN;
         if (active) s[j * RANKS + rank] = l2;
-        __syncthreads();
-        for (int e = t; e < LN; e += 256) {
-            double sum = 0;
-#pragma unroll 1
-            for (int r = 0; r < RANKS; ++r) sum += s[e * RANKS + r];
-            a.rec[size_t(unit) * LN + e] = sum;
-        }
+        TFQ_GRADE_UNIT_TAIL(LN, RANKS, a.rec[size_t(unit) * LN + e])
     }
 }
 
@@ -150,11 +113,7 @@ void leak_launch(DevPlan const& d, void const* A, uint32_t nUnits, uint32_t cons
     a.A = A; a.X = d.x;
     a.posStart = posStart; a.pairs = pairs; a.unitFirst = unitFirst; a.colUnitPtr = colUnitPtr;
     a.ilv = d.ilv; a.rec = rec; a.col = col;
-    int const key = d.LM * 1000 + d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: leak_run<R, LM, LN>(nUnits, d.nCols, a, s); break;
-    if (d.dbl) { switch (key) { TFQ_SIZES(TFQ_CASE, double) default: break; } }
-    else       { switch (key) { TFQ_SIZES(TFQ_CASE, float)  default: break; } }
-#undef TFQ_CASE
+    for_shape(d.dbl, d.LM, d.LN, [&](auto sh) { using S = decltype(sh); leak_run<typename S::real, S::LM, S::LN>(nUnits, d.nCols, a, s); });
 }
 
 } // namespace tfq

@@ -1,7 +1,8 @@
 // Leak map: the truncation leak of tfq_leak.hip per leak POSITION -- |(A X)(i, c)(:, j)|^2 for every block row i outside the pattern of
 // block column c that receives a product, per right-hand side j, in double whatever the plan's precision (tfqmrgpu_ext.h section 12).
-// Not part of a solve: it reads A and X where the plan keeps them and writes only into memory that the library owns.  The products and
-// their order are k_leak's; what k_leak folds into one record per work unit stays apart here:
+// Not part of a solve: it reads A and X where the plan keeps them and writes only into memory that the library owns.  What is
+// this kernel's own: it walks the positions of the leak listing one by one, adds the products of a position before it squares them and
+// keeps one record per position (the products and the lane geometry are tfq_grade.hpp's):
 //   k_leak_map<RA, LM, LN>   one work group per run of kLeakMapRun consecutive positions of the listing (its work units are not used:
 //                            a record belongs to ONE position, so there is nothing to add across positions and no second kernel)
 //     LM, LN multiples of 16: a whole position per wave, wave w of the group takes the positions w, w + 4, ... of the run.  It walks the
@@ -11,14 +12,14 @@
 //                            flight per round; the lanes that share a column of a position are added through LDS in rank order.  The
 //                            round count is a constant, so that every wave reaches every barrier; the work is predicated
 // No atomics, and every sum has one fixed order: two calls on the same data give the same bits.
-#include "tfq_residual.hpp"
+#include "tfq_grade.hpp"
 
 namespace tfq {
 
 constexpr uint32_t kLeakMapRun = 32;        // positions per work group
 
 struct LeakMapArgs {
-    void const *A, *X;                      // as LeakArgs (tfq_leak.hip)
+    void const *A, *X;                      // storage type RA; A blocks transposed ([k][i]) in the caller's block order, X in the internal order
     uint32_t const *posStart, *pairs;       // the listing's: products per leak position; (A block, X block) per product
     uint32_t nPos;
     int ilv;
@@ -37,7 +38,6 @@ __global__ __launch_bounds__(256) void k_leak_map(LeakMapArgs a) {
 
     if constexpr (MFMA) {
         constexpr int NT = LN / 16;
-        using T4 = typename Acc<double>::T;
         int const lane = t & 63, wave = t >> 6, lr = lane >> 4, lc = lane & 15;
         for (uint32_t y = first + uint32_t(wave); y < last; y += 4) {      // y is the same for the whole wave: the shuffles below see all 64 lanes
             uint32_t const q0 = a.posStart[y], q1 = a.posStart[y + 1];
@@ -46,31 +46,15 @@ __global__ __launch_bounds__(256) void k_leak_map(LeakMapArgs a) {
             for (int n = 0; n < NT; ++n) l2[n] = 0;
 #pragma unroll 1
             for (int i0 = 0; i0 < LM; i0 += 16) {
-                T4 cre[NT], cim[NT];
+                GradeAcc cre[NT], cim[NT];
 #pragma unroll
-                for (int n = 0; n < NT; ++n) { cre[n] = T4{0, 0, 0, 0}; cim[n] = T4{0, 0, 0, 0}; }
+                for (int n = 0; n < NT; ++n) { cre[n] = GradeAcc{0, 0, 0, 0}; cim[n] = GradeAcc{0, 0, 0, 0}; }
                 for (uint32_t q = q0; q < q1; ++q) {
                     RA const* Ab = A + size_t(a.pairs[2 * size_t(q)]) * 2 * LM * LM;
                     RA const* Xb = X + size_t(a.pairs[2 * size_t(q) + 1]) * 2 * P;
-#pragma unroll 4
-                    for (int k0 = 0; k0 < LM; k0 += 4) {      // lane (lr, lc) feeds A[k][i0 + lc] and X[k][16 n + lc], k = k0 + lr
-                        int const k = k0 + lr, oa = res_offset(ilv, k, i0 + lc, LM);
-                        double const ar = double(Ab[oa]), ai = double(Ab[LM * LM + oa]);
-#pragma unroll
-                        for (int n = 0; n < NT; ++n) {
-                            int const ox = res_offset(ilv, k, 16 * n + lc, LN);
-                            double const xr = double(Xb[ox]), xi = double(Xb[P + ox]);
-                            cre[n] = Acc<double>::mma(ar, xr, cre[n]);
-                            cim[n] = Acc<double>::mma(ar, xi, cim[n]);
-                            cre[n] = Acc<double>::mma(-ai, xi, cre[n]);
-                            cim[n] = Acc<double>::mma(ai, xr, cim[n]);
-                        }
-                    }
+TFQ_GRADE_STRIP_PAIR      // lane (lr, lc) feeds A[k][i0 + lc] and X[k][16 n + lc], k = k0 + lr
                 }
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) epi_nrm(l2[n], cre[n][r], cim[n][r]);   // register r of the lane: row lr + 4 r of the strip, column 16 n + lc
+                TFQ_GRADE_STRIP_SQUARE(l2)        // register r of the lane: row lr + 4 r of the strip, column 16 n + lc
             }
             // the four lanes (lr, lc) of a column, added in ascending lr; every lane computes the sum, the lanes lr == 0 store it
 #pragma unroll
@@ -82,16 +66,14 @@ __global__ __launch_bounds__(256) void k_leak_map(LeakMapArgs a) {
             }
         }
     } else {
-        constexpr int NACC = (P >= 256) ? P / 256 : 1;   // elements per lane
-        constexpr int GRP = (P >= 256) ? 1 : 256 / P;    // positions in flight per round
-        static_assert(P < 256 || (P % 256 == 0 && 256 % LN == 0), "block does not tile the work group");
+        using L = GradeLanes<LM, LN>;
+        constexpr int NACC = L::NACC, GRP = L::GRP;
         constexpr int ROUNDS = (int(kLeakMapRun) + GRP - 1) / GRP;
-        constexpr int RANKS = (P >= 256) ? 256 / LN : LM;     // lanes that share a column of a position
+        constexpr int RANKS = L::RANKS_ITEM;     // lanes that share a column of a position
         static_assert(GRP * LN <= 256, "one lane per entry of the records of a round");
         __shared__ double s[GRP * LN * RANKS];
-        int const g = (P >= 256) ? 0 : t / P;
-        int const e0 = (P >= 256) ? t : t % P;
-        int const j = e0 % LN;                           // the same for all NACC elements of a lane (256 % LN == 0)
+        L const l = TFQ_GRADE_LANES(t);
+        int const g = l.g, e0 = l.e0, j = l.j;
         int const rank = (P >= 256) ? t / LN : e0 / LN;  // P < 256: the row of the element
 #pragma unroll 1
         for (int round = 0; round < ROUNDS; ++round) {
@@ -104,16 +86,7 @@ __global__ __launch_bounds__(256) void k_leak_map(LeakMapArgs a) {
                 for (uint32_t q = a.posStart[y]; q < a.posStart[y + 1]; ++q) {
                     RA const* Ab = A + size_t(a.pairs[2 * size_t(q)]) * 2 * LM * LM;
                     RA const* Xb = X + size_t(a.pairs[2 * size_t(q) + 1]) * 2 * P;
-#pragma unroll
-                    for (int k = 0; k < LM; ++k) {
-                        int const ox = res_offset(ilv, k, j, LN);
-                        double const xr = double(Xb[ox]), xi = double(Xb[P + ox]);
-#pragma unroll
-                        for (int n = 0; n < NACC; ++n) {
-                            int const oa = res_offset(ilv, k, (e0 + n * 256) / LN, LM);
-                            res_cmac(yr[n], yi[n], double(Ab[oa]), double(Ab[LM * LM + oa]), xr, xi);
-                        }
-                    }
+                    TFQ_GRADE_LANE_PAIR
                 }
                 double l2 = 0;
 #pragma unroll
@@ -143,11 +116,7 @@ void leak_map_launch(DevPlan const& d, void const* A, uint32_t nPos, uint32_t co
     a.A = A; a.X = d.x;
     a.posStart = posStart; a.pairs = pairs; a.nPos = nPos;
     a.ilv = d.ilv; a.rec = rec;
-    int const key = d.LM * 1000 + d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: leak_map_run<R, LM, LN>(a, s); break;
-    if (d.dbl) { switch (key) { TFQ_SIZES(TFQ_CASE, double) default: break; } }
-    else       { switch (key) { TFQ_SIZES(TFQ_CASE, float)  default: break; } }
-#undef TFQ_CASE
+    for_shape(d.dbl, d.LM, d.LN, [&](auto sh) { using S = decltype(sh); leak_map_run<typename S::real, S::LM, S::LN>(a, s); });
 }
 
 } // namespace tfq

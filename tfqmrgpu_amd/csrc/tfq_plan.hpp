@@ -83,6 +83,19 @@ constexpr uint32_t kColSlot = 64;      // granule of the slot numbering of colPa
     X(R, 4, 4) X(R, 4, 5) X(R, 4, 8) X(R, 4, 32) X(R, 8, 8) X(R, 8, 9) X(R, 8, 10) X(R, 8, 32) X(R, 8, 64) \
     X(R, 16, 16) X(R, 16, 32) X(R, 16, 64) X(R, 32, 32) X(R, 32, 64) X(R, 64, 64)
 
+// f(Shape<R, LM, LN>{}) for the instance of that list that a plan of this storage type and block shape needs.  false: there is none, and
+// f has not been called -- a missing instance is the caller's error to report, never a fall-back
+template <typename R, int LM_, int LN_> struct Shape { using real = R; static constexpr int LM = LM_, LN = LN_; };
+template <typename F>
+inline bool for_shape(bool dbl, int lm, int ln, F const& f) {
+    int const key = lm * 1000 + ln;
+#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: f(Shape<R, LM, LN>{}); return true;
+    if (dbl) { switch (key) { TFQ_SIZES(TFQ_CASE, double) default: break; } }
+    else     { switch (key) { TFQ_SIZES(TFQ_CASE, float)  default: break; } }
+#undef TFQ_CASE
+    return false;
+}
+
 // Waves per 16-row strip of a Y block in k_spmm_mfma | k_spmm_mfma_m (rb: bytes per accumulator element): two, each with LN / 2 columns,
 // where the double accumulators of a whole strip and two operand slices would not fit the 256 VGPRs of two waves per SIMD
 // (128 columns: 128 VGPRs of accumulators)

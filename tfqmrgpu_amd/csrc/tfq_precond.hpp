@@ -21,6 +21,16 @@ size_t kept_a_bytes(Plan const& p);
 KeptA kept_a(Plan const& p);                // the pieces of Plan::aKept (allocated)
 inline bool kept_is_callers_a(Plan const& p) { return p.keepA && p.aKept && TFQMRGPU_PRECOND_NONE != p.precondInA; }
 
+// ---- the caller's operands, for the calls that read them outside of a solve (tfq_grade_host.cpp; solveFrom, refineFrom and carry of tfq_api.hip)
+// their checks in front of the first device call, in the documented order: no buffer | user-defined operator | and where the call reads A
+// (needA): A never set | A scaled and not kept
+tfqmrgpuStatus_t operands_ready(Plan const& p, bool needA);                     // tfq_grade_host.cpp
+// the caller's A: the buffer's (d.A), or the kept copy while the buffer holds A M^-1 ('m': its double part) -- a patch of setBlocks('A')
+// that no set-up has seen yet is in the copy already
+void const* callers_a(Plan const& p, struct DevPlan const& d);                    // tfq_grade_host.cpp
+// host -> device on the stream, not waited for; nothing for no bytes or no source (tfq_api.hip)
+tfqmrgpuStatus_t upload(void* dst, void const* src, size_t bytes, hipStream_t s);
+
 // ---- what a solve needs before its first iteration, and behind its last
 tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p);
 tfqmrgpuStatus_t precond_back(Handle& h, Plan& p);      // X := M^-1 Y

@@ -182,7 +182,7 @@ static tfqmrgpuStatus_t precond_update(Handle& h, Plan& p) {
     auto const m = precond_mem(p);
     auto const k = kept_a(p);
     bool const mixed = ('m' == p.precision), wDbl = ('c' != p.precision);
-    DevPlan const d = mixed ? resolveZ(p) : resolve(p);
+    DevPlan const d = resolve_callers(p);
     uint32_t const* const blocks = rows + nRowsListed;
     launch_precond_invert_listed(d.dbl, wDbl, k.a, m.diag, m.minv, m.identity, rows, nRowsListed, p.LM, d.ilv, s);
     launch_precond_apply_listed(d.dbl, wDbl, true, k.a, d.A, nBlocksListed, blocks, m.colA, m.minv, p.LM, p.LM, d.ilv, s);
@@ -231,7 +231,7 @@ static tfqmrgpuStatus_t precond_prepare_(Handle& h, Plan& p) {
     }
     auto const m = precond_mem(p);
     bool const mixed = ('m' == p.precision), wDbl = ('c' != p.precision);
-    DevPlan const d = mixed ? resolveZ(p) : resolve(p);      // mixed: M^-1 comes from the double copy of A
+    DevPlan const d = resolve_callers(p);      // mixed: M^-1 comes from the double copy of A
     if (p.keepA) {   // the caller's A, device to device, before it is scaled in place: block order, transposition and element order are the buffer's
         if (!p.aKept) if (auto const st = p.aKept.reserve(kept_a_bytes(p))) return st;
         auto const k = kept_a(p);
@@ -261,7 +261,7 @@ tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p) {
 tfqmrgpuStatus_t precond_back(Handle& h, Plan& p) {
     if (TFQMRGPU_PRECOND_BLOCK_JACOBI != p.precondInA) return TFQMRGPU_STATUS_SUCCESS;
     auto const m = precond_mem(p);
-    DevPlan const d = ('m' == p.precision) ? resolveZ(p) : resolve(p);
+    DevPlan const d = resolve_callers(p);
     launch_precond_apply(d.dbl, 'c' != p.precision, false, d.x, p.nnzbX, d.rowI, m.minv, p.LM, p.LN, d.ilv, (hipStream_t)h.stream);
     TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
     p.flops_performed += 8. * p.LM * p.LM * p.LN * p.nnzbX;

@@ -5,8 +5,10 @@
 //                            the fused multiplies): the truncated product A X of every block of the chunk, minus its B block, squared and
 //                            summed per column of the block; two [LN] records per chunk
 //   k_residual_col<LN>       one work group per block column: the records of its chunks added in chunk order
+// What is this kernel's own: it walks the plan's pair list by chunks, adds the products of a Y block before it squares them, subtracts B,
+// and ends in the per-unit tail with two record planes.  The products and that tail are tfq_grade.hpp's.
 // No atomics, and every sum has one fixed order: two calls on the same data give the same bits.
-#include "tfq_residual.hpp"
+#include "tfq_grade.hpp"
 
 namespace tfq {
 
@@ -19,7 +21,7 @@ struct ResidualArgs {
     double* col;                            // [nCols][2][LN]
 };
 
-// r = y - b, sums of squares (res_offset, res_cmac: tfq_residual.hpp)
+// r = y - b, sums of squares (res_offset, res_cmac: tfq_grade.hpp)
 __device__ __forceinline__ void res_square(double& r2, double& b2, double yr, double yi, double br, double bi) {
     double const rr = fma_(-1., br, yr), ri = fma_(-1., bi, yi);
     epi_nrm(r2, rr, ri); epi_nrm(b2, br, bi);
@@ -38,7 +40,6 @@ __global__ __launch_bounds__(256) void k_residual(ResidualArgs a) {
     if constexpr (MFMA) {
         // v_mfma_f64_16x16x4_f64 on operands converted to double in registers: a wave keeps a strip of 16 rows of a Y block, all its columns
         constexpr int MT = LM / 16, NT = LN / 16;
-        using T4 = typename Acc<double>::T;
         int const lane = t & 63, wave = t >> 6, lr = lane >> 4, lc = lane & 15;
         double r2[NT], b2[NT];
 #pragma unroll
@@ -47,26 +48,13 @@ __global__ __launch_bounds__(256) void k_residual(ResidualArgs a) {
         for (uint32_t u = uint32_t(wave); u < units; u += 4) {
             uint32_t const y = first + u / MT;
             int const i0 = int(u % MT) * 16;
-            T4 cre[NT], cim[NT];
+            GradeAcc cre[NT], cim[NT];
 #pragma unroll
-            for (int n = 0; n < NT; ++n) { cre[n] = T4{0, 0, 0, 0}; cim[n] = T4{0, 0, 0, 0}; }
+            for (int n = 0; n < NT; ++n) { cre[n] = GradeAcc{0, 0, 0, 0}; cim[n] = GradeAcc{0, 0, 0, 0}; }
             for (uint32_t q = a.starts[y]; q < a.starts[y + 1]; ++q) {
                 RA const* Ab = A + size_t(a.pairs[2 * size_t(q)]) * 2 * LM * LM;
                 RA const* Xb = X + size_t(a.pairs[2 * size_t(q) + 1]) * 2 * P;
-#pragma unroll 4
-                for (int k0 = 0; k0 < LM; k0 += 4) {      // lane (lr, lc) feeds A[k][i0 + lc] and X[k][16 n + lc], k = k0 + lr
-                    int const k = k0 + lr, oa = res_offset(ilv, k, i0 + lc, LM);
-                    double const ar = double(Ab[oa]), ai = double(Ab[LM * LM + oa]);
-#pragma unroll
-                    for (int n = 0; n < NT; ++n) {
-                        int const ox = res_offset(ilv, k, 16 * n + lc, LN);
-                        double const xr = double(Xb[ox]), xi = double(Xb[P + ox]);
-                        cre[n] = Acc<double>::mma(ar, xr, cre[n]);
-                        cim[n] = Acc<double>::mma(ar, xi, cim[n]);
-                        cre[n] = Acc<double>::mma(-ai, xi, cre[n]);
-                        cim[n] = Acc<double>::mma(ai, xr, cim[n]);
-                    }
-                }
+TFQ_GRADE_STRIP_PAIR      // lane (lr, lc) feeds A[k][i0 + lc] and X[k][16 n + lc], k = k0 + lr
             }
             uint32_t const bq = a.bOfX[y];
             RA const* Bb = B + size_t(bq != 0xffffffffu ? bq : 0) * 2 * P;
@@ -87,13 +75,7 @@ __global__ __launch_bounds__(256) void k_residual(ResidualArgs a) {
         int const rank = wave * 4 + lr;
 #pragma unroll
         for (int n = 0; n < NT; ++n) { s[(16 * n + lc) * 16 + rank] = r2[n]; s[(LN + 16 * n + lc) * 16 + rank] = b2[n]; }
-        __syncthreads();
-        for (int e = t; e < 2 * LN; e += 256) {
-            double sum = 0;
-#pragma unroll 1
-            for (int r = 0; r < 16; ++r) sum += s[e * 16 + r];
-            a.rec[size_t(chunk) * 2 * LN + e] = sum;
-        }
+        TFQ_GRADE_UNIT_TAIL(2 * LN, 16, a.rec[size_t(chunk) * 2 * LN + e])
     } else {
         // one lane per element of a Y block, the 4- and 8-row shapes
         constexpr int NACC = (P >= 256) ? P / 256 : 1;   // elements per lane
@@ -111,16 +93,7 @@ __global__ __launch_bounds__(256) void k_residual(ResidualArgs a) {
             for (uint32_t q = a.starts[y]; q < a.starts[y + 1]; ++q) {
                 RA const* Ab = A + size_t(a.pairs[2 * size_t(q)]) * 2 * LM * LM;
                 RA const* Xb = X + size_t(a.pairs[2 * size_t(q) + 1]) * 2 * P;
-#pragma unroll
-                for (int k = 0; k < LM; ++k) {
-                    int const ox = res_offset(ilv, k, j, LN);
-                    double const xr = double(Xb[ox]), xi = double(Xb[P + ox]);
-#pragma unroll
-                    for (int n = 0; n < NACC; ++n) {
-                        int const oa = res_offset(ilv, k, (e0 + n * 256) / LN, LM);
-                        res_cmac(yr[n], yi[n], double(Ab[oa]), double(Ab[LM * LM + oa]), xr, xi);
-                    }
-                }
+                TFQ_GRADE_LANE_PAIR
             }
             uint32_t const bq = a.bOfX[y];
             RA const* Bb = B + size_t(bq != 0xffffffffu ? bq : 0) * 2 * P;
@@ -139,13 +112,7 @@ __global__ __launch_bounds__(256) void k_residual(ResidualArgs a) {
         __shared__ double s[2 * LN * RANKS];
         int const rank = (P >= 256) ? t / LN : g * LM + e0 / LN;
         if (active) { s[j * RANKS + rank] = r2; s[(LN + j) * RANKS + rank] = b2; }
-        __syncthreads();
-        for (int e = t; e < 2 * LN; e += 256) {
-            double sum = 0;
-#pragma unroll 1
-            for (int r = 0; r < RANKS; ++r) sum += s[e * RANKS + r];
-            a.rec[size_t(chunk) * 2 * LN + e] = sum;
-        }
+        TFQ_GRADE_UNIT_TAIL(2 * LN, RANKS, a.rec[size_t(chunk) * 2 * LN + e])
     }
 }
 
@@ -172,11 +139,7 @@ void residual_launch(DevPlan const& d, void const* A, double* rec, double* col, 
     a.A = A; a.X = d.x; a.B = d.B;
     a.starts = d.starts; a.pairs = d.pairs; a.bOfX = d.bOfX; a.chunkFirst = d.chunkFirst; a.colChunkPtr = d.colChunkPtr;
     a.ilv = d.ilv; a.rec = rec; a.col = col;
-    int const key = d.LM * 1000 + d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: residual_run<R, LM, LN>(d, a, s); break;
-    if (d.dbl) { switch (key) { TFQ_SIZES(TFQ_CASE, double) default: break; } }
-    else       { switch (key) { TFQ_SIZES(TFQ_CASE, float)  default: break; } }
-#undef TFQ_CASE
+    for_shape(d.dbl, d.LM, d.LN, [&](auto sh) { using S = decltype(sh); residual_run<typename S::real, S::LM, S::LN>(d, a, s); });
 }
 
 } // namespace tfq

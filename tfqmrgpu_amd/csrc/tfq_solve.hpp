@@ -26,7 +26,7 @@ static inline tfqmrgpuStatus_t hipCheck(hipError_t e, int code, int line) {
 // one solve of the plan: tfQMR in the plan's precision, or the refinement around float solves for 'm'
 tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt);
 
-// the same from the X in the plan (tfqmrgpu_ext.h section 14): R = B - A X0 with the caller's A (`callersA`: tfq_api.hip, callers_a), the
+// the same from the X in the plan (tfqmrgpu_ext.h section 14): R = B - A X0 with the caller's A (`callersA`: tfq_grade_host.cpp, callers_a), the
 // tfQMR driver on A D = R, X = X0 + D.  `early`: a refusal the ABI's checks have found already; several ranks are refused here -- either
 // travels through the ranks' vote like every refusal of a solve
 tfqmrgpuStatus_t run_solve_from(Handle& h, Plan& p, double tol, int maxIt, void const* callersA, tfqmrgpuStatus_t early);

@@ -1,4 +1,5 @@
-// internal launch interface of the vector / column kernels (tfq_vec.hip) and the multiply (tfq_spmm.hip, tfq_spmm.hpp)
+// internal launch interface of the vector / column kernels (tfq_vec.hip), the multiply (tfq_spmm.hip, tfq_spmm.hpp), the grading kernels
+// (tfq_residual.hip, tfq_leak.hip, tfq_leak_map.hip, tfq_drop_cost.hip; device helpers tfq_grade.hpp, host side tfq_grade_host.cpp) and the warm start
 #pragma once
 #include "tfq_device.hpp"
 

@@ -195,12 +195,8 @@ void warm_run(int what, DevPlan const& d, void const* Y, void* X0, void* Rv, dou
 }
 
 bool warm_dispatch(int what, DevPlan const& d, void const* Y, void* X0, void* Rv, double* bn2z, double tol, int maxIt, hipStream_t s) {
-    int const key = d.LM * 1000 + d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: warm_run<R, LM, LN>(what, d, Y, X0, Rv, bn2z, tol, maxIt, s); return true;
-    if (d.dbl) { switch (key) { TFQ_SIZES(TFQ_CASE, double) default: break; } }
-    else       { switch (key) { TFQ_SIZES(TFQ_CASE, float)  default: break; } }
-#undef TFQ_CASE
-    return false;     // a missing instance is an error, never a fall-back
+    // false: a missing instance is an error, never a fall-back
+    return for_shape(d.dbl, d.LM, d.LN, [&](auto sh) { using S = decltype(sh); warm_run<typename S::real, S::LM, S::LN>(what, d, Y, X0, Rv, bn2z, tol, maxIt, s); });
 }
 
 } // namespace
