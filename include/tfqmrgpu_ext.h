@@ -699,6 +699,74 @@ tfqmrgpuStatus_t tfqmrgpuExt_carry(tfqmrgpuHandle_t handle,
 tfqmrgpuStatus_t tfqmrgpuExt_refineFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
     double threshold, int maxIterations);
 
+/* ---- (17) start projection: blend the kept solutions per right-hand side ------------------------------------------------------------- */
+/* Every turn of the loop of sections 8 to 16 ends in solveFrom / refineFrom from "the X in the plan", and that X is ONE vector: the solution
+ * of the previous energy.  A caller who has solved at E1, E2, E3 holds three good vectors when E4 arrives.  These calls keep up to four
+ * solutions in the plan and, in front of the solve, put into X the combination of them that minimises the residual of the NEW system
+ * (Fischer's projection for successive right-hand sides).  Every right-hand side of every block column is a system of its own here, so
+ * the projection is a k x k least-squares problem per (compressed block column c, right-hand side j), k <= 4; nothing couples columns or
+ * ranks.  The loop: setBlocks('A'), projectStart, solveFrom, pushStart.  Nothing that exists changes; solveFrom starts from a better X0.
+ *
+ * keepStarts(plan, depth): the plan keeps the `depth` newest starts, depth = 0 (the default: off) ... 4.  Call it after bufferSize; it
+ *   survives bufferSize and setBuffer as the preconditioner kind does (the starts themselves do not: they hold values of one buffer).  A depth
+ *   outside 0 ... 4: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'X' (status = 14 + 1000 * line + 10^7 * 'X').  A smaller depth drops
+ *   the oldest starts, 0 releases everything; changing the depth while starts are held waits for the device (the call has no stream).  A
+ *   plan that never calls it, or calls it with 0, is bit for bit the plan it was: same launches, same buffer, same results.
+ * pushStart: copies what getMatrix('X') would return at that moment -- after a solve the solution (back-transformed on a preconditioned
+ *   plan, section 7), after setMatrix('X') / setBlocks('X') / carry the caller's X -- into slot 0; the older starts move up one slot, and
+ *   with `depth` starts held the oldest leaves.  The copy is device to device on the handle's stream, in the plan's storage precision and
+ *   internal order; an 'm' plan copies its double X.  Checks, in this order: plan / handle pointers: TFQMRGPU_POINTER_INVALID; no
+ *   bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; depth 0: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'X'; no buffer:
+ *   TFQMRGPU_POINTER_INVALID.
+ * startCount: the number of starts held, 0 ... depth (0 for a plan pointer that is none).  startDepth: the depth that keepStarts set, which
+ *   sizes `coefficients` of projectStart (0 for a plan pointer that is none).
+ *
+ * projectStart works with the k = startCount starts S_0 (the newest) ... S_{k-1}:
+ *   W_i = A S_i by the plan's own multiply, truncated to the pattern of X as every product is, in the plan's storage
+ *     precision.  A is the caller's A, chosen as in section 14: the buffer's A while it has not been scaled, the kept copy (section 9)
+ *     once it has, patches of setBlocks('A') that no set-up has seen yet included.  'm' plans use the double side, as refineFrom does.
+ *   Per (c, j), with <u, v> = sum conj(u) v over the blocks of block column c and column j of each block, all summed in double:
+ *     G_il = <W_i, W_l>,  g_i = <W_i, B>,  |B|^2;  B is zero under X blocks that carry no B block, as in sections 10 and 14.
+ *   gamma minimises |B - sum_i gamma_i W_i|: G gamma = g by a Cholesky factorisation G = L L^H in double, the starts taken in the order
+ *     newest first.  Start i is DROPPED for that right-hand side (gamma_i = 0, it takes no part in the rows behind it) when its pivot
+ *     d_i = G_ii - sum_{l < i} |L_il|^2 is not greater than G_ii * TFQMRGPU_PROJECT_PIVOT_DOUBLE (2^-26, double storage: 'z' and 'm') or
+ *     G_ii * TFQMRGPU_PROJECT_PIVOT_FLOAT (2^-12, 'c') -- the square root of the rounding unit of the storage type.  Normal equations can
+ *     be trusted only while 1 / cond^2 stays above the rounding of the Gram entries; a start below the threshold adds less than that
+ *     fraction of a new direction.  A start with G_ii = 0 is dropped.  A right-hand side with b = 0 gets gamma = 0 and nUsed = 0.
+ *   x := sum_i gamma_i[c, j] S_i is written into the plan's X: accumulated in double by fused multiply-adds in slot order, rounded once
+ *     to the storage precision.  The ring is not changed.
+ *   coefficients[((c*LN + j)*depth + i)*2 + {0, 1}] = Re, Im of gamma_i, a HOST array [nCols][LN][depth][2] of double, zeros for dropped
+ *     and absent slots, may be NULL;  nUsed[c*LN + j] = the number of kept starts, a HOST array [nCols][LN], may be NULL.  With both
+ *     NULL the call still projects.
+ *   No residual is returned: tfqmrgpuExt_residual (section 10) grades the result on the same A, B and X.  By construction, up to
+ *     rounding, the projected residual of every right-hand side is at most that of X = S_0 and at most |B|.
+ * All checks of projectStart come before the first device call, in the order of section 14: plan / handle pointers:
+ *   TFQMRGPU_POINTER_INVALID; no bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; no buffer: TFQMRGPU_POINTER_INVALID; a user-defined operator
+ *   (section 5): TFQMRGPU_NO_IMPLEMENTATION; A never set whole on this buffer: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A'; A
+ *   scaled and no copy kept: TFQMRGPU_NO_IMPLEMENTATION; no start held: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'X'.  After any
+ *   error nothing has been written: not X, not the host arrays.
+ * Precisions: 'z', 'c' and 'm'.  Several ranks (section 4): local to the rank's own block columns, no collective, like section 10.
+ * Deterministic: one record of k^2 + 2k + 1 doubles per right-hand side and chunk (the diagonal of G, Re / Im of its upper triangle,
+ *   Re / Im of g, |B|^2), written by one work group; the chunks of a column are added in chunk order by one work group per column; no
+ *   atomics.  Two calls give the same bits.
+ * Non-destructive: the three calls write nothing into the caller's buffer but X (projectStart) -- not the work vectors v4 ... v9, not the
+ *   results of the last solve, not its control block, not the float floor of an 'm' plan; getWorkVector, getBoundHistory and getInfo
+ *   behind them return what they returned in front of them.
+ * Memory: library-owned device memory -- `depth` starts, allocated by the first pushStart; `depth` images W, the records and gamma,
+ *   allocated by the first projectStart.  Released by destroyPlan, bufferSize, setBuffer and keepStarts(plan, 0).  bufferSize and the
+ *   buffer layout do not change.
+ * Stream: asynchronous on the handle's stream; projectStart synchronises it once if a host array is asked for.  Do not call any of them
+ *   during a solve. */
+#define TFQMRGPU_PROJECT_PIVOT_DOUBLE 1.4901161193847656e-08   /* 2^-26 */
+#define TFQMRGPU_PROJECT_PIVOT_FLOAT  2.44140625e-04           /* 2^-12 */
+tfqmrgpuStatus_t tfqmrgpuExt_keepStarts(tfqmrgpuBsrsvPlan_t plan, int depth);                 /* 0 (default, off) ... 4 */
+tfqmrgpuStatus_t tfqmrgpuExt_pushStart(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan);    /* X of the plan -> slot 0, older ones move up */
+int32_t          tfqmrgpuExt_startCount(tfqmrgpuBsrsvPlan_t plan);                            /* starts held, 0 ... depth */
+int32_t          tfqmrgpuExt_startDepth(tfqmrgpuBsrsvPlan_t plan);                            /* the depth kept, 0 ... 4 */
+tfqmrgpuStatus_t tfqmrgpuExt_projectStart(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double *coefficients /* HOST [nCols][LN][depth][2] (Re, Im), may be NULL */,
+    int32_t *nUsed       /* HOST [nCols][LN], may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

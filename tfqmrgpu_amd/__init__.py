@@ -44,6 +44,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_leakMap", "tfqmrgpuExt_growPattern", "tfqmrgpuExt_freeGrownPattern",
     "tfqmrgpuExt_dropCost", "tfqmrgpuExt_shrinkPattern", "tfqmrgpuExt_solveFrom", "tfqmrgpuExt_carry",
     "tfqmrgpuExt_refineFrom",
+    "tfqmrgpuExt_keepStarts", "tfqmrgpuExt_pushStart", "tfqmrgpuExt_startCount", "tfqmrgpuExt_startDepth", "tfqmrgpuExt_projectStart",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -164,6 +165,13 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_solveFrom.argtypes = [P, P, C.c_double, I]
     lib.tfqmrgpuExt_carry.argtypes = [P, P, P, C.c_char, C.c_int32, P]
     lib.tfqmrgpuExt_refineFrom.argtypes = [P, P, C.c_double, I]
+    lib.tfqmrgpuExt_keepStarts.argtypes = [P, I]
+    lib.tfqmrgpuExt_pushStart.argtypes = [P, P]
+    lib.tfqmrgpuExt_startCount.argtypes = [P]
+    lib.tfqmrgpuExt_startCount.restype = C.c_int32
+    lib.tfqmrgpuExt_startDepth.argtypes = [P]
+    lib.tfqmrgpuExt_startDepth.restype = C.c_int32
+    lib.tfqmrgpuExt_projectStart.argtypes = [P, P, P, P]
     return lib
 
 
@@ -395,6 +403,31 @@ class Solver:
         solve_from.  Returns the raw status as solve does"""
         st = lib.tfqmrgpuExt_refineFrom(self.handle, self.plan, threshold, max_iterations)
         return _check(st, "tfqmrgpuExt_refineFrom", allowed=(0, 6, 9))
+
+    # -- start projection (tfqmrgpu_ext.h section 17) ---------------------------------------------------
+    def keep_starts(self, depth):
+        """keep the `depth` newest starts in the plan, 0 (off) ... 4; call after buffer_size.  A smaller depth drops the oldest starts"""
+        return _check(lib.tfqmrgpuExt_keepStarts(self.plan, int(depth)), "tfqmrgpuExt_keepStarts")
+
+    def push_start(self):
+        """the X that get_matrix would return now becomes the newest start; with `depth` starts held the oldest leaves"""
+        return _check(lib.tfqmrgpuExt_pushStart(self.handle, self.plan), "tfqmrgpuExt_pushStart")
+
+    def start_count(self):
+        return int(lib.tfqmrgpuExt_startCount(self.plan))
+
+    def start_depth(self):
+        return int(lib.tfqmrgpuExt_startDepth(self.plan))
+
+    def project_start(self):
+        """X := per (block column, right-hand side) the combination of the kept starts that minimises |B - A X| for the caller's A as it
+        is now; what precedes solve_from / refine_from in an energy loop.  Returns a dict: coefficients, complex [nCols, LN, depth]
+        (newest start first, zeros for dropped and absent starts), and n_used, int32 [nCols, LN], the starts kept per right-hand side"""
+        n, depth = int(self.plan_view()["nCols"]), self.start_depth()      # the plan's own depth sizes the array the library fills
+        g = np.zeros((n, self.LN, max(depth, 1), 2), np.float64)
+        used = np.zeros((n, self.LN), np.int32)
+        _check(lib.tfqmrgpuExt_projectStart(self.handle, self.plan, _ptr(g), _ptr(used)), "tfqmrgpuExt_projectStart")
+        return dict(coefficients=(g[..., 0] + 1j * g[..., 1])[:, :, :depth], n_used=used)
 
     # -- operands from another plan (tfqmrgpu_ext.h section 15) ---------------------------------------------
     def carry_from(self, src, var, old_block=None):

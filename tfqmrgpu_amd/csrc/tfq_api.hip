@@ -2,7 +2,8 @@
 // Mirrors the entry points of real-space/tfQMRgpu tfQMRgpu/source/tfqmrgpu.cu (same names,
 // argument meaning and status codes); the implementation behind them is this library's own.
 // The solve itself -- the tfQMR driver, the refinement -- is tfq_solve.cpp; the preconditioner's set-up and the state of the A in the
-// buffer are tfq_precond_host.cpp; the calls that grade the caller's system (tfqmrgpu_ext.h sections 10 to 13) are tfq_grade_host.cpp.
+// buffer are tfq_precond_host.cpp; the calls that grade the caller's system (tfqmrgpu_ext.h sections 10 to 13) are tfq_grade_host.cpp; the start projection
+// (section 17) is tfq_project_host.cpp.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +19,7 @@
 #include "tfq_vec.hpp"
 #include "tfq_switch.hpp"
 #include "tfq_carry.hpp"
+#include "tfq_project.hpp"
 
 using namespace tfq;
 
@@ -296,6 +298,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     p->leak = LeakListing{}; p->leakDev.release(); p->leakMapRec.release();   // ... and the work units of the previous block shape
     p->dropDev.release();                  // ... and the records of the previous block shape
     p->warm.release();                     // ... and X0 and R of the previous block shape
+    starts_release(*p);                    // ... and the kept starts and their scratch
     a_new_layout(*p);
     p->precision = prec;
     p->buffer = nullptr;
@@ -313,6 +316,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     p->buffer = (char*)pBuffer;
     a_new_buffer(*p);
     p->warm.release();                     // (X0 and R of a warm solve belong to the X of the old buffer)
+    starts_release(*p);                    // (... and so do the kept starts)
     auto at = [&](Window const& w) { return (void*)(p->buffer + w.offset); };
     for (auto const& l : indexLists(*p))   // (tfq_plan.cpp: the windows were sized from the same list)
         if (auto const st = upload(at(*l.window), l.data, l.bytes, s)) return st;
@@ -772,6 +776,35 @@ tfqmrgpuStatus_t tfqmrgpuExt_refineFrom(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPl
     tfqmrgpuStatus_t const early = operands_ready(*p, true);
     void const* const a = early ? nullptr : callers_a(*p, resolveZ(*p));   // the double A: the buffer's, or the double part of the kept copy
     return run_refine_from(*h, *p, threshold, maxIterations, a, early);
+}
+
+// ---- start projection: blend the kept solutions per right-hand side (tfqmrgpu_ext.h section 17; tfq_project_host.cpp) ------------------------
+tfqmrgpuStatus_t tfqmrgpuExt_keepStarts(tfqmrgpuBsrsvPlan_t plan, int const depth) {
+    auto p = asPlan(plan);
+    if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    return starts_keep(*p, depth);
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_pushStart(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan) {
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    return starts_push(*h, *p);
+}
+
+int32_t tfqmrgpuExt_startCount(tfqmrgpuBsrsvPlan_t plan) {
+    auto p = asPlan(plan);
+    return p ? p->startCount : 0;
+}
+
+int32_t tfqmrgpuExt_startDepth(tfqmrgpuBsrsvPlan_t plan) {
+    auto p = asPlan(plan);
+    return p ? p->startDepth : 0;
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_projectStart(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double* coefficients, int32_t* nUsed) {
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (!p || !h) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    return starts_project(*h, *p, coefficients, nUsed);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_commUniqueId(char id[128]) {

@@ -314,6 +314,12 @@ struct Plan {
     // tfqmrgpuExt_carry (tfqmrgpu_ext.h section 15), on the DESTINATION plan: library-owned device copy of the composed block list
     // (tfq_carry_host.cpp: carry_compose), grown on demand
     DevMem carryList;
+    // start projection (tfqmrgpu_ext.h section 17; tfq_project_host.cpp): the ring of kept starts -- startDepth X-shaped vectors in the plan's
+    // storage type and internal order, start i (0: the newest) in slot (startHead + i) % startDepth, allocated by the first pushStart -- and
+    // the scratch of projectStart [images W | records | gamma | nUsed], allocated by its first call.  Both hold values of one buffer and are
+    // sized by the block shape: released by bufferSize and setBuffer (starts_release); the depth stays, as the preconditioner kind does
+    int startDepth = 0, startCount = 0, startHead = 0;
+    DevMem startMem, projectMem;
 
     // ---- results of the last solve -------------------------------------------------------------
     double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;

@@ -13,47 +13,12 @@
 #include "tfq_device.hpp"
 #include "tfq_vec.hpp"
 #include "tfq_colops.hpp"
+#include "tfq_stream.hpp"
 
 namespace tfq {
 namespace {
 
-// geometry and 16-byte accesses as in tfq_vec.hip (Geo, ldv, stv)
-template <typename R> struct WVec;
-template <> struct WVec<double> { static constexpr int N = 2; };
-template <> struct WVec<float>  { static constexpr int N = 4; };
-
-template <typename R, int LM, int LN>
-struct WGeo {
-    static constexpr int VEC = WVec<R>::N;
-    static constexpr int P = LM * LN;            // elements of one plane (Re or Im) of a block
-    static constexpr int IPB = P / VEC;          // vector items per block plane
-    static constexpr int T = (256 / LN) * LN;    // active threads: a multiple of LN, so that a thread keeps its right-hand side on every trip
-    static_assert(P % VEC == 0, "block plane must be a multiple of the vector width");
-};
-
-template <typename R> __device__ inline void w_ld(R (&r)[WVec<R>::N], R const* p) {
-    using V = R __attribute__((ext_vector_type(WVec<R>::N)));
-    auto const v = __builtin_nontemporal_load(reinterpret_cast<V const*>(p));
-#pragma unroll
-    for (int i = 0; i < WVec<R>::N; ++i) r[i] = v[i];
-}
-template <typename R> __device__ inline void w_st(R* p, R const (&r)[WVec<R>::N]) {
-    using V = R __attribute__((ext_vector_type(WVec<R>::N)));
-    V v;
-#pragma unroll
-    for (int i = 0; i < WVec<R>::N; ++i) v[i] = r[i];
-    __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
-}
-
-// the terms of one right-hand side in the work group's slice of LDS, added in slot order: slot m belongs to column (m / ILV) % LN for plans that keep
-// ILV rows of a column together (tfq_device.hpp: ilv_offset), to column m % LN otherwise
-template <int LN, int VEC, int T, int ILV>
-__device__ inline double w_ordered_sum(double const* sp, int j) {
-    constexpr int terms = (T * VEC) / LN;
-    double sum = 0;
-    for (int n = 0; n < terms; ++n) sum += ILV ? sp[((n / ILV) * LN + j) * ILV + n % ILV] : sp[n * LN + j];
-    return sum;
-}
+// geometry, 16-byte accesses and the ordered sum: tfq_stream.hpp (WGeo, w_ld, w_st, w_ordered_sum)
 
 // ---- per chunk: X0 := x, R := B - Y, {|r|^2, |b|^2} -------------------------------------------------------------------------------
 // one pass: reads x, Y and the B block under each X block (where there is one), writes X0 and R.  Never gated: it runs in front of the solve
