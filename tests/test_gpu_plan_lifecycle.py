@@ -1,8 +1,10 @@
 """The transitions of a plan's host state that no other test walks, through the C-ABI on the GPU: a second bufferSize with another block
 shape, a second setBuffer, keepOperator(0) after patches, block lists that grow, a user-operator plan that changes its shape, the prepared
-multiply orders, and destroyPlan / DestroyHandle in every one of these states.  The yardstick is a FRESH plan that is given the same final
+multiply orders, destroyPlan / DestroyHandle in every one of these states, and (8) a second bufferSize and a second setBuffer while
+everything that tfqmrgpu_ext.h sections 10 to 17 keep in a plan is alive.  The yardstick is a FRESH plan that is given the same final
 inputs: status, iteration count, bound history, residual, X, M^-1 and the number of unit matrices are the same bits (np.array_equal).
-Fixture: tests/golden/fd_4x4_2d (109 block rows of 4 x 4 blocks, 849 blocks of A).  Needs an MI355X (`pytest -m gpu`)."""
+Fixture: tests/golden/fd_4x4_2d (109 block rows of 4 x 4 blocks, 849 blocks of A); 8: a truncated stencil of 16 block rows.  Needs an
+MI355X (`pytest -m gpu`)."""
 import ctypes as C
 
 import numpy as np
@@ -243,3 +245,155 @@ def test_destroy_a_handle_with_a_vote_buffer():
         assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, cb, None) == 0
         assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, cb, None) == 0
         assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, T.REDUCE_CB(0), None) == 0
+
+
+# ---- 8. a second bufferSize and a second setBuffer with everything of sections 10 to 17 alive ---------------------------------------------------
+# What a plan keeps for these calls is sized or cut by the layout (the scratch of the residual, the leak listing and its device copy, the
+# records of the leak map and of the drop cost, M^-1) or holds values of one buffer (X0 and R of a warm solve, the kept starts and the scratch
+# of their projection, the kept A).  Each of them is built by its first call and found there by every later one: one that outlived its
+# layout would be read and written with the new shape.
+WARM_MAXIT = 8
+
+
+@pytest.fixture(scope="module")
+def stencils():
+    """{LN: the small truncated stencil of test_gpu_truncation_leak.py with 4 x LN right-hand-side blocks}: 16 block rows, one full block
+    column and two with leak positions.  The patterns do not depend on LN: one plan serves both"""
+    prs = {LN: PR.stencil_2d(4, 4, 4, LN, ncols=3, seed=404, radius=[None, 1.1, 2.3]) for LN in (4, 8)}
+    for name in ("rowPtrA", "colIndA", "rowPtrX", "colIndX", "rowPtrB", "colIndB"):
+        assert np.array_equal(getattr(prs[4], name), getattr(prs[8], name)), name
+    assert prs[4].mb == 16 and np.array_equal(prs[4].A, prs[8].A)
+    return prs
+
+
+def _lay_out(s, LN, prec, kept):
+    """bufferSize, what the caller asks for (it outlives every later bufferSize), a new workspace"""
+    nbytes = s.buffer_size(4, LN, prec)
+    if kept:                                                             # M^-1 and the kept copy of the caller's A exist as well
+        s.set_preconditioner(BJ)
+        s.keep_operator(True)
+    s.new_buffer(nbytes)
+    return nbytes
+
+
+def _left(s, status, prec):
+    info = s.get_info()
+    out = dict(status=status, iterations=info["iterations"], residual=info["residual"], flops=info["flops"], bounds=s.bound_history(),
+               X=s.get_matrix())
+    if prec == "m":
+        out["refinement"], out["cycle_iterations"] = s.refinement_history(with_iterations=True)
+    return out
+
+
+def _warm(s, prec):
+    return (s.refine_from if prec == "m" else s.solve_from)(KO.TOL[prec], WARM_MAXIT)
+
+
+def _everything_alive(s, pr, prec, kept):
+    """on a laid-out plan with a buffer: every call of sections 10 to 17 once, so that each library-owned piece exists; all results"""
+    out = {}
+    cplx = lambda seed, shape: PR.hashed_uniform(seed, shape) - 0.5 + 1j * (PR.hashed_uniform(seed + 1, shape) - 0.5)   # noqa: E731
+    s.set_matrix("A", pr.A)
+    s.set_matrix("B", pr.B)
+    out["solve"] = _left(s, s.solve(KO.TOL[prec], WARM_MAXIT), prec)
+    if kept:
+        out["Minv"], out["n_identity"] = s.get_preconditioner()
+    out["residual"], out["leak"], out["map"], out["drop"] = s.residual(), s.truncation_leak(), s.leak_map(), s.drop_cost()
+    s.keep_starts(2)
+    s.push_start()
+    s.set_matrix("B", pr.B[:, :, ::-1] * (0.5 - 0.25j))
+    out["solve2"] = _left(s, s.solve(KO.TOL[prec], WARM_MAXIT), prec)
+    s.push_start()
+    out["starts"] = (s.start_count(), s.start_depth())
+    s.set_matrix("B", pr.B + 0.3 * cplx(51, pr.B.shape))                # not in the span of the two: the warm solve has work to do
+    out["project"] = s.project_start()
+    out["projected"] = s.get_matrix()
+    out["warm"] = _left(s, _warm(s, prec), prec)
+    listed = np.arange(0, pr.nnzbX, 3, dtype=np.int32)
+    s.set_blocks("X", listed, cplx(31, (len(listed), pr.LM, pr.LN)))
+    out["listed"] = s.get_matrix()
+    # X from a second, smaller plan of the same block shape: every block of this plan takes a block of that one, every fifth is zero
+    small = PR.stencil_2d(4, 4, pr.LM, pr.LN, ncols=3, seed=405, radius=[None, 1.1, 1.1])
+    assert small.nnzbX < pr.nnzbX
+    old = (np.arange(pr.nnzbX, dtype=np.int32) * 7) % small.nnzbX
+    old[::5] = -1
+    with _Plan() as src:
+        src.create_plan(small)
+        src.new_buffer(src.buffer_size(pr.LM, pr.LN, "z"))
+        src.set_matrix("X", cplx(41, (small.nnzbX, pr.LM, pr.LN)))
+        s.carry_from(src, "X", old)
+        out["carried"] = s.get_matrix()
+    return out
+
+
+def _flat(d, prefix=""):
+    out = {}
+    for k, v in d.items():
+        out.update(_flat(v, prefix + k + ".") if isinstance(v, dict) else {prefix + k: v})
+    return out
+
+
+def _same_entries(got, want):
+    got, want = _flat(got), _flat(want)
+    print("everything alive:", {k: got[k] for k in got if k.split(".")[-1] in ("status", "iterations", "starts", "n_leak_blocks", "n_leak_pairs", "worst")})
+    assert got.keys() == want.keys()
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+    assert want["starts"] == (2, 2) and min(want["solve.iterations"], want["warm.iterations"]) >= 1 and want["leak.n_leak_blocks"] > 0
+
+
+@pytest.fixture(scope="module")
+def alive_fresh(stencils):
+    """the yardsticks, each computed once: (LN, precision, kept) -> what a plan that only ever saw this layout leaves behind"""
+    cache = {}
+
+    def get(LN, prec, kept):
+        if (LN, prec, kept) not in cache:
+            with _Plan() as s:
+                s.create_plan(stencils[LN])
+                _lay_out(s, LN, prec, kept)
+                cache[LN, prec, kept] = _everything_alive(s, stencils[LN], prec, kept)
+        return cache[LN, prec, kept]
+    return get
+
+
+# each group of the plan's state grows and shrinks, and the storage type changes under it
+STEPS = [((4, "z"), (8, "z")), ((8, "z"), (4, "c")), ((4, "c"), (8, "m")), ((8, "m"), (4, "z"))]
+
+
+@pytest.mark.parametrize("kept", [False, True], ids=["plain", "kept"])
+@pytest.mark.parametrize("before,after", STEPS, ids=["4z-8z", "8z-4c", "4c-8m", "8m-4z"])
+def test_second_buffer_size_with_everything_alive(stencils, alive_fresh, before, after, kept):
+    (LN0, prec0), (LN1, prec1) = before, after
+    want = alive_fresh(LN1, prec1, kept)
+    with _Plan() as s:
+        s.create_plan(stencils[LN0])
+        _lay_out(s, LN0, prec0, kept)
+        _same_entries(_everything_alive(s, stencils[LN0], prec0, kept), alive_fresh(LN0, prec0, kept))
+        nbytes = s.buffer_size(4, LN1, prec1)
+        assert (s.start_count(), s.start_depth()) == (0, 2)              # the starts go with their buffer, the depth is the caller's
+        assert T.lib.tfqmrgpuExt_leakUnits(s.plan, None) == 0            # the listing of the old shape is gone ...
+        assert s.leak_counts() == (want["leak"]["n_leak_blocks"], want["leak"]["n_leak_pairs"])   # ... and is built again on demand
+        s.new_buffer(nbytes)
+        _same_entries(_everything_alive(s, stencils[LN1], prec1, kept), want)
+
+
+@pytest.mark.parametrize("kept", [False, True], ids=["plain", "kept"])
+@pytest.mark.parametrize("prec", ["z", "c", "m"])
+def test_second_set_buffer_with_everything_alive(stencils, alive_fresh, prec, kept):
+    pr = stencils[4]
+    want = alive_fresh(4, prec, kept)
+    warm = T.lib.tfqmrgpuExt_refineFrom if prec == "m" else T.lib.tfqmrgpuExt_solveFrom
+    with _Plan() as never:                                               # a plan whose A was never set
+        never.create_plan(pr)
+        _lay_out(never, 4, prec, kept)
+        refused = warm(never.handle, never.plan, KO.TOL[prec], WARM_MAXIT)
+    assert T.decode(refused)[::2] == (14, ord("A"))
+    with _Plan() as s:
+        s.create_plan(pr)
+        nbytes = _lay_out(s, 4, prec, kept)
+        _same_entries(_everything_alive(s, pr, prec, kept), want)
+        s.new_buffer(nbytes)
+        assert (s.start_count(), s.start_depth()) == (0, 2)
+        assert warm(s.handle, s.plan, KO.TOL[prec], WARM_MAXIT) == refused   # the new buffer holds no A, and no X0 of the old one
+        _same_entries(_everything_alive(s, pr, prec, kept), want)

@@ -1,9 +1,9 @@
 // C-ABI of libtfQMRgpu.so (include/tfqmrgpu.h, include/tfqmrgpu_ext.h) for MI355X.
 // Mirrors the entry points of real-space/tfQMRgpu tfQMRgpu/source/tfqmrgpu.cu (same names,
 // argument meaning and status codes); the implementation behind them is this library's own.
-// The solve itself -- the tfQMR driver, the refinement -- is tfq_solve.cpp; the preconditioner's set-up and the state of the A in the
-// buffer are tfq_precond_host.cpp; the calls that grade the caller's system (tfqmrgpu_ext.h sections 10 to 13) are tfq_grade_host.cpp; the start projection
-// (section 17) is tfq_project_host.cpp.
+// The solve itself -- the tfQMR driver, the refinement, the reset of Plan::last -- is tfq_solve.cpp; the preconditioner's set-up, the state of
+// the A in the buffer and the ends of Plan::layout (bufferSize) and Plan::held (bufferSize, setBuffer) are tfq_precond_host.cpp; the calls that
+// grade the caller's system (tfqmrgpu_ext.h sections 10 to 13) are tfq_grade_host.cpp; the start projection (section 17) is tfq_project_host.cpp.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -293,13 +293,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     tfqmrgpuStatus_t st;
     try { st = layoutBuffer(*p, LM, LN, prec); }
     catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
-    p->opScratch.release();                // sized for the previous block shape
-    p->residualScratch.release();          // ... and the previous chunks
-    p->leak = LeakListing{}; p->leakDev.release(); p->leakMapRec.release();   // ... and the work units of the previous block shape
-    p->dropDev.release();                  // ... and the records of the previous block shape
-    p->warm.release();                     // ... and X0 and R of the previous block shape
-    starts_release(*p);                    // ... and the kept starts and their scratch
-    a_new_layout(*p);
+    a_new_layout(*p);                      // whatever was sized or cut for the previous layout, or held values of its buffer, ends here
     p->precision = prec;
     p->buffer = nullptr;
     *pBufferSizeInBytes = p->bufferBytes;
@@ -314,9 +308,7 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_setBuffer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);        // bufferSize has not been called
     hipStream_t const s = (hipStream_t)h->stream;
     p->buffer = (char*)pBuffer;
-    a_new_buffer(*p);
-    p->warm.release();                     // (X0 and R of a warm solve belong to the X of the old buffer)
-    starts_release(*p);                    // (... and so do the kept starts)
+    a_new_buffer(*p);                      // whatever held values of the old buffer, or said what it holds, ends here
     auto at = [&](Window const& w) { return (void*)(p->buffer + w.offset); };
     for (auto const& l : indexLists(*p))   // (tfq_plan.cpp: the windows were sized from the same list)
         if (auto const st = upload(at(*l.window), l.data, l.bytes, s)) return st;
@@ -487,8 +479,8 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_getInfo(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPl
     if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     int any = 0;
     if (residuum_reached)    { ++any; *residuum_reached = p->residuum_reached; }
-    if (iterations_needed)   { ++any; *iterations_needed = p->iterations_needed; }
-    if (flops_performed)     { ++any; *flops_performed = p->flops_performed; }
+    if (iterations_needed)   { ++any; *iterations_needed = p->last.iterations_needed; }
+    if (flops_performed)     { ++any; *flops_performed = p->last.flops_performed; }
     if (flops_performed_all) { ++any; *flops_performed_all = p->flops_performed_all; }
     return any ? TFQMRGPU_STATUS_SUCCESS : TFQMRGPU_STATUS_NO_INFO_PASSED;
 }
@@ -566,10 +558,11 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_c(int mb, int ldA, int ldB,
 // ---- extensions (include/tfqmrgpu_ext.h) --------------------------------------------------------------
 
 // the three views of a solve's profile: all launches that did work, those that returned at once, those of the first iteration
-static tfqmrgpuStatus_t get_profile(tfqmrgpuBsrsvPlan_t plan, int64_t const (Plan::*count)[16], double const (Plan::*ms)[16], int64_t* launches, double* milliseconds) {
+static tfqmrgpuStatus_t get_profile(tfqmrgpuBsrsvPlan_t plan, Plan::Profile const Plan::Last::*view, int64_t* launches, double* milliseconds) {
     auto p = asPlan(plan);
     if (!p || !launches || !milliseconds) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    for (int k = 0; k < TFQMRGPU_PROFILE_CLASSES; ++k) { launches[k] = (p->*count)[k]; milliseconds[k] = (p->*ms)[k]; }
+    auto const& v = p->last.*view;
+    for (int k = 0; k < TFQMRGPU_PROFILE_CLASSES; ++k) { launches[k] = v.launches[k]; milliseconds[k] = v.ms[k]; }
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
@@ -587,8 +580,8 @@ tfqmrgpuStatus_t tfqmrgpuExt_planView(tfqmrgpuBsrsvPlan_t plan, tfqmrgpuPlanView
 int32_t tfqmrgpuExt_getBoundHistory(tfqmrgpuBsrsvPlan_t plan, double* bound2, int32_t capacity) {
     auto p = asPlan(plan);
     if (!p) return -1;
-    auto const n = int32_t(p->boundHistory.size());
-    for (int32_t i = 0; i < std::min(n, capacity); ++i) if (bound2) bound2[i] = p->boundHistory[i];
+    auto const n = int32_t(p->last.boundHistory.size());
+    for (int32_t i = 0; i < std::min(n, capacity); ++i) if (bound2) bound2[i] = p->last.boundHistory[i];
     return n;
 }
 
@@ -600,15 +593,15 @@ tfqmrgpuStatus_t tfqmrgpuExt_setProfiling(tfqmrgpuBsrsvPlan_t plan, int on) {
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getProfile(tfqmrgpuBsrsvPlan_t plan, int64_t* launches, double* milliseconds) {
-    return get_profile(plan, &Plan::profLaunches, &Plan::profMs, launches, milliseconds);
+    return get_profile(plan, &Plan::Last::all, launches, milliseconds);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getProfileGated(tfqmrgpuBsrsvPlan_t plan, int64_t* launches, double* milliseconds) {
-    return get_profile(plan, &Plan::profGatedLaunches, &Plan::profGatedMs, launches, milliseconds);
+    return get_profile(plan, &Plan::Last::gated, launches, milliseconds);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getProfileFirst(tfqmrgpuBsrsvPlan_t plan, int64_t* launches, double* milliseconds) {
-    return get_profile(plan, &Plan::profFirstLaunches, &Plan::profFirstMs, launches, milliseconds);
+    return get_profile(plan, &Plan::Last::first, launches, milliseconds);
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_getMultiplyKernel(tfqmrgpuBsrsvPlan_t plan, char* name, int32_t capacity) {
@@ -630,10 +623,10 @@ tfqmrgpuStatus_t tfqmrgpuExt_setThreeProductMultiply(tfqmrgpuBsrsvPlan_t plan, i
 int32_t tfqmrgpuExt_getRefinementHistory(tfqmrgpuBsrsvPlan_t plan, double* residual, int32_t* iterations, int32_t capacity) {
     auto p = asPlan(plan);
     if (!p) return -1;
-    auto const n = int32_t(p->cycleResidual.size());
+    auto const n = int32_t(p->last.cycleResidual.size());
     for (int32_t i = 0; i < std::min(n, capacity); ++i) {
-        if (residual) residual[i] = p->cycleResidual[i];
-        if (iterations) iterations[i] = (size_t(i) < p->cycleIterations.size()) ? p->cycleIterations[i] : 0;   // the last entry has no solve behind it
+        if (residual) residual[i] = p->last.cycleResidual[i];
+        if (iterations) iterations[i] = (size_t(i) < p->last.cycleIterations.size()) ? p->last.cycleIterations[i] : 0;   // the last entry has no solve behind it
     }
     return n;
 }
@@ -793,7 +786,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_pushStart(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPla
 
 int32_t tfqmrgpuExt_startCount(tfqmrgpuBsrsvPlan_t plan) {
     auto p = asPlan(plan);
-    return p ? p->startCount : 0;
+    return p ? p->held.startCount : 0;
 }
 
 int32_t tfqmrgpuExt_startDepth(tfqmrgpuBsrsvPlan_t plan) {

@@ -23,13 +23,13 @@ tfqmrgpuStatus_t operands_ready(Plan const& p, bool const needA) {
     if (nullptr == p.buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     if (p.opFn) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);         // a user-defined operator is the caller's to apply
     if (!needA) return TFQMRGPU_STATUS_SUCCESS;
-    if (!p.haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
-    if (TFQMRGPU_PRECOND_NONE != p.precondInA && !kept_is_callers_a(p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone; keepOperator keeps it
+    if (!p.held.haveA) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'A');
+    if (TFQMRGPU_PRECOND_NONE != p.held.precondInA && !kept_is_callers_a(p)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);   // the caller's A is gone; keepOperator keeps it
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
 void const* callers_a(Plan const& p, DevPlan const& d) {
-    return (TFQMRGPU_PRECOND_NONE != p.precondInA) ? (void const*)kept_a(p).a : d.A;
+    return (TFQMRGPU_PRECOND_NONE != p.held.precondInA) ? (void const*)kept_a(p).a : d.A;
 }
 
 namespace {
@@ -76,7 +76,7 @@ tfqmrgpuStatus_t fetch(hipStream_t s, Result& a, Result* b = nullptr) {
 
 // ---- the leak listing (sections 11 and 12): the host analysis, once per plan and block shape
 tfqmrgpuStatus_t leak_host(Plan& p) {
-    auto& l = p.leak;
+    auto& l = p.layout.leak;
     if (l.built) return TFQMRGPU_STATUS_SUCCESS;
     try {
         if (p.cscPtr.empty()) a_by_column(p.nRows, p.colOfA, p.cscPtr, p.cscBlock);
@@ -89,15 +89,15 @@ tfqmrgpuStatus_t leak_host(Plan& p) {
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
-// the listing on the device, Plan::leakDev.  ONE copy for truncationLeak and leakMap: whichever comes first uploads it
+// the listing on the device, Plan::layout.leakDev.  ONE copy for truncationLeak and leakMap: whichever comes first uploads it
 enum { kLeakPairs, kLeakPos, kLeakUnit, kLeakCol, kLeakRec, kLeakSum, kLeakPieces };
 tfqmrgpuStatus_t leak_device(Plan& p, size_t (&at)[kLeakPieces], hipStream_t s) {
-    auto const& l = p.leak;
+    auto const& l = p.layout.leak;
     Piece const piece[kLeakPieces] = {
         {l.pairs.data(), l.pairs.size() * 4}, {l.posStart.data(), l.posStart.size() * 4}, {l.unitFirst.data(), l.unitFirst.size() * 4},
         {l.colUnitPtr.data(), l.colUnitPtr.size() * 4},
         {nullptr, l.nUnits() * size_t(p.LN) * sizeof(double)}, {nullptr, size_t(p.nCols) * size_t(p.LN) * sizeof(double)}};
-    return dev_listing(p.leakDev, piece, at, s);
+    return dev_listing(p.layout.leakDev, piece, at, s);
 }
 
 // a pattern of sections 12 and 13 into malloc'ed arrays for the caller (tfqmrgpuExt_freeGrownPattern releases them)
@@ -134,8 +134,8 @@ tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
     size_t const nRec = size_t(d.nChunks) * 2 * p->LN, nCol = size_t(p->nCols) * 2 * p->LN;
     Result col;
     if (!col.size(nCol)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
-    if (auto const st = p->residualScratch.reserve(std::max<size_t>((nRec + nCol) * sizeof(double), 256))) return st;
-    double* const rec = p->residualScratch.as<double>();
+    if (auto const st = p->layout.residualScratch.reserve(std::max<size_t>((nRec + nCol) * sizeof(double), 256))) return st;
+    double* const rec = p->layout.residualScratch.as<double>();
     col.dev = rec + nRec;
     residual_launch(d, callers_a(*p, d), rec, rec + nRec, s);
     if (auto const st = fetch(s, col)) return st;
@@ -165,14 +165,14 @@ tfqmrgpuStatus_t tfqmrgpuExt_truncationLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsr
     // everything but leak2 depends on the patterns alone: plan and bufferSize suffice
     if (leak2) if (auto const st = operands_ready(*p, true)) return st;
     if (auto const st = leak_host(*p)) return st;
-    auto& l = p->leak;
+    auto& l = p->layout.leak;
     if (leak2) {
         hipStream_t const s = (hipStream_t)h->stream;
         Result col; col.to = leak2;
         if (!col.size(size_t(p->nCols) * size_t(p->LN))) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
         size_t at[kLeakPieces];
         if (auto const st = leak_device(*p, at, s)) return st;
-        char* const dev = p->leakDev.as<char>();
+        char* const dev = p->layout.leakDev.as<char>();
         col.dev = dev + at[kLeakSum];
         DevPlan const d = resolve_callers(*p);                      // 'm': the double copies of X and A
         leak_launch(d, callers_a(*p, d), uint32_t(l.nUnits()), (uint32_t const*)(dev + at[kLeakPairs]), (uint32_t const*)(dev + at[kLeakPos]),
@@ -194,7 +194,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_
     // everything but pos2 depends on the patterns alone, as in section 11
     if (pos2) if (auto const st = operands_ready(*p, true)) return st;
     if (auto const st = leak_host(*p)) return st;
-    auto const& l = p->leak;
+    auto const& l = p->layout.leak;
     size_t const LN = size_t(p->LN), nPos = l.nPositions();
     if ((rows || cols || pos2) && capacity < uint64_t(nPos)) {      // the caller learns how much room the arrays need, and nothing else
         if (nLeakBlocks) *nLeakBlocks = uint64_t(nPos);
@@ -206,11 +206,11 @@ tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_
         if (!rec.size(nPos * LN)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
         size_t at[kLeakPieces];
         if (auto const st = leak_device(*p, at, s)) return st;      // the listing of section 11, uploaded once for both calls
-        if (auto const st = p->leakMapRec.reserve(std::max<size_t>(nPos * LN * sizeof(double), 256))) return st;
-        char* const dev = p->leakDev.as<char>();
-        rec.dev = p->leakMapRec.ptr;
+        if (auto const st = p->layout.leakMapRec.reserve(std::max<size_t>(nPos * LN * sizeof(double), 256))) return st;
+        char* const dev = p->layout.leakDev.as<char>();
+        rec.dev = p->layout.leakMapRec.ptr;
         DevPlan const d = resolve_callers(*p);                      // 'm': the double copies of X and A
-        leak_map_launch(d, callers_a(*p, d), uint32_t(nPos), (uint32_t const*)(dev + at[kLeakPairs]), (uint32_t const*)(dev + at[kLeakPos]), p->leakMapRec.as<double>(), s);
+        leak_map_launch(d, callers_a(*p, d), uint32_t(nPos), (uint32_t const*)(dev + at[kLeakPairs]), (uint32_t const*)(dev + at[kLeakPos]), p->layout.leakMapRec.as<double>(), s);
         if (auto const st = fetch(s, rec)) return st;
     }
     if (rows) for (size_t n = 0; n < nPos; ++n) rows[n] = int32_t(l.posRow[n]);
@@ -225,7 +225,7 @@ tfqmrgpuStatus_t tfqmrgpuExt_growPattern(tfqmrgpuBsrsvPlan_t plan, uint64_t nTak
     *grown = tfqmrgpuGrownPattern_t{};
     if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
     if (auto const st = leak_host(*p)) return st;
-    auto const& l = p->leak;
+    auto const& l = p->layout.leak;
     GrownPattern g;
     try {
         int const bad = grow_pattern(g, p->nRows, p->nCols, p->nnzbX, p->rowOfX.data(), p->col32.data(), p->original_bsrColIndX.data(),
@@ -257,13 +257,13 @@ tfqmrgpuStatus_t tfqmrgpuExt_dropCost(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
     } catch (std::bad_alloc const&) { p->drop = DropListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     hipStream_t const s = (hipStream_t)h->stream;
     auto const& l = p->drop;
-    // the listing on the device, Plan::dropDev
+    // the listing on the device, Plan::layout.dropDev
     enum { kStart, kAOf, kXOf, kCost, kWeight, kPieces };
     Piece const piece[kPieces] = {{l.start.data(), l.start.size() * 4}, {l.aOf.data(), l.aOf.size() * 4}, {l.xOf.data(), l.xOf.size() * 4},
                                   {nullptr, n * sizeof(double)}, {nullptr, n * sizeof(double)}};
     size_t at[kPieces];
-    if (auto const st = dev_listing(p->dropDev, piece, at, s)) return st;
-    char* const dev = p->dropDev.as<char>();
+    if (auto const st = dev_listing(p->layout.dropDev, piece, at, s)) return st;
+    char* const dev = p->layout.dropDev.as<char>();
     cost.dev = dev + at[kCost]; weight.dev = dev + at[kWeight];
     DevPlan const d = resolve_callers(*p);                          // 'm': the double copies of X and A
     // the kernel writes the record of a block at the caller's index of that block: the copy-out is a plain copy
@@ -294,9 +294,9 @@ tfqmrgpuStatus_t tfqmrgpuExt_shrinkPattern(tfqmrgpuBsrsvPlan_t plan, uint64_t nD
 // how the listing is cut: work units per compressed block column
 int64_t tfqmrgpuExt_leakUnits(tfqmrgpuBsrsvPlan_t plan, uint32_t* unitsPerColumn) {
     auto p = asPlan(plan);
-    if (!p || !p->leak.built) return 0;
-    if (unitsPerColumn) for (uint32_t c = 0; c < p->nCols; ++c) unitsPerColumn[c] = p->leak.colUnitPtr[c + 1] - p->leak.colUnitPtr[c];
-    return int64_t(p->leak.nUnits());
+    if (!p || !p->layout.leak.built) return 0;
+    if (unitsPerColumn) for (uint32_t c = 0; c < p->nCols; ++c) unitsPerColumn[c] = p->layout.leak.colUnitPtr[c + 1] - p->layout.leak.colUnitPtr[c];
+    return int64_t(p->layout.leak.nUnits());
 }
 
 } // extern "C"

@@ -22,7 +22,8 @@ inline tfqmrgpuStatus_t err(int code, int line = 0, int key = 0) {
 inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
 // ---- library-owned memory: every allocation the library makes for itself has ONE owner, whose destructor releases it.  destroyPlan,
-// DestroyHandle and multiplyRelease are `delete`; a new member of this kind needs no line anywhere else
+// DestroyHandle and multiplyRelease are `delete`.  What in a plan must not outlive a layout or a buffer stands in the group that bufferSize
+// or setBuffer ends with one assignment (Plan::Layout, Plan::Held): a new member of this kind needs a line in its group and nowhere else
 struct DevMem {     // device memory (hipMalloc), move-only
     void* ptr = nullptr;
     size_t bytes = 0;
@@ -258,80 +259,78 @@ struct Plan {
     int shadowMode = TFQMRGPU_SHADOW_HASH;
     bool v3IsHash = false;             // the buffer's v3 holds the counter-based hash (set by setBuffer, cleared by a user-supplied vector)
     bool threeProducts = false;        // tfqmrgpuExt_setThreeProductMultiply: Gauss' three real products per complex one in the double multiplies
-    std::vector<double> cycleResidual; // 'm': relative residual (double arithmetic) in front of every inner solve and at the end
-    std::vector<int32_t> cycleIterations; // 'm': float iterations of every inner solve
-    int refinementCycles = 0;
-    // user-defined operator (tfqmrgpu_ext.h section 5): callback, and library-owned device scratch
-    // [xu | yu | i2u | colindx in the caller's block order]
-    void* opFn = nullptr; void* opCtx = nullptr;
-    DevMem opScratch;                  // (tfq_solve.cpp: op_scratch; sized by the block shape: released by bufferSize)
+    void* opFn = nullptr; void* opCtx = nullptr;   // user-defined operator (tfqmrgpu_ext.h section 5): the callback
     // block-Jacobi right preconditioner (tfqmrgpu_ext.h section 7)
     std::vector<uint32_t> diagOfRow;   // [nRows] the diagonal block of each block row of A, ~0u: the pattern has none
     std::vector<uint32_t> colOfA;      // [nnzbA] block column of each block of A
+    std::vector<uint32_t> rowOfA;      // [nnzbA] block row of each block of A (for the truncation leak, section 11)
+    std::vector<uint32_t> cscPtr, cscBlock;    // the blocks of A grouped by block column, built at the first setBlocks('A') into a kept copy or the first leak listing
     int precondKind = TFQMRGPU_PRECOND_NONE;     // what the caller asked for
-    DevMem precond;                    // library-owned device memory [M^-1 | diagOfRow | colOfA | counter | flags], allocated at the first preconditioned solve
     bool keepA = false;                // tfqmrgpuExt_keepOperator: keep the caller's own A next to the scaled one (tfqmrgpu_ext.h section 9)
-    DevMem keepList;                   // device copy of [dirty rows | blocks of the dirty columns] of a partial set-up, grown on demand
-
-    // ---- the state of the A in the buffer: what it holds, and what is stale.  Written by the transitions of tfq_precond_host.cpp
-    // (a_new_layout ... a_restored) and by nobody else
-    bool haveA = false;                // a whole setMatrix('A') has succeeded on this buffer
-    int precondInA = TFQMRGPU_PRECOND_NONE;      // what the A in the buffer has been scaled with (NONE: it is the caller's A)
-    int32_t precondIdentity = 0;       // block rows whose M_ii is the unit matrix (no diagonal block, or a singular one), as of the last set-up
-    double mixedFloor = 0;             // 'm': the gain at which the first float solve of this plan's last solve ran into its floor (0: not known; forgotten with a new A)
-    DevMem aKept;                      // library-owned device copy of the A window as it was before it was scaled ('m': the double A, then the float A);
-                                       // it is the caller's A while precondInA != NONE, stale otherwise
-    std::vector<uint8_t> dirtyRow, dirtyCol;   // [nRows] since the last set-up setBlocks('A') has written: the diagonal block of this row | a block of this column
-    bool anyDirty = false;
-    std::vector<uint32_t> cscPtr, cscBlock;    // the blocks of A grouped by block column, built at the first such setBlocks('A')
-
-    // setBlocks / getBlocks (tfqmrgpu_ext.h section 8): library-owned device copy of the caller's block list, grown on demand
-    DevMem blockList;
-
-    // tfqmrgpuExt_residual (tfqmrgpu_ext.h section 10): library-owned scratch [nChunks][2][LN] + [nCols][2][LN] doubles, allocated at the
-    // first call (sized by the block shape and the chunks: released by bufferSize)
-    DevMem residualScratch;
-
-    // tfqmrgpuExt_truncationLeak (tfqmrgpu_ext.h section 11): the listing (built at the first call; its work units are cut by the block
-    // shape and its X indices are the internal ones: released by bufferSize) and its device copy [pairs | posStart | unitFirst |
-    // colUnitPtr | records [nUnits][LN] | column sums [nCols][LN]], uploaded at the first call that asks for leak2
-    std::vector<uint32_t> rowOfA;      // [nnzbA] block row of each block of A
-    LeakListing leak;
-    DevMem leakDev;
-    // tfqmrgpuExt_leakMap (tfqmrgpu_ext.h section 12): one [LN] record of doubles per leak position, allocated at the first call that asks
-    // for pos2; the listing on the device is leakDev's (sized by the block shape and the positions: released by bufferSize)
-    DevMem leakMapRec;
-    // tfqmrgpuExt_dropCost (tfqmrgpu_ext.h section 13): the pairs grouped by X block (built at the first call that needs it; patterns
-    // only, it outlives bufferSize) and its device copy [start | aOf | xOf | cost records [nnzbX][LN] | weight records [nnzbX][LN]],
-    // allocated and uploaded by the first call that asks for an array (sized by the block shape: released by bufferSize)
-    DropListing drop;
-    DevMem dropDev;
-    // tfqmrgpuExt_solveFrom (tfqmrgpu_ext.h section 14): library-owned [X0 | R], two X-shaped vectors of the plan's storage type, allocated
-    // by the first call (sized by the block shape, and holding values of the buffer they were taken from: released by bufferSize and setBuffer).
-    // tfqmrgpuExt_refineFrom (section 16) on an 'm' plan: the same two vectors, of doubles
-    DevMem warm;
+    int32_t precondIdentity = 0;       // block rows whose M_ii is the unit matrix (no diagonal block, or a singular one), as of the last set-up; outlives bufferSize and setBuffer
+    double mixedFloor = 0;             // 'm': the gain at which the first float solve of this plan's last solve ran into its floor (0: not known; forgotten with a new A, NOT with a new layout: a_new_layout)
+    DropListing drop;                  // tfqmrgpuExt_dropCost (section 13): the pairs grouped by X block, built at the first call that needs it; patterns only, it outlives bufferSize
     void* warmR = nullptr;             // not null only while a warm solve runs: resolve() hands it to the driver as DevPlan::R
-    // tfqmrgpuExt_carry (tfqmrgpu_ext.h section 15), on the DESTINATION plan: library-owned device copy of the composed block list
-    // (tfq_carry_host.cpp: carry_compose), grown on demand
-    DevMem carryList;
-    // start projection (tfqmrgpu_ext.h section 17; tfq_project_host.cpp): the ring of kept starts -- startDepth X-shaped vectors in the plan's
-    // storage type and internal order, start i (0: the newest) in slot (startHead + i) % startDepth, allocated by the first pushStart -- and
-    // the scratch of projectStart [images W | records | gamma | nUsed], allocated by its first call.  Both hold values of one buffer and are
-    // sized by the block shape: released by bufferSize and setBuffer (starts_release); the depth stays, as the preconditioner kind does
-    int startDepth = 0, startCount = 0, startHead = 0;
-    DevMem startMem, projectMem;
+    int startDepth = 0;                // tfqmrgpuExt_keepStarts (section 17): the depth of the ring of kept starts; it stays, as the preconditioner kind does
 
-    // ---- results of the last solve -------------------------------------------------------------
-    double residuum_reached = 0, flops_performed = -1, flops_performed_all = 0;
-    int iterations_needed = -1;
-    std::vector<double> boundHistory;
+    // ---- device lists that only grow (reserve), each filled again by every call that reads it: they outlive layouts and buffers
+    DevMem keepList;                   // [dirty rows | blocks of the dirty columns] of a partial set-up (tfq_precond_host.cpp: precond_update)
+    DevMem blockList;                  // setBlocks / getBlocks (tfqmrgpu_ext.h section 8): the caller's block list
+    DevMem carryList;                  // tfqmrgpuExt_carry (section 15), on the DESTINATION plan: the composed block list (tfq_carry_host.cpp: carry_compose)
+
+    // ---- of the layout: sized or cut by (LM, LN, precision) and the chunk tables, built by the first call that needs it and found there by
+    // every later one.  bufferSize ends it (tfq_precond_host.cpp: a_new_layout), with `layout = Layout{}`
+    struct Layout {
+        DevMem opScratch;              // user-defined operator: [xu | yu | i2u | colindx in the caller's block order] (tfq_solve.cpp: op_scratch)
+        DevMem residualScratch;        // tfqmrgpuExt_residual (section 10): [nChunks][2][LN] + [nCols][2][LN] doubles
+        // tfqmrgpuExt_truncationLeak (section 11): the listing (its work units are cut by the block shape, its X indices are the internal
+        // ones) and its device copy [pairs | posStart | unitFirst | colUnitPtr | records [nUnits][LN] | column sums [nCols][LN]], uploaded
+        // at the first call that asks for leak2
+        LeakListing leak;
+        DevMem leakDev;
+        DevMem leakMapRec;             // tfqmrgpuExt_leakMap (section 12): one [LN] record of doubles per leak position; the listing on the device is leakDev's
+        DevMem dropDev;                // tfqmrgpuExt_dropCost (section 13): Plan::drop on the device [start | aOf | xOf | cost records [nnzbX][LN] | weight records [nnzbX][LN]]
+        DevMem precond;                // block-Jacobi: [M^-1 | diagOfRow | colOfA | counter | flags], allocated at the first preconditioned solve
+    } layout;
+
+    // ---- of the buffer: values that belong to ONE registered buffer, and what that buffer holds.  bufferSize and setBuffer end it
+    // (tfq_precond_host.cpp: a_new_buffer), with `held = Held{}`
+    struct Held {
+        // tfqmrgpuExt_solveFrom (section 14): [X0 | R], two X-shaped vectors of the plan's storage type, allocated by the first call.
+        // tfqmrgpuExt_refineFrom (section 16) on an 'm' plan: the same two vectors, of doubles
+        DevMem warm;
+        // start projection (section 17; tfq_project_host.cpp): the ring of kept starts -- Plan::startDepth X-shaped vectors in the plan's storage
+        // type and internal order, start i (0: the newest) in slot (startHead + i) % startDepth, allocated by the first pushStart -- and the
+        // scratch of projectStart [images W | records | gamma | nUsed], allocated by its first call
+        DevMem startMem, projectMem;
+        int startCount = 0, startHead = 0;
+        // the state of the A in the buffer: what it holds, and what is stale.  Written by the transitions of tfq_precond_host.cpp
+        // (a_new_layout ... a_restored) and by nobody else
+        bool haveA = false;            // a whole setMatrix('A') has succeeded on this buffer
+        int precondInA = TFQMRGPU_PRECOND_NONE;  // what the A in the buffer has been scaled with (NONE: it is the caller's A)
+        DevMem aKept;                  // device copy of the A window as it was before it was scaled ('m': the double A, then the float A);
+                                       // it is the caller's A while precondInA != NONE, stale otherwise
+        std::vector<uint8_t> dirtyRow, dirtyCol;   // [nRows] since the last set-up setBlocks('A') has written: the diagonal block of this row | a block of this column
+        bool anyDirty = false;
+    } held;
+
+    // ---- of the last solve: what it leaves for getInfo, the histories and the profile.  The start of the next solve ends it
+    // (tfq_solve.cpp: reset_results), with `last = Last{}`
+    struct Profile { int64_t launches[16] = {}; double ms[16] = {}; };
+    struct Last {
+        double flops_performed = -1;   // (-1: no solve yet)
+        int iterations_needed = -1;
+        std::vector<double> boundHistory;
+        std::vector<double> cycleResidual;     // 'm': relative residual (double arithmetic) in front of every inner solve and at the end
+        std::vector<int32_t> cycleIterations;  // 'm': float iterations of every inner solve
+        int refinementCycles = 0;
+        Profile all;                   // the launches that did work
+        Profile gated;                 // launches that found the solve stopped / no probe requested
+        Profile first;                 // of `all`: the launches of the first iteration (they skip the operands that are zero there)
+    } last;
+    double residuum_reached = 0;       // of the last solve that came to its end: a solve that is refused behind its reset leaves it
+    double flops_performed_all = 0;    // over all solves
     int profiling = 0;                 // 0 off, 1 every kernel class, 2 the two fused multiplies only
-    int64_t profLaunches[16] = {};
-    double profMs[16] = {};
-    int64_t profGatedLaunches[16] = {};   // launches that found the solve stopped / no probe requested
-    double profGatedMs[16] = {};
-    int64_t profFirstLaunches[16] = {};   // of profLaunches: the launches of the first iteration (they skip the operands that are zero there)
-    double profFirstMs[16] = {};
 
     size_t nPairs() const { return pairs.size() / 2; }
 };

@@ -13,13 +13,13 @@ namespace tfq {
 // ---- the library-owned memory of a plan: one function says how large, one where
 struct PrecondMem { char* minv; uint32_t* diag; uint32_t* colA; uint32_t* counter; uint32_t* identity; size_t minvBytes; };
 size_t precond_bytes(Plan const& p);
-PrecondMem precond_mem(Plan const& p);      // the pieces of Plan::precond (allocated)
+PrecondMem precond_mem(Plan const& p);      // the pieces of Plan::layout.precond (allocated)
 
-// the kept copy of the caller's A (section 9): Plan::aKept holds the A window of the buffer, for 'm' the double A (`a`) followed by the float A (`aFloat`)
+// the kept copy of the caller's A (section 9): Plan::held.aKept holds the A window of the buffer, for 'm' the double A (`a`) followed by the float A (`aFloat`)
 struct KeptA { char* a; char* aFloat; size_t aBytes, aFloatBytes; };
 size_t kept_a_bytes(Plan const& p);
-KeptA kept_a(Plan const& p);                // the pieces of Plan::aKept (allocated)
-inline bool kept_is_callers_a(Plan const& p) { return p.keepA && p.aKept && TFQMRGPU_PRECOND_NONE != p.precondInA; }
+KeptA kept_a(Plan const& p);                // the pieces of Plan::held.aKept (allocated)
+inline bool kept_is_callers_a(Plan const& p) { return p.keepA && p.held.aKept && TFQMRGPU_PRECOND_NONE != p.held.precondInA; }
 
 // ---- the caller's operands, for the calls that read them outside of a solve (tfq_grade_host.cpp; solveFrom, refineFrom and carry of tfq_api.hip)
 // their checks in front of the first device call, in the documented order: no buffer | user-defined operator | and where the call reads A
@@ -35,9 +35,9 @@ tfqmrgpuStatus_t upload(void* dst, void const* src, size_t bytes, hipStream_t s)
 tfqmrgpuStatus_t precond_prepare(Handle& h, Plan& p);
 tfqmrgpuStatus_t precond_back(Handle& h, Plan& p);      // X := M^-1 Y
 
-// ---- the state of the A in the buffer (Plan::haveA ... Plan::cscBlock): every transition, by the call that causes it
-void a_new_layout(Plan& p);                             // bufferSize
-void a_new_buffer(Plan& p);                             // setBuffer
+// ---- the state of the A in the buffer (Plan::held, precondIdentity, mixedFloor, cscPtr, cscBlock): every transition, by the call that causes it
+void a_new_layout(Plan& p);                             // bufferSize: ends Plan::layout and Plan::held
+void a_new_buffer(Plan& p);                             // setBuffer: ends Plan::held
 void a_named(Plan& p);                                  // setMatrix('A'), before its argument checks
 void a_set_whole(Plan& p, bool ok);                     // setMatrix('A'), behind its transfer
 tfqmrgpuStatus_t a_patched(Plan& p, int32_t const* blocks, int32_t nBlocks, bool& intoKept);   // setBlocks('A'), behind its argument checks

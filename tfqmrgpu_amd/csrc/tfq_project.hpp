@@ -19,7 +19,6 @@ bool project_launch(DevPlan const& d, int k, ProjectVecs const& pv, double* rec,
 // the host side of the four calls, behind the pointer checks of the C-ABI
 tfqmrgpuStatus_t starts_keep(Plan& p, int depth);
 tfqmrgpuStatus_t starts_push(Handle& h, Plan& p);
-void starts_release(Plan& p);                                       // bufferSize, setBuffer: the starts go, the depth stays
 tfqmrgpuStatus_t starts_project(Handle& h, Plan& p, double* coefficients, int32_t* nUsed);
 #pragma GCC visibility pop
 

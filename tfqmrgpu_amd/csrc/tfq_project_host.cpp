@@ -1,7 +1,7 @@
 // Start projection (tfqmrgpu_ext.h section 17), host side: the ring of kept starts, and projectStart -- its checks in front of the first
 // device call, the images W_i = A S_i by the plan's own multiply on the caller's A, the three launches of tfq_project.hip, the copy-out.
-// Everything lives in two library-owned pieces of device memory: Plan::startMem, `depth` X-shaped vectors in the plan's storage type and
-// internal order, and Plan::projectMem [images W | records | gamma | nUsed], allocated at the first projectStart.
+// Everything lives in two library-owned pieces of device memory: Plan::held.startMem, `depth` X-shaped vectors in the plan's storage type and
+// internal order, and Plan::held.projectMem [images W | records | gamma | nUsed], allocated at the first projectStart.
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -18,33 +18,33 @@ namespace {
 size_t start_bytes(Plan const& p) { return ('m' == p.precision) ? p.wXz.bytes : p.S; }
 size_t start_stride(Plan const& p) { return align256(start_bytes(p)); }
 // start i (0: the newest) lies in slot (head + i) % depth of the ring
-char* start_at(Plan const& p, int i) { return p.startMem.as<char>() + size_t((p.startHead + i) % p.startDepth) * start_stride(p); }
-}
-
+char* start_at(Plan const& p, int i) { return p.held.startMem.as<char>() + size_t((p.held.startHead + i) % p.startDepth) * start_stride(p); }
+// the ring ends on its own (keepStarts; a new buffer ends it with the rest of Plan::held): the starts go, the depth stays
 void starts_release(Plan& p) {
-    p.startMem.release(); p.projectMem.release();
-    p.startCount = 0; p.startHead = 0;
+    p.held.startMem.release(); p.held.projectMem.release();
+    p.held.startCount = 0; p.held.startHead = 0;
+}
 }
 
 tfqmrgpuStatus_t starts_keep(Plan& p, int const depth) {
     if (depth < 0 || depth > kProjectMax) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');
     if (depth == p.startDepth) return TFQMRGPU_STATUS_SUCCESS;
-    if (0 == depth || 0 == p.startCount) {      // nothing to carry over: the ring is allocated by the next pushStart
+    if (0 == depth || 0 == p.held.startCount) {      // nothing to carry over: the ring is allocated by the next pushStart
         starts_release(p);
         p.startDepth = depth;
         return TFQMRGPU_STATUS_SUCCESS;
     }
     // a ring of another depth with the newest starts in slots 0, 1, ...  (the call has no stream: it waits for the device)
-    int const keep = std::min(p.startCount, depth);
+    int const keep = std::min(p.held.startCount, depth);
     size_t const stride = start_stride(p);
     DevMem ring;
     if (auto const st = ring.reserve(std::max<size_t>(size_t(depth) * stride, 256))) return st;
     TFQ_HIP(hipDeviceSynchronize(), TFQMRGPU_STATUS_LAUNCH_FAILED)
     for (int i = 0; i < keep; ++i)
         TFQ_HIP(hipMemcpy(ring.as<char>() + size_t(i) * stride, start_at(p, i), start_bytes(p), hipMemcpyDeviceToDevice), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    p.startMem = std::move(ring);
-    p.projectMem.release();                     // sized by the depth
-    p.startDepth = depth; p.startCount = keep; p.startHead = 0;
+    p.held.startMem = std::move(ring);
+    p.held.projectMem.release();                     // sized by the depth
+    p.startDepth = depth; p.held.startCount = keep; p.held.startHead = 0;
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
@@ -52,21 +52,21 @@ tfqmrgpuStatus_t starts_push(Handle& h, Plan& p) {
     if (0 == p.LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);     // bufferSize has not been called
     if (0 == p.startDepth) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');
     if (nullptr == p.buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
-    if (auto const st = p.startMem.reserve(std::max<size_t>(size_t(p.startDepth) * start_stride(p), 256))) return st;
-    int const head = (p.startHead + p.startDepth - 1) % p.startDepth;   // the slot of the oldest start, or a free one
+    if (auto const st = p.held.startMem.reserve(std::max<size_t>(size_t(p.startDepth) * start_stride(p), 256))) return st;
+    int const head = (p.held.startHead + p.startDepth - 1) % p.startDepth;   // the slot of the oldest start, or a free one
     hipStream_t const s = (hipStream_t)h.stream;
-    char* const slot = p.startMem.as<char>() + size_t(head) * start_stride(p);
+    char* const slot = p.held.startMem.as<char>() + size_t(head) * start_stride(p);
     TFQ_HIP(hipMemcpyAsync(slot, resolve_callers(p).x, start_bytes(p), hipMemcpyDeviceToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    p.startHead = head;
-    p.startCount = std::min(p.startCount + 1, p.startDepth);
+    p.held.startHead = head;
+    p.held.startCount = std::min(p.held.startCount + 1, p.startDepth);
     return TFQMRGPU_STATUS_SUCCESS;
 }
 
 tfqmrgpuStatus_t starts_project(Handle& h, Plan& p, double* const coefficients, int32_t* const nUsed) {
     if (0 == p.LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);     // bufferSize has not been called
     if (auto const st = operands_ready(p, true)) return st;         // no buffer | user-defined operator | A never set | A scaled and not kept
-    int const k = p.startCount, depth = p.startDepth;
-    if (k < 1 || !p.startMem) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');
+    int const k = p.held.startCount, depth = p.startDepth;
+    if (k < 1 || !p.held.startMem) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');
 
     hipStream_t const s = (hipStream_t)h.stream;
     DevPlan const d = resolve_callers(p);                           // 'm': the double copies of X, B and A
@@ -79,8 +79,8 @@ tfqmrgpuStatus_t starts_project(Handle& h, Plan& p, double* const coefficients, 
     size_t const atRec = size_t(depth) * stride;
     size_t const atGamma = atRec + align256(size_t(project_planes(depth)) * d.nChunks * LN * sizeof(double));
     size_t const atUsed = atGamma + align256(nRhs * 2 * kProjectMax * sizeof(double));
-    if (auto const st = p.projectMem.reserve(std::max<size_t>(atUsed + align256(nRhs * sizeof(int32_t)), 256))) return st;
-    char* const mem = p.projectMem.as<char>();
+    if (auto const st = p.held.projectMem.reserve(std::max<size_t>(atUsed + align256(nRhs * sizeof(int32_t)), 256))) return st;
+    char* const mem = p.held.projectMem.as<char>();
     double* const gamma = (double*)(mem + atGamma);
     int32_t* const used = (int32_t*)(mem + atUsed);
 

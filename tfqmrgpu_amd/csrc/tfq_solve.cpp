@@ -131,14 +131,14 @@ tfqmrgpuStatus_t vote(Handle& h, hipStream_t s, tfqmrgpuStatus_t early, int& ahe
 struct OpScratch { char* xu; char* yu; uint32_t* i2u; uint16_t* colU; };
 size_t op_vector_bytes(Plan const& p) { return align256(size_t(p.nnzbX) * 2 * p.LM * p.LN * ('z' == p.precision ? 8 : 4)); }
 size_t op_scratch_bytes(Plan const& p) { return 2 * op_vector_bytes(p) + align256(size_t(p.nnzbX) * 4) + align256(size_t(p.nnzbX) * 2); }
-OpScratch op_scratch(Plan const& p) {       // the pieces of Plan::opScratch (allocated)
-    char* const b = p.opScratch.as<char>();
+OpScratch op_scratch(Plan const& p) {       // the pieces of Plan::layout.opScratch (allocated)
+    char* const b = p.layout.opScratch.as<char>();
     size_t const v = op_vector_bytes(p);
     return { b, b + v, (uint32_t*)(b + 2 * v), (uint16_t*)(b + 2 * v + align256(size_t(p.nnzbX) * 4)) };
 }
 tfqmrgpuStatus_t ensure_op_scratch(Plan& p, hipStream_t s) {
-    if (p.opScratch) return TFQMRGPU_STATUS_SUCCESS;
-    if (auto const st = p.opScratch.reserve(std::max<size_t>(op_scratch_bytes(p), 256))) return st;
+    if (p.layout.opScratch) return TFQMRGPU_STATUS_SUCCESS;
+    if (auto const st = p.layout.opScratch.reserve(std::max<size_t>(op_scratch_bytes(p), 256))) return st;
     auto const o = op_scratch(p);
     std::vector<uint16_t> cu(p.nnzbX);      // compressed block column per block, caller's order
     for (uint32_t u = 0; u < p.nnzbX; ++u) cu[u] = p.colindx[u];
@@ -265,7 +265,7 @@ struct Slots {
     bool harvest(int slot, bool iteration = true) {
         if (hipSuccess != hipEventSynchronize(ringEvent(slot))) { if (!fail) fail = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED); return false; }
         last = ring()[slot];
-        if (iteration) p.boundHistory.push_back(last.max_bound2 * histScale);
+        if (iteration) p.last.boundHistory.push_back(last.max_bound2 * histScale);
         return true;
     }
 
@@ -278,9 +278,9 @@ struct Slots {
         for (int k = 0; k < NK; ++k) {
             float ms = 0;
             if (!timed(k) || hipSuccess != hipEventElapsedTime(&ms, pev[slot * (NK + 1) + k], pev[slot * (NK + 1) + k + 1])) continue;
-            if (Found::Stopped == found || (TFQMRGPU_PROF_PROBE == k && !probed)) { p.profGatedMs[k] += ms; p.profGatedLaunches[k] += 1; continue; }
-            p.profMs[k] += ms; p.profLaunches[k] += 1;
-            if (Found::FirstWork == found) { p.profFirstMs[k] += ms; p.profFirstLaunches[k] += 1; }
+            if (Found::Stopped == found || (TFQMRGPU_PROF_PROBE == k && !probed)) { p.last.gated.ms[k] += ms; p.last.gated.launches[k] += 1; continue; }
+            p.last.all.ms[k] += ms; p.last.all.launches[k] += 1;
+            if (Found::FirstWork == found) { p.last.first.ms[k] += ms; p.last.first.launches[k] += 1; }
         }
     }
 
@@ -455,10 +455,10 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt, Mix
     // what a cycle copies into the control block of its float solve: pageable sources, alive until run_tfqmr has synchronised the stream
     double t2[2]; int32_t lim;
     for (int cycle = 0; ; ++cycle) {
-        if (cycle > 0) { spmm_apply(dz, dz.x, (void*)a.Yz, s); p.flops_performed += fm.fMult; }
+        if (cycle > 0) { spmm_apply(dz, dz.x, (void*)a.Yz, s); p.last.flops_performed += fm.fMult; }
         a.cycle = cycle; a.innerTol = 1e-4; a.innerMaxIt = std::max(0, maxIt - used);
         launch_refine_residual(a, s, nullptr != warm);
-        p.flops_performed += fm.fNrm;
+        p.last.flops_performed += fm.fNrm;
         if (!mine && hipSuccess != hipGetLastError()) mine = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
         // (k_refine_max has written {.., .., 0}: this rank's mark behind it, on the same stream)
         if (mine && multi) (void)hipMemcpyAsync(a.refine + 2, &kOne, sizeof kOne, hipMemcpyHostToDevice, s);
@@ -469,8 +469,8 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt, Mix
         TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
         if (v[2] > 0.) return TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);      // a rank failed: every rank reads the same value and leaves here
         res2 = v[0];
-        p.cycleResidual.push_back(std::sqrt(res2));
-        p.refinementCycles = cycle;
+        p.last.cycleResidual.push_back(std::sqrt(res2));
+        p.last.refinementCycles = cycle;
         if (v[1] > 0.) { result = TFQMRGPU_STATUS_BREAKDOWN; break; }      // the residual is not finite
         if (res2 <= tol * tol) { result = TFQMRGPU_STATUS_SUCCESS; break; }
         if (used >= maxIt) break;
@@ -500,28 +500,46 @@ static tfqmrgpuStatus_t run_mixed(Handle& h, Plan& p, double tol, int maxIt, Mix
         used += o.last.iteration;
         lastIts = o.last.iteration;
         if (0 == cycle) firstStalled = (3 == o.last.state && o.last.iteration < ask.innerIts);   // ended by itself at its floor, not at a limit
-        p.cycleIterations.push_back(o.last.iteration);
+        p.last.cycleIterations.push_back(o.last.iteration);
         brokeDown = (2 == o.last.state);                                    // every right-hand side of this float solve broke down
-        p.flops_performed += fm.solve(o.last) - fm.fNrm;                    // (|r|^2 of the set-up is the refinement's, counted above)
+        p.last.flops_performed += fm.solve(o.last) - fm.fNrm;                    // (|r|^2 of the set-up is the refinement's, counted above)
         launch_refine_update(a, s);
         if (warm) warm->updated = true;
-        p.flops_performed += 2. * p.nnzbX * p.LM * p.LN;
+        p.last.flops_performed += 2. * p.nnzbX * p.LM * p.LN;
     }
     if (!warm || warm->updated)                          // (warm and no update: x still holds X0, in X space)
     if (auto const st = precond_back(h, p)) return st;   // (every rank gets here: errors that one rank alone could see have left above, behind a collective)
     TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    p.flops_performed_all += p.flops_performed;
+    p.flops_performed_all += p.last.flops_performed;
     p.residuum_reached = std::sqrt(std::max(res2, 1.4e-76 * 1.4e-76));
-    p.iterations_needed = (TFQMRGPU_STATUS_SUCCESS == result) ? used : maxIt;
+    p.last.iterations_needed = (TFQMRGPU_STATUS_SUCCESS == result) ? used : maxIt;
     if (warm) warm->finished = true;
     return result;
 }
 
-// what a solve leaves for getInfo, getBoundHistory and the profile, as it is before the solve starts
+// what a solve leaves for getInfo, getBoundHistory and the profile, as it is before the solve starts (residuum_reached: see Plan)
 static void reset_results(Plan& p, int maxIt) {
-    for (int k = 0; k < TFQMRGPU_PROFILE_CLASSES; ++k) { p.profLaunches[k] = 0; p.profMs[k] = 0; p.profGatedLaunches[k] = 0; p.profGatedMs[k] = 0; p.profFirstLaunches[k] = 0; p.profFirstMs[k] = 0; }
-    p.boundHistory.clear(); p.cycleResidual.clear(); p.cycleIterations.clear(); p.refinementCycles = 0;
-    p.iterations_needed = maxIt; p.flops_performed = 0;
+    p.last = Plan::Last{};
+    p.last.iterations_needed = maxIt; p.last.flops_performed = 0;
+}
+
+// the tail of a tfQMR solve that came to its end (the back transform has run, flops_performed is complete): getInfo's values and the status
+static tfqmrgpuStatus_t finish_tfqmr(Plan& p, Ctl const& last, int maxIt) {
+    p.flops_performed_all += p.last.flops_performed;
+    p.residuum_reached = std::sqrt(last.residual2_reached);
+    p.last.iterations_needed = (1 == last.state) ? last.iterations_needed : maxIt;
+    switch (last.state) {
+        case 1: return TFQMRGPU_STATUS_SUCCESS;
+        case 2: return TFQMRGPU_STATUS_BREAKDOWN;
+        default: return TFQMRGPU_STATUS_MAX_ITERATIONS;
+    }
+}
+
+// a warm solve that was given no iteration at all: X0 is the answer, untouched; status and getInfo of a cold solve that was given none
+static tfqmrgpuStatus_t finish_warm_unstarted(Plan& p) {
+    p.flops_performed_all += p.last.flops_performed;
+    p.residuum_reached = std::sqrt(1e300);
+    return TFQMRGPU_STATUS_MAX_ITERATIONS;
 }
 
 // Warm start (tfqmrgpu_ext.h section 14): the driver above, untouched, wrapped in a correction solve the way run_mixed wraps it.
@@ -537,15 +555,11 @@ tfqmrgpuStatus_t run_solve_from(Handle& h, Plan& p, double tol, int maxIt, void 
     if (early) return early;
     if ('z' != p.precision && 'c' != p.precision) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
     reset_results(p, maxIt);
-    if (maxIt <= 0) {   // no iteration at all: X0 is the answer, untouched; status and getInfo of a cold solve that was given no iteration
-        p.flops_performed_all += p.flops_performed;
-        p.residuum_reached = std::sqrt(1e300);
-        return TFQMRGPU_STATUS_MAX_ITERATIONS;
-    }
+    if (maxIt <= 0) return finish_warm_unstarted(p);
     hipStream_t const s = (hipStream_t)h.stream;
     size_t const S = align256(p.S);
-    if (auto const st = p.warm.reserve(std::max<size_t>(2 * S, 256))) return st;
-    char* const X0 = p.warm.as<char>();
+    if (auto const st = p.held.warm.reserve(std::max<size_t>(2 * S, 256))) return st;
+    char* const X0 = p.held.warm.as<char>();
     char* const R = X0 + S;
     DevPlan const d = resolve(p);
     {   // R from the caller's A, before precond_prepare scales the A in the buffer (or brings it up to date with pending patches: the kept copy has them)
@@ -565,18 +579,11 @@ tfqmrgpuStatus_t run_solve_from(Handle& h, Plan& p, double tol, int maxIt, void 
     Ctl const& last = o.last;
     FlopModel const fm(p);
     // the correction solve (its set-up norm is |r|^2 of the residual pass) + the product A X0 + |b|^2 + the subtraction and the update
-    p.flops_performed = fm.solve(last) + fm.fMult + fm.fNrm + 4. * p.nnzbX * p.LM * p.LN;
+    p.last.flops_performed = fm.solve(last) + fm.fMult + fm.fNrm + 4. * p.nnzbX * p.LM * p.LN;
     if (auto const st2 = precond_back(h, p)) return st2;            // D := M^-1 Y, also after max iterations or a breakdown
     if (!warm_update_launch(d, X0, s)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
     TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-    p.flops_performed_all += p.flops_performed;
-    p.residuum_reached = std::sqrt(last.residual2_reached);
-    p.iterations_needed = (1 == last.state) ? last.iterations_needed : maxIt;
-    switch (last.state) {
-        case 1: return TFQMRGPU_STATUS_SUCCESS;
-        case 2: return TFQMRGPU_STATUS_BREAKDOWN;
-        default: return TFQMRGPU_STATUS_MAX_ITERATIONS;
-    }
+    return finish_tfqmr(p, last, maxIt);
 }
 
 // The same for an 'm' plan (tfqmrgpu_ext.h section 16): the refinement of run_mixed, its float driver untouched, on the correction system.
@@ -590,15 +597,11 @@ tfqmrgpuStatus_t run_refine_from(Handle& h, Plan& p, double tol, int maxIt, void
     if (early) return early;
     if ('m' != p.precision) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
     reset_results(p, maxIt);
-    if (maxIt <= 0) {   // no iteration at all: X0 is the answer, untouched; status and getInfo as run_solve_from leaves them
-        p.flops_performed_all += p.flops_performed;
-        p.residuum_reached = std::sqrt(1e300);
-        return TFQMRGPU_STATUS_MAX_ITERATIONS;
-    }
+    if (maxIt <= 0) return finish_warm_unstarted(p);
     hipStream_t const s = (hipStream_t)h.stream;
     size_t const Z = align256(p.wXz.bytes);
-    if (auto const st = p.warm.reserve(std::max<size_t>(2 * Z, 256))) return st;
-    char* const X0 = p.warm.as<char>();
+    if (auto const st = p.held.warm.reserve(std::max<size_t>(2 * Z, 256))) return st;
+    char* const X0 = p.held.warm.as<char>();
     char* const R = X0 + Z;
     DevPlan const dz = resolveZ(p);
     FlopModel const fm(p);
@@ -608,7 +611,7 @@ tfqmrgpuStatus_t run_refine_from(Handle& h, Plan& p, double tol, int maxIt, void
         spmm_apply(dA, dz.x, dz.v4, s);
         if (!warm_refine_residual_launch(dz, dz.v4, X0, R, (double*)(p.buffer + p.wBn2z.offset), s)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
         TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        p.flops_performed += fm.fMult + fm.fNrm + nReal;            // the product A X0, |b|^2 and the subtraction (|r|^2: cycle 0 of the refinement counts it)
+        p.last.flops_performed += fm.fMult + fm.fNrm + nReal;            // the product A X0, |b|^2 and the subtraction (|r|^2: cycle 0 of the refinement counts it)
     }
     if (auto const st = precond_prepare(h, p)) return st;           // (x has not been written yet)
     MixedWarm w{ (double const*)R };
@@ -620,7 +623,7 @@ tfqmrgpuStatus_t run_refine_from(Handle& h, Plan& p, double tol, int maxIt, void
     if (w.updated) {     // x holds D, back-transformed: x := X0 + D
         if (!warm_update_launch(dz, X0, s)) return TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
         TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
-        p.flops_performed += nReal; p.flops_performed_all += nReal;
+        p.last.flops_performed += nReal; p.flops_performed_all += nReal;
     }
     return st;
 }
@@ -637,17 +640,10 @@ tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt) {
     if (auto const st = run_tfqmr(h, p, tol, maxIt, early, 1., o)) return st;
     Ctl const& last = o.last;
     FlopModel const fm(p);
-    p.flops_performed = fm.solve(last);
-    if (p.opFn) p.flops_performed += o.userFlops - (2. * last.iteration + last.nprobes) * fm.fMult;  // the operator's own count
+    p.last.flops_performed = fm.solve(last);
+    if (p.opFn) p.last.flops_performed += o.userFlops - (2. * last.iteration + last.nprobes) * fm.fMult;  // the operator's own count
     if (auto const st = precond_back(h, p)) return st;   // X := M^-1 Y, also when the solve ended at maxIterations or in a breakdown
-    p.flops_performed_all += p.flops_performed;
-    p.residuum_reached = std::sqrt(last.residual2_reached);
-    p.iterations_needed = (1 == last.state) ? last.iterations_needed : maxIt;
-    switch (last.state) {
-        case 1: return TFQMRGPU_STATUS_SUCCESS;
-        case 2: return TFQMRGPU_STATUS_BREAKDOWN;
-        default: return TFQMRGPU_STATUS_MAX_ITERATIONS;
-    }
+    return finish_tfqmr(p, last, maxIt);
 }
 
 } // namespace tfq
