@@ -1,5 +1,6 @@
-// Column operations of the tfQMR iteration: the scalar Krylov coefficient updates per block column and the stopping decision, as
-// DEVICE functions.  They run (a) as kernels of their own, one work group per block column (tfq_vec.hip: k_dec35 ... k_decide), and
+// Column operations of the tfQMR iteration: the scalar Krylov coefficient updates per block column, the stopping decision and the set-up of
+// a solve (control block, per-column scalars: reset_ctl, init_col_scalars), as DEVICE functions.  The column operations run (a) as kernels of
+// their own, one work group per block column (tfq_vec.hip: k_dec35 ... k_decide), and
 // (b) for small systems in the TAIL of the kernel that produces their input: the work group that finishes a block column last
 // (per-column arrival counter) runs the column's update, the one that finishes the last column runs the decision -- six launches
 // less per iteration slot where the slot is all launch latency ("small systems").  The arithmetic and the order
@@ -324,6 +325,33 @@ __device__ inline void decide_body(DevPlan const& d, int what, int phase, double
     }
 }
 
+// ---- the start of a solve (tfqmrgpu_core.hxx:121-127,154-166): k_init_col, k_refine_init_col (tfq_vec.hip), k_warm_init_col (tfq_warm.hip) ----
+// the control block
+__device__ inline void reset_ctl(Ctl* c, double tol, int maxIterations, int stallStop) {
+    double const tol2 = tol * tol;
+    c->tol2 = tol2; c->target_bound2 = tol2 * 100 * 100; c->max_bound2 = 0; c->residual2_reached = 1e300; c->probe_bound2 = 0;
+    for (int i = 0; i < 6; ++i) c->red[i] = 0;
+    c->iteration = 0; c->maxIterations = maxIterations;
+    c->state = (maxIterations > 0) ? 0 : 3;
+    c->probe = 0; c->iterations_needed = maxIterations; c->nprobes = 0; c->xpend = 0; c->stallStop = stallStop;
+}
+// block column col, every thread of its work group: thread t < LN writes the scalars of right-hand side t -- tau and 1 / |b|^2 as given, rho := 1,
+// everything else 0 -- and thread 0 the arrival counters of the folded column operations, which start every solve at zero, whatever the previous one left
+template <typename R, int LN>
+__device__ inline void init_col_scalars(DevPlan const& d, uint32_t col, int t, double tau, double invBn2) {
+    if (t < LN) {
+        size_t const ir = (size_t(col) * 2 + 0) * LN + t, ii = ir + LN, i1 = size_t(col) * LN + t;
+        d.tau[i1] = tau; d.invBn2[i1] = invBn2; d.var[i1] = 0; d.d[i1] = 0; d.status[i1] = 0;
+        ((R*)d.rho)[ir] = 1; ((R*)d.rho)[ii] = 0;
+        ((R*)d.alfa)[ir] = 0; ((R*)d.alfa)[ii] = 0; ((R*)d.beta)[ir] = 0; ((R*)d.beta)[ii] = 0;
+        ((R*)d.c67)[ir] = 0; ((R*)d.c67)[ii] = 0; ((R*)d.eta)[ir] = 0; ((R*)d.eta)[ii] = 0;
+        ((R*)d.c67a)[ir] = 0; ((R*)d.c67a)[ii] = 0; ((R*)d.eta2)[ir] = 0; ((R*)d.eta2)[ii] = 0;
+    }
+    if (0 == t) {
+        d.foldCount[col] = 0;
+        if (0 == col) d.foldCount[d.nCols] = 0;
+    }
+}
 
 enum { FOLD_DEC34 = 1, FOLD_DECT_C67 = 2, FOLD_DECT_FINAL = 3, FOLD_PROBE = 4 };
 

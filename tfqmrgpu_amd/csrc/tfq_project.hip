@@ -5,7 +5,8 @@
 //   k_project_solve_col  per block column: the records summed in chunk order; one lane per right-hand side runs the Cholesky factorisation of G in
 //                                          the order of the starts, drops a start whose pivot is too small, writes gamma and the number of kept starts
 //   k_project_combine    per chunk:        x := sum gamma_i S_i, accumulated in double in slot order, rounded once to the storage type
-// Work groups, chunk tables, element order and access width are those of tfq_warm.hip (tfq_stream.hpp).  The record of a chunk is kept plane by
+// Work groups, chunk span, accesses, the right-hand side of a slot and the sums of a chunk are the vector kernels' own (tfq_stream.hpp: Geo,
+// TFQ_CHUNK_SPAN, ldv / stv, ld_b_under_x, slot_rhs, chunk_reduce_rounds).  The record of a chunk is kept plane by
 // plane -- rec[plane][chunk][LN] -- so that every plane is summed by column_sum<LN, 1> (tfq_colops.hpp) as the records of the solver are.  No atomics.
 #include "tfq_device.hpp"
 #include "tfq_vec.hpp"
@@ -28,35 +29,23 @@ template <int K> struct PPlanes {
 
 // ---- per chunk: the Gram sums ---------------------------------------------------------------------------------------------------------
 // one pass over W_0 ... W_{K-1} and the B block under each X block (zero where there is none, as in k_warm_residual); every product and
-// every sum in double.  The planes leave through LDS in rounds of ROUND planes (all at once: 25 planes x 8 KiB for float storage)
+// every sum in double.  The planes leave through LDS in rounds of ROUND planes (all at once: 25 planes x 8 KiB for float storage), each round
+// in the fixed slot order of chunk_reduce
 template <typename R, int LM, int LN, int K>
 __global__ __launch_bounds__(256) void k_project_gram(DevPlan d, ProjectVecs pv, double* rec) {
-    using G = WGeo<R, LM, LN>;
+    using G = Geo<R, LM, LN>;
     using PL = PPlanes<K>;
     constexpr int NP = PL::N;
     constexpr int ROUND = 4096 / (256 * G::VEC);             // planes per round: 32 KiB of LDS
     __shared__ double s[ROUND * 256 * G::VEC];
-    int const t = threadIdx.x;
-    uint32_t const chunk = blockIdx.x;
-    uint32_t const first = d.chunkFirst[chunk];
-    uint32_t const nItems = (d.chunkFirst[chunk + 1] - first) * G::IPB;
-    size_t const base = size_t(first) * 2 * G::P;
+    TFQ_CHUNK_SPAN(G)
     double acc[NP][G::VEC] = {};
     if (t < G::T) for (uint32_t w = t; w < nItems; w += G::T) {
-        uint32_t const blk = w / G::IPB;
-        size_t const inner = size_t(w - blk * G::IPB) * G::VEC;
-        size_t const re = base + size_t(blk) * 2 * G::P + inner, im = re + G::P;
+        TFQ_ITEM_OFFSETS(G)
         R wr[K][G::VEC], wi[K][G::VEC], br[G::VEC], bi[G::VEC];
 #pragma unroll
-        for (int i = 0; i < K; ++i) { w_ld(wr[i], (R const*)pv.w[i] + re); w_ld(wi[i], (R const*)pv.w[i] + im); }
-        uint32_t const bq = d.bOfX[first + blk];
-        if (0xffffffffu == bq) {
-#pragma unroll
-            for (int v = 0; v < G::VEC; ++v) { br[v] = 0; bi[v] = 0; }
-        } else {
-            R const* b = (R const*)d.B + size_t(bq) * 2 * G::P + inner;
-            w_ld(br, b); w_ld(bi, b + G::P);
-        }
+        for (int i = 0; i < K; ++i) { ldv(wr[i], (R const*)pv.w[i] + re); ldv(wi[i], (R const*)pv.w[i] + im); }
+        ld_b_under_x<R, G::VEC>(br, bi, d, first + blk, size_t(w - blk * G::IPB) * G::VEC, G::P);
 #pragma unroll
         for (int v = 0; v < G::VEC; ++v) {
             double const b0 = br[v], b1 = bi[v];
@@ -77,24 +66,8 @@ __global__ __launch_bounds__(256) void k_project_gram(DevPlan d, ProjectVecs pv,
             }
         }
     }
-    // rec[plane][chunk][LN]: the terms of a right-hand side added in one fixed order, ROUND planes at a time in plane order
-#pragma unroll
-    for (int p0 = 0; p0 < NP; p0 += ROUND) {
-        __syncthreads();                                     // the sums of the round before have been read
-        if (t < G::T) {
-#pragma unroll
-            for (int q = 0; q < ROUND; ++q)
-                if (p0 + q < NP)
-#pragma unroll
-                    for (int v = 0; v < G::VEC; ++v) s[q * (256 * G::VEC) + t * G::VEC + v] = acc[(p0 + q < NP) ? p0 + q : 0][v];
-        }
-        __syncthreads();
-        int const nq = (NP - p0 < ROUND) ? NP - p0 : ROUND;
-        for (int e = t; e < nq * LN; e += 256) {
-            int const q = e / LN, j = e % LN;
-            rec[(size_t(p0 + q) * d.nChunks + chunk) * LN + j] = w_ordered_sum<LN, G::VEC, G::T>(d.ilv, s + q * (256 * G::VEC), j);
-        }
-    }
+    // rec[plane][chunk][LN]
+    chunk_reduce_rounds<LN, G::VEC, G::T, ROUND>(acc, s, rec + size_t(chunk) * LN, size_t(d.nChunks) * LN, t, d.ilv);
 }
 
 // ---- per block column: the minimiser ---------------------------------------------------------------------------------------------------------
@@ -176,33 +149,24 @@ __global__ __launch_bounds__(256) void k_project_solve_col(DevPlan d, double con
 // multiply-adds in slot order, each slot Re-part first, and rounded once to the storage type
 template <typename R, int LM, int LN, int K>
 __global__ __launch_bounds__(256) void k_project_combine(DevPlan d, ProjectVecs pv, double const* gamma) {
-    using G = WGeo<R, LM, LN>;
-    int const t = threadIdx.x;
+    using G = Geo<R, LM, LN>;
+    TFQ_CHUNK_SPAN(G)
     if (t >= G::T) return;
-    uint32_t const chunk = blockIdx.x;
-    uint32_t const first = d.chunkFirst[chunk];
-    uint32_t const nItems = (d.chunkFirst[chunk + 1] - first) * G::IPB;
-    size_t const base = size_t(first) * 2 * G::P;
-    uint32_t const col = d.chunkCol[chunk];
     double cr[K][G::VEC], ci[K][G::VEC];
 #pragma unroll
     for (int v = 0; v < G::VEC; ++v) {
-        int const m = t * G::VEC + v;
-        int const j = d.ilv ? (m / d.ilv) % LN : m % LN;        // the right-hand side of slot m (tfq_stream.hpp: w_ordered_sum)
-        double const* const c = gamma + (size_t(col) * LN + j) * 2 * kProjectMax;
+        double const* const c = gamma + (size_t(col) * LN + slot_rhs<LN>(d.ilv, t * G::VEC + v)) * 2 * kProjectMax;
 #pragma unroll
         for (int i = 0; i < K; ++i) { cr[i][v] = c[2 * i]; ci[i][v] = c[2 * i + 1]; }
     }
     R* const x = (R*)d.x;
     for (uint32_t w = t; w < nItems; w += G::T) {
-        uint32_t const blk = w / G::IPB;
-        size_t const inner = size_t(w - blk * G::IPB) * G::VEC;
-        size_t const re = base + size_t(blk) * 2 * G::P + inner, im = re + G::P;
+        TFQ_ITEM_OFFSETS(G)
         double ar[G::VEC] = {}, ai[G::VEC] = {};
 #pragma unroll
         for (int i = 0; i < K; ++i) {
             R sr[G::VEC], si[G::VEC];
-            w_ld(sr, (R const*)pv.s[i] + re); w_ld(si, (R const*)pv.s[i] + im);
+            ldv(sr, (R const*)pv.s[i] + re); ldv(si, (R const*)pv.s[i] + im);
 #pragma unroll
             for (int v = 0; v < G::VEC; ++v) {
                 double const s0 = sr[v], s1 = si[v];
@@ -213,7 +177,7 @@ __global__ __launch_bounds__(256) void k_project_combine(DevPlan d, ProjectVecs 
         R xr[G::VEC], xi[G::VEC];
 #pragma unroll
         for (int v = 0; v < G::VEC; ++v) { xr[v] = R(ar[v]); xi[v] = R(ai[v]); }
-        w_st(x + re, xr); w_st(x + im, xi);
+        stv(x + re, xr); stv(x + im, xi);
     }
 }
 

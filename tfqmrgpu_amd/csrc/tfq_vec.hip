@@ -12,70 +12,26 @@
 //    between two scalar barriers), the second x update of an iteration rides on the next iteration;
 //  * reductions are deterministic: fixed shuffle-free LDS order inside a work group, fixed chunk
 //    order per column in the decision kernels.
+// Here: the kernels of the slot, the start of a cold solve and the refinement of the mixed precision, with their launchers.  What
+// they share with the other chunk-streaming kernels (geometry, accesses, ordered sums, chunk span, B under X) is tfq_stream.hpp;
+// the column operations, the control block and the per-column scalars at the start of a solve are tfq_colops.hpp.
 #include <type_traits>
 
 #include "tfq_device.hpp"
 #include "tfq_vec.hpp"
 #include "tfq_colops.hpp"
+#include "tfq_stream.hpp"
 
 namespace tfq {
-
-
-// ---------------------------------------------------------------------------------------------------
-template <typename R> struct Vec;
-template <> struct Vec<double> { static constexpr int N = 2; using T = double2; };
-template <> struct Vec<float>  { static constexpr int N = 4; using T = float4;  };
-
-// largest thread count <= 256 such that a thread's elements keep their RHS index j on every trip -- in the native order ((t * VEC) % LN == 0) and in
-// the interleaved ones, where a thread's VEC elements are ROWS of one column and its column is (t + trip * T) % LN: T % LN == 0 (r04, for the 8 x 9 and
-// 8 x 10 plans on row pairs; the only shape for which the two rules differ is LN = 10: 250 threads where 255 would do for the native order)
-template <int LN, int VEC> constexpr int activeThreads() {
-    int t = 256;
-    while (t % LN) --t;
-    return t;
-}
-
-template <typename R, int LM, int LN>
-struct Geo {
-    static constexpr int VEC = Vec<R>::N;
-    static constexpr int P = LM * LN;            // elements of one plane (Re or Im) of a block
-    static constexpr int IPB = P / VEC;          // vector items per block plane
-    static constexpr int T = activeThreads<LN, VEC>();
-    static_assert(P % VEC == 0, "block plane must be a multiple of the vector width");
-};
-
-// The vector kernels touch every element exactly once: all their accesses are non-temporal, so the streams neither
-// wait for nor leave lines in the L2 that the multiply kernels want for their operand blocks (measured on P2:
-// x_v6_v7 0.780 -> 0.716 ms, xpay_v6 0.316 -> 0.289 ms, and the two fused multiplies that follow 0.773/0.716 ->
-// 0.743/0.681 ms).
-template <typename R> __device__ inline void ldv(R (&r)[Vec<R>::N], R const* p) {
-    using V = R __attribute__((ext_vector_type(Vec<R>::N)));
-    auto const v = __builtin_nontemporal_load(reinterpret_cast<V const*>(p));
-#pragma unroll
-    for (int i = 0; i < Vec<R>::N; ++i) r[i] = v[i];
-}
-template <typename R> __device__ inline void stv(R* p, R const (&r)[Vec<R>::N]) {
-    using V = R __attribute__((ext_vector_type(Vec<R>::N)));
-    V v;
-#pragma unroll
-    for (int i = 0; i < Vec<R>::N; ++i) v[i] = r[i];
-    __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
-}
-// the float shadow vector read with the vector width of R
-template <int N> __device__ inline void ldf(float (&r)[N], float const* p) {
-    if constexpr (N == 2) { auto const v = *reinterpret_cast<float2 const*>(p); r[0] = v.x; r[1] = v.y; }
-    else { auto const v = *reinterpret_cast<float4 const*>(p); r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w; }
-}
 
 // per-thread copy of one complex scalar per owned RHS index
 template <typename R, int LN, int VEC>
 struct Scal {
     R re[VEC], im[VEC];
-    // ilv = G > 0: every G consecutive elements are rows of ONE column (tfq_device.hpp: ilv_offset), else consecutive columns
     __device__ inline void load(R const* a, uint32_t col, int t, int ilv = 0) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
-            int const j = ilv ? ((t * VEC + v) / ilv) % LN : (t * VEC + v) % LN;
+            int const j = ilv ? ((t * VEC + v) / ilv) % LN : (t * VEC + v) % LN;   // written in place: slot_rhs (tfq_stream.hpp) here moves an instruction in every slot kernel
             re[v] = a[(size_t(col) * 2 + 0) * LN + j];
             im[v] = a[(size_t(col) * 2 + 1) * LN + j];
         }
@@ -96,86 +52,13 @@ template <typename R> __device__ inline void axpy(R& yr, R& yi, R xr, R xi, R ar
     yr = nr; yi = ni;
 }
 
-// Sum the per-thread accumulators of a work group into out[NPL][LN] (one record per chunk).
-// Fixed order => bitwise reproducible.  s is LDS of NPL*256*VEC doubles.
-// The terms of one sum, in order: element m of the work group's slice belongs to column (m / G) % LN for plans that keep G rows of a
-// column together (ILV = G, tfq_device.hpp: ilv_offset), to column m % LN otherwise.  (r04) ILV is a template parameter and the
-// terms are fetched in batches of 16 before they are added: with the run-time `ilv` of r01-r03 every LDS read waited for the
-// addition in front of it -- 32 dependent round trips by 16 threads at the end of every work group of k_v5_nrm, which is what made
-// that kernel stream at 5.8 TB/s where k_xpay_v6, the same three vectors without a sum, reaches 6.6.  Same additions, same order.
-template <int LN, int VEC, int T, int ILV>
-__device__ inline double ordered_sum(double const* sp, int j) {
-    constexpr int terms = (T * VEC) / LN, B = (terms < 16) ? terms : 16, full = terms / B * B;
-    auto at = [&](int n) { return ILV ? sp[((n / ILV) * LN + j) * ILV + n % ILV] : sp[n * LN + j]; };
-    double sum = 0;
-    for (int n0 = 0; n0 < full; n0 += B) {
-        double v[B];
-#pragma unroll
-        for (int i = 0; i < B; ++i) v[i] = at(n0 + i);
-#pragma unroll
-        for (int i = 0; i < B; ++i) sum += v[i];
-    }
-#pragma unroll
-    for (int n = full; n < terms; ++n) sum += at(n);
-    return sum;
-}
-template <int LN, int VEC, int T, int NPL>
-__device__ inline void chunk_reduce(double (&acc)[NPL][VEC], double* s, double* out, int t, int ilv = 0, bool coherent = false) {   // coherent: folded path, tfq_colops.hpp: co_store
-    __syncthreads();
-    if (t < T) {
-#pragma unroll
-        for (int p = 0; p < NPL; ++p)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) s[p * (256 * VEC) + t * VEC + v] = acc[p][v];
-    }
-    __syncthreads();
-    for (int e = t; e < NPL * LN; e += 256) {
-        int const p = e / LN, j = e % LN;
-        double const* sp = s + p * (256 * VEC);
-        st_record(out + p * LN + j, (2 == ilv) ? ordered_sum<LN, VEC, T, 2>(sp, j) : (4 == ilv) ? ordered_sum<LN, VEC, T, 4>(sp, j) : ordered_sum<LN, VEC, T, 0>(sp, j), coherent);
-    }
-}
-
-#define TFQ_CHUNK_PROLOGUE(G)                                                     \
-    if (d.ctl->state != 0) return;                                                \
-    int const t = threadIdx.x;                                                    \
-    uint32_t const chunk = blockIdx.x;                                            \
-    uint32_t const first = d.chunkFirst[chunk];                                   \
-    uint32_t const nItems = (d.chunkFirst[chunk + 1] - first) * G::IPB;           \
-    uint32_t const col = d.chunkCol[chunk];                                       \
-    size_t const base = size_t(first) * 2 * G::P;                                 \
-    (void)col;
-
-#define TFQ_ITEM_OFFSETS(G)                                                       \
-    uint32_t const blk = w / G::IPB;                                              \
-    size_t const re = base + size_t(blk) * 2 * G::P + size_t(w - blk * G::IPB) * G::VEC; \
-    size_t const im = re + G::P;
-
-// At the start of a solve v5 is B scattered onto zeros (tfqmrgpu_core.hxx:153): the kernels of the first iteration that read it
-// take the B block under an X block (bOfX), or zeros, directly -- v5 itself is first WRITTEN by k_v5_nrm of that iteration.
-template <typename R, int VEC>
-__device__ inline void ld_rhs(R (&r)[VEC], R (&i)[VEC], DevPlan const& d, uint32_t xblock, size_t inner, int P) {
-    if (d.R) {   // the right-hand side of this solve is a whole X-shaped vector (mixed-precision refinement)
-        R const* b = (R const*)d.R + size_t(xblock) * 2 * P + inner;
-        ldv(r, b); ldv(i, b + P);
-        return;
-    }
-    uint32_t const bq = d.bOfX[xblock];
-    if (0xffffffffu == bq) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) { r[v] = 0; i[v] = 0; }
-    } else {
-        R const* b = (R const*)d.B + size_t(bq) * 2 * P + inner;
-        ldv(r, b); ldv(i, b + P);
-    }
-}
-
 // ---- K0: pz <- v3 . v5 (unconjugated), start of a solve -------------------------------------------
 template <typename R, int LM, int LN>
 __global__ __launch_bounds__(256) void k_dot35(DevPlan d) {
     using G = Geo<R, LM, LN>;
     __shared__ double s[2 * 256 * G::VEC];
-    TFQ_CHUNK_PROLOGUE(G)
+    TFQ_CHUNK_GATE
+    TFQ_CHUNK_SPAN(G)
     double acc[2][G::VEC] = {};
     if (t < G::T) for (uint32_t w = t; w < nItems; w += G::T) {
         TFQ_ITEM_OFFSETS(G)
@@ -196,7 +79,8 @@ __global__ __launch_bounds__(256) void k_dot35(DevPlan d) {
 template <typename R, int LM, int LN>
 __global__ __launch_bounds__(256) void k_xpay_v6(DevPlan d) {
     using G = Geo<R, LM, LN>;
-    TFQ_CHUNK_PROLOGUE(G)
+    TFQ_CHUNK_GATE
+    TFQ_CHUNK_SPAN(G)
     if (t >= G::T) return;
     R const* v5 = (R const*)d.v5; R* v6 = (R*)d.v6;
     Scal<R, LN, G::VEC> beta; beta.load((R const*)d.beta, col, t, d.ilv);
@@ -224,7 +108,8 @@ template <typename R, int LM, int LN>
 __global__ __launch_bounds__(256) void k_v5_nrm(DevPlan d) {
     using G = Geo<R, LM, LN>;
     __shared__ double s[256 * G::VEC];
-    TFQ_CHUNK_PROLOGUE(G)
+    TFQ_CHUNK_GATE
+    TFQ_CHUNK_SPAN(G)
     R* v5 = (R*)d.v5; R const* v9 = (R const*)d.v9;
     double acc[1][G::VEC] = {};
     if (t < G::T) {
@@ -262,7 +147,8 @@ __global__ __launch_bounds__(256) void k_v5_nrm(DevPlan d) {
 template <typename R, int LM, int LN>
 __global__ __launch_bounds__(256) void k_x_v6_v7(DevPlan d) {
     using G = Geo<R, LM, LN>;
-    TFQ_CHUNK_PROLOGUE(G)
+    TFQ_CHUNK_GATE
+    TFQ_CHUNK_SPAN(G)
     if (t >= G::T) return;
     bool const pend = (d.ctl->xpend != 0);
     R* x = (R*)d.x; R* v6 = (R*)d.v6; R* v7 = (R*)d.v7; R const* v4 = (R const*)d.v4;
@@ -313,7 +199,8 @@ template <typename R, int LM, int LN>
 __global__ __launch_bounds__(256) void k_x_flush(DevPlan d) {
     using G = Geo<R, LM, LN>;
     if (d.ctl->probe == 0 || d.ctl->xpend == 0) return;
-    TFQ_CHUNK_PROLOGUE(G)
+    TFQ_CHUNK_GATE
+    TFQ_CHUNK_SPAN(G)
     if (t >= G::T) return;
     R* x = (R*)d.x; R const* v7 = (R const*)d.v7;
     Scal<R, LN, G::VEC> eta; eta.load((R const*)d.eta2, col, t, d.ilv);
@@ -369,16 +256,7 @@ __global__ __launch_bounds__(256) void k_decide(DevPlan d, int what, int phase) 
 }
 
 // ---- start of a solve ---------------------------------------------------------------------------
-// tau := |b|^2 per RHS, 1/|b|^2, rho := 1, everything else 0 (tfqmrgpu_core.hxx:121-127,154-166)
-// the control block
-__device__ inline void reset_ctl(Ctl* c, double tol, int maxIterations, int stallStop) {
-    double const tol2 = tol * tol;
-    c->tol2 = tol2; c->target_bound2 = tol2 * 100 * 100; c->max_bound2 = 0; c->residual2_reached = 1e300; c->probe_bound2 = 0;
-    for (int i = 0; i < 6; ++i) c->red[i] = 0;
-    c->iteration = 0; c->maxIterations = maxIterations;
-    c->state = (maxIterations > 0) ? 0 : 3;
-    c->probe = 0; c->iterations_needed = maxIterations; c->nprobes = 0; c->xpend = 0; c->stallStop = stallStop;
-}
+// (the control block and the scalars: tfq_colops.hpp: reset_ctl, init_col_scalars)
 // tau := |b|^2 per RHS, 1/|b|^2, rho := 1, everything else 0 (tfqmrgpu_core.hxx:121-127,154-166)
 template <typename R, int LM, int LN>
 __global__ __launch_bounds__(256) void k_init_col(DevPlan d, double tol, int maxIterations) {
@@ -399,20 +277,9 @@ __global__ __launch_bounds__(256) void k_init_col(DevPlan d, double tol, int max
     }
     if (g < G) s[g * LN + j] = acc;
     __syncthreads();
-    if (t < LN) {
-        double n2 = 0;
-        for (int gg = 0; gg < G; ++gg) n2 += s[gg * LN + t];
-        size_t const ir = (size_t(col) * 2 + 0) * LN + t, ii = ir + LN, i1 = size_t(col) * LN + t;
-        d.tau[i1] = n2; d.invBn2[i1] = 1. / n2; d.var[i1] = 0; d.d[i1] = 0; d.status[i1] = 0;
-        ((R*)d.rho)[ir] = 1; ((R*)d.rho)[ii] = 0;
-        ((R*)d.alfa)[ir] = 0; ((R*)d.alfa)[ii] = 0; ((R*)d.beta)[ir] = 0; ((R*)d.beta)[ii] = 0;
-        ((R*)d.c67)[ir] = 0; ((R*)d.c67)[ii] = 0; ((R*)d.eta)[ir] = 0; ((R*)d.eta)[ii] = 0;
-        ((R*)d.c67a)[ir] = 0; ((R*)d.c67a)[ii] = 0; ((R*)d.eta2)[ir] = 0; ((R*)d.eta2)[ii] = 0;
-    }
-    if (0 == t) {   // the arrival counters of the folded column operations start every solve at zero, whatever the previous one left
-        d.foldCount[col] = 0;
-        if (0 == col) d.foldCount[d.nCols] = 0;
-    }
+    double n2 = 0;
+    if (t < LN) for (int gg = 0; gg < G; ++gg) n2 += s[gg * LN + t];
+    init_col_scalars<R, LN>(d, col, t, n2, 1. / n2);
     if (0 == col && 0 == t) reset_ctl(d.ctl, tol, maxIterations, 0);
 }
 
@@ -432,7 +299,7 @@ __global__ __launch_bounds__(256) void k_init_col(DevPlan d, double tol, int max
 // block under x -- r = R - Y, in cycle 0 r = R -- with the arithmetic and the sum order of the cold form, whose code the parameter leaves as it was
 template <int LM, int LN, int ILVZ, bool WARM = false>
 __global__ __launch_bounds__(256) void k_refine_residual_q(RefineArgs a) {
-    constexpr int P = LM * LN, T = (256 / LN) * LN, Q = LM / 4, IPB = 2 * Q * LN;   // items per block
+    constexpr int P = LM * LN, T = Geo<float, LM, LN>::T, Q = LM / 4, IPB = 2 * Q * LN;   // items per block
     using f4v = float __attribute__((ext_vector_type(4)));
     using d2v = double __attribute__((ext_vector_type(2)));
     __shared__ double s[256];
@@ -500,7 +367,7 @@ __global__ __launch_bounds__(256) void k_refine_update_q(RefineArgs a) {
 
 template <int LM, int LN, bool WARM = false>
 __global__ __launch_bounds__(256) void k_refine_residual(RefineArgs a) {
-    constexpr int P = LM * LN, T = (256 / LN) * LN;
+    constexpr int P = LM * LN, T = Geo<float, LM, LN>::T;
     __shared__ double s[256];
     DevPlan const& d = a.d;
     int const t = threadIdx.x;
@@ -532,7 +399,6 @@ __global__ __launch_bounds__(256) void k_refine_residual(RefineArgs a) {
 // WARM: |b|^2 is that of B, preset by k_warm_bn2_col (tfq_warm.hip), where cycle 0 of a cold solve takes its own |r|^2 = |b|^2
 template <int LN, bool WARM = false>
 __global__ __launch_bounds__(256) void k_refine_init_col(RefineArgs a) {
-    using R = float;
     __shared__ double s[256];
     __shared__ double rec[LN];
     DevPlan const& d = a.d;
@@ -540,27 +406,19 @@ __global__ __launch_bounds__(256) void k_refine_init_col(RefineArgs a) {
     double dd[1];
     column_sum<LN, 1>(d.pd, d.colChunkPtr[col], d.colChunkPtr[col + 1], s, dd);
     int const t = threadIdx.x;
+    double const n2 = dd[0];
     if (t < LN) {
-        double const n2 = dd[0];
-        size_t const ir = (size_t(col) * 2 + 0) * LN + t, ii = ir + LN, i1 = size_t(col) * LN + t;
+        size_t const i1 = size_t(col) * LN + t;
         if (!WARM && 0 == a.cycle) a.bn2z[i1] = n2;
         double const b2 = a.bn2z[i1];
         rec[t] = (b2 > 0.) ? n2 / b2 : 0.;      // a right-hand side that is zero is solved by x = 0
-        d.tau[i1] = n2; d.invBn2[i1] = 1. / n2; d.var[i1] = 0; d.d[i1] = 0; d.status[i1] = 0;
-        ((R*)d.rho)[ir] = 1; ((R*)d.rho)[ii] = 0;
-        ((R*)d.alfa)[ir] = 0; ((R*)d.alfa)[ii] = 0; ((R*)d.beta)[ir] = 0; ((R*)d.beta)[ii] = 0;
-        ((R*)d.c67)[ir] = 0; ((R*)d.c67)[ii] = 0; ((R*)d.eta)[ir] = 0; ((R*)d.eta)[ii] = 0;
-        ((R*)d.c67a)[ir] = 0; ((R*)d.c67a)[ii] = 0; ((R*)d.eta2)[ir] = 0; ((R*)d.eta2)[ii] = 0;
     }
+    init_col_scalars<float, LN>(d, col, t, n2, 1. / n2);
     __syncthreads();
     if (0 == t) {
         double mx = 0, bad = 0;
         for (int j = 0; j < LN; ++j) { if (rec[j] > mx) mx = rec[j]; if (!(rec[j] == rec[j]) || rec[j] > 1e300) bad = 1; }
         d.colrec[size_t(col) * 2 + 0] = mx; d.colrec[size_t(col) * 2 + 1] = bad;
-    }
-    if (0 == t) {
-        d.foldCount[col] = 0;
-        if (0 == col) d.foldCount[d.nCols] = 0;
     }
     if (0 == col && 0 == t) reset_ctl(d.ctl, a.innerTol, a.innerMaxIt, 1);   // (stallStop: the float iteration has a floor, Ctl::stallStop)
 }
@@ -628,12 +486,9 @@ static hipError_t vec_run(int op, DevPlan const& d, double tol, int maxIt, hipSt
 }
 
 hipError_t vec_launch(int op, DevPlan const& d, double tol, int maxIt, hipStream_t s) {
-    int const key = d.LM * 1000 + d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: return vec_run<R, LM, LN>(op, d, tol, maxIt, s);
-    if (d.dbl) { switch (key) { TFQ_SIZES(TFQ_CASE, double) default: break; } }
-    else       { switch (key) { TFQ_SIZES(TFQ_CASE, float)  default: break; } }
-#undef TFQ_CASE
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;   // stays: no instance for this block shape
+    for_shape(d.dbl, d.LM, d.LN, [&](auto sh) { using S = decltype(sh); e = vec_run<typename S::real, S::LM, S::LN>(op, d, tol, maxIt, s); });
+    return e;
 }
 
 template <int LM, int LN, bool WARM>
@@ -662,10 +517,7 @@ static void refine_run(int what, RefineArgs const& a, hipStream_t s, bool warm) 
     }
 }
 static void refine_dispatch(int what, RefineArgs const& a, hipStream_t s, bool warm) {
-    int const key = a.d.LM * 1000 + a.d.LN;
-#define TFQ_CASE(R, LM, LN) case LM * 1000 + LN: refine_run<LM, LN>(what, a, s, warm); break;
-    switch (key) { TFQ_SIZES(TFQ_CASE, float) default: break; }
-#undef TFQ_CASE
+    for_shape(false, a.d.LM, a.d.LN, [&](auto sh) { using S = decltype(sh); refine_run<S::LM, S::LN>(what, a, s, warm); });
 }
 void launch_refine_residual(RefineArgs const& a, hipStream_t s, bool warm) { refine_dispatch(0, a, s, warm); }
 void launch_refine_update(RefineArgs const& a, hipStream_t s)   { refine_dispatch(1, a, s, false); }
