@@ -767,6 +767,58 @@ tfqmrgpuStatus_t tfqmrgpuExt_projectStart(tfqmrgpuHandle_t handle, tfqmrgpuBsrsv
     double *coefficients /* HOST [nCols][LN][depth][2] (Re, Im), may be NULL */,
     int32_t *nUsed       /* HOST [nCols][LN], may be NULL */);
 
+/* ---- (18) padded plans: any block shape up to 64 x 64 on the listed kernels ---------------------------------------------------------- */
+/* The solver has kernels for the fifteen block shapes of tfqmrgpu_bsrsv_allowedBlockSizes; every other shape ends at bufferSize with
+ * TFQMRGPU_BLOCKSIZE_MISSING.  Callers come with (lmax+1)^2 = 9, 25, 36, with 18 or 50 when spin is included, or with one right-hand side
+ * per block column.  With padding allowed, bufferSize picks the smallest listed shape that holds the caller's, and the operand calls move
+ * the caller's COMPACT blocks into and out of it on the device.  The caller's shape is lm x ln, the plan's LM x LN.
+ *
+ * Why it is exact.  In every block of A, B and X the rows lm ... LM-1 are zero, in A their columns too; the columns ln ... LN-1 of B and X
+ *   are zero; the diagonal blocks of A carry 1 on the padded part of their diagonal.  Then A_pad = A (+) 1 is as regular as A; every Krylov
+ *   vector stays exactly 0 in the padding, because 0 * finite sums to 0 in every multiply; the padded right-hand sides are zero columns of
+ *   B, which the solve and sections 10 to 17 already treat as such; and the inverse in the block-Jacobi set-up (section 7) is A_ii^-1 (+) 1
+ *   -- without the ones every padded diagonal block would be singular and fall back to M_ii = 1.  No iteration kernel, no window of the
+ *   buffer and no reduction knows of the padding: a padded plan IS the plan of shape LM x LN fed with the padded operands, bit for bit.
+ *
+ * allowPadding(plan, on): call it after createPlan and before bufferSize; default 0.  It survives bufferSize and setBuffer, as the
+ *   preconditioner kind does.  A plan pointer that is none: TFQMRGPU_POINTER_INVALID.  A plan that never calls it, or calls it with 0, is
+ *   bit for bit the plan it was: the same statuses (TFQMRGPU_BLOCKSIZE_MISSING included), the same launches, the same buffer.
+ * bufferSize(ldA = blockDim = lm, ldB = RhsBlockDim = ln, ...) on a plan with padding on: the checks ldA == blockDim, ldB == RhsBlockDim and
+ *   the pointer checks stay, in their order; the check lm > ln is dropped -- a caller may bring fewer right-hand sides than rows, down to
+ *   ln = 1; lm < 1 or ln < 1: TFQMRGPU_UNDOCUMENTED_ERROR.  The plan's shape is the listed (LM, LN) with LM >= lm and LN >= ln that has the
+ *   smallest LM for which such an LN exists, then the smallest such LN (LM first: the products cost LM^2 LN).  A listed (lm, ln) picks
+ *   itself; the plan is then not padded and runs the path of a plan without the switch.  lm > 64 or ln > 64: TFQMRGPU_BLOCKSIZE_MISSING
+ *   with lm and ln, as without padding.  The buffer size returned is that of the plan's shape.
+ * paddedShape(plan, &lm, &ln, &LM, &LN): the caller's shape as given to bufferSize, and the plan's; any pointer may be NULL.  Before
+ *   bufferSize: TFQMRGPU_UNDOCUMENTED_ERROR.  On a plan that is not padded the two pairs are equal.
+ *
+ * WHICH CALL SPEAKS WHICH SHAPE.
+ *   The caller's shape: bufferSize and the four operand calls -- setMatrix, getMatrix, setBlocks, getBlocks (section 8), with host or
+ *     device `values`, every layout, every `trans`, 'm' plans with 'c' or 'z' data.  The arrays hold compact blocks: A [nnzbA] blocks of
+ *     lm x lm, B and X blocks of lm x ln (ln x lm where `trans` says so) -- exactly what a plan of that shape without padding would take.
+ *     Setting writes EVERY element of each block of the buffer it touches: the caller's values inside, +0.0 in the padding, 1.0 in the
+ *     real plane of the padded diagonal of the blocks of A whose block row equals their block column; nothing stale survives a set.
+ *     Getting reads the inside only.  All checks and their order are those of a plan without padding: these calls gain no status.
+ *   The plan's shape (paddedShape tells it): the per-right-hand-side arrays of sections 10 to 17, sized [nCols][LN]; getPreconditioner,
+ *     sized [mb][2][LM][LM]; getWorkVector, get / setShadowVector and planView (LM, LN); the flop counts of getInfo, which count the
+ *     padded products.  The padded right-hand sides are zero columns of B: residual2 = bnorm2 = 0 there, which *worst ignores, and
+ *     nUsed = 0.
+ *   carry (section 15) requires equal caller's shapes on both plans as well as equal plan shapes; otherwise its status with the key 'L'.
+ *   tfqmrgpu_bsrsv_z / _c, the Fortran wrappers and allowedBlockSizes are unchanged and keep refusing unlisted shapes.
+ *   A user-defined operator (section 5) on a padded plan: solve returns TFQMRGPU_NO_IMPLEMENTATION, on several ranks through the vote, as
+ *     the preconditioner's refusal travels -- the callback contract names one shape.
+ *
+ * WHAT PADDING COSTS: the buffer, the memory traffic and the products of the PLAN's shape.  25 x 25 on 32 x 32 is 1.64 x the elements of X
+ *   and 2.1 x the products; 9 x 9 on 16 x 16 is 3.2 x and 5.6 x.  What is saved is the host pass over every operand on either side of
+ *   every solve, and setBlocks / getBlocks with device arrays keep their point.
+ * Memory: one byte per block of A in library-owned device memory (which blocks are diagonal blocks), built from A's pattern at the first
+ *   padded transfer of A, uploaded once, released by destroyPlan.  No scratch beyond the staging that the operand calls have.
+ * Several ranks (section 4): local to the rank's plan; every rank pads alike. */
+tfqmrgpuStatus_t tfqmrgpuExt_allowPadding(tfqmrgpuBsrsvPlan_t plan, int on);      /* default 0 */
+tfqmrgpuStatus_t tfqmrgpuExt_paddedShape(tfqmrgpuBsrsvPlan_t plan,
+    int32_t *lm, int32_t *ln,      /* the caller's block shape, as given to bufferSize */
+    int32_t *LM, int32_t *LN);     /* the plan's shape: one of the fifteen; any pointer may be NULL */
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_dropCost", "tfqmrgpuExt_shrinkPattern", "tfqmrgpuExt_solveFrom", "tfqmrgpuExt_carry",
     "tfqmrgpuExt_refineFrom",
     "tfqmrgpuExt_keepStarts", "tfqmrgpuExt_pushStart", "tfqmrgpuExt_startCount", "tfqmrgpuExt_startDepth", "tfqmrgpuExt_projectStart",
+    "tfqmrgpuExt_allowPadding", "tfqmrgpuExt_paddedShape",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -172,6 +173,8 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_startDepth.argtypes = [P]
     lib.tfqmrgpuExt_startDepth.restype = C.c_int32
     lib.tfqmrgpuExt_projectStart.argtypes = [P, P, P, P]
+    lib.tfqmrgpuExt_allowPadding.argtypes = [P, I]
+    lib.tfqmrgpuExt_paddedShape.argtypes = [P] + [C.POINTER(C.c_int32)] * 4
     return lib
 
 
@@ -262,11 +265,25 @@ class Solver:
                     colindx=np.ctypeslib.as_array(v.colindx, (v.nnzbX,)).copy(),
                     original_bsrColIndX=np.ctypeslib.as_array(v.original_bsrColIndX, (v.nCols,)).copy())
 
+    def allow_padding(self, on=True):
+        """tfqmrgpu_ext.h section 18: buffer_size may pick the smallest listed block shape that holds the caller's; call after
+        create_plan and before buffer_size"""
+        return _check(lib.tfqmrgpuExt_allowPadding(self.plan, int(bool(on))), "tfqmrgpuExt_allowPadding")
+
+    def padded_shape(self):
+        """(lm, ln, LM, LN): the caller's block shape as given to buffer_size, and the plan's -- equal unless the plan is padded"""
+        v = [C.c_int32(0) for _ in range(4)]
+        _check(lib.tfqmrgpuExt_paddedShape(self.plan, *[C.byref(x) for x in v]), "tfqmrgpuExt_paddedShape")
+        return tuple(int(x.value) for x in v)
+
     def buffer_size(self, LM, LN, precision):
+        """LM, LN: the caller's block shape.  Afterwards self.lm, self.ln hold it -- the shape of the arrays of set_matrix, get_matrix,
+        set_blocks and get_blocks -- and self.LM, self.LN the plan's shape, which sizes everything else; they differ on a padded plan only"""
         n = C.c_size_t(0)
         _check(lib.tfqmrgpu_bsrsv_bufferSize(self.handle, self.plan, LM, LM, LN, LN, precision.encode(), C.byref(n)),
                "tfqmrgpu_bsrsv_bufferSize")
-        self.LM, self.LN, self.precision = LM, LN, precision
+        self.lm, self.ln, self.LM, self.LN = self.padded_shape()
+        self.precision = precision
         # precision of the host arrays handed to set_matrix / returned by get_matrix: the plan's, for a mixed-precision plan ('m',
         # which takes both) double unless the caller sets data_precision = "c"
         self.data_precision = "z" if precision in "zm" else "c"
@@ -308,31 +325,31 @@ class Solver:
             a = np.ascontiguousarray(a, dtype=self._real_dtype())
         self._keep.append(a)
         st = lib.tfqmrgpu_bsrsv_setMatrix(self.handle, self.plan, var.encode(), _ptr(a), self.data_precision.encode(),
-                                          self.LN if var in "XBxb" else self.LM, self.LM, trans.encode(), layout)
+                                          self.ln if var in "XBxb" else self.lm, self.lm, trans.encode(), layout)
         return _check(st, "tfqmrgpu_bsrsv_setMatrix('%s')" % var)
 
     def set_matrix_device(self, var, device_ptr, trans="n", layout=LAYOUT_RIRIRIRI):
         """the same call with an array that lives in DEVICE memory (data_precision says float or double): the library converts
         straight from it, asynchronously on the handle's stream"""
         st = lib.tfqmrgpu_bsrsv_setMatrix(self.handle, self.plan, var.encode(), C.c_void_p(device_ptr), self.data_precision.encode(),
-                                          self.LN if var in "XBxb" else self.LM, self.LM, trans.encode(), layout)
+                                          self.ln if var in "XBxb" else self.lm, self.lm, trans.encode(), layout)
         return _check(st, "tfqmrgpu_bsrsv_setMatrix('%s', device array)" % var)
 
     def get_matrix_device(self, device_ptr, trans="n", layout=LAYOUT_RIRIRIRI):
         st = lib.tfqmrgpu_bsrsv_getMatrix(self.handle, self.plan, b"X", C.c_void_p(device_ptr), self.data_precision.encode(),
-                                          self.LN, self.LM, trans.encode(), layout)
+                                          self.ln, self.lm, trans.encode(), layout)
         return _check(st, "tfqmrgpu_bsrsv_getMatrix(device array)")
 
     def get_matrix(self, nnzb=None, trans="n", layout=LAYOUT_RIRIRIRI, raw=False):
         nnzb = self.problem.nnzbX if nnzb is None else nnzb
-        out = np.zeros((nnzb, self.LM, self.LN, 2), dtype=self._real_dtype())
+        out = np.zeros((nnzb, self.lm, self.ln, 2), dtype=self._real_dtype())
         st = lib.tfqmrgpu_bsrsv_getMatrix(self.handle, self.plan, b"X", _ptr(out), self.data_precision.encode(),
-                                          self.LN, self.LM, trans.encode(), layout)
+                                          self.ln, self.lm, trans.encode(), layout)
         _check(st, "tfqmrgpu_bsrsv_getMatrix")
         if raw or layout != LAYOUT_RIRIRIRI:
             return out.reshape(nnzb, -1)
         c = out[..., 0] + 1j * out[..., 1]
-        return c if trans in "n*" else c.reshape(nnzb, self.LN, self.LM)
+        return c if trans in "n*" else c.reshape(nnzb, self.ln, self.lm)
 
     # -- listed blocks (tfqmrgpu_ext.h section 8) -------------------------------------------------------
     def set_blocks(self, var, blocks, values, trans="n", layout=LAYOUT_RIRIRIRI):
@@ -365,14 +382,14 @@ class Solver:
     def get_blocks(self, blocks=None, trans="n", layout=LAYOUT_RIRIRIRI, raw=False):
         """the X blocks that `blocks` lists (None: those on B's pattern, in B's block order); shapes as get_matrix"""
         idx, n = self._block_list(blocks)
-        out = np.zeros((n, self.LM, self.LN, 2), dtype=self._real_dtype())
+        out = np.zeros((n, self.lm, self.ln, 2), dtype=self._real_dtype())
         st = lib.tfqmrgpuExt_getBlocks(self.handle, self.plan, b"X", n, None if idx is None else _ptr(idx), _ptr(out),
                                        self.data_precision.encode(), trans.encode(), layout)
         _check(st, "tfqmrgpuExt_getBlocks")
         if raw or layout != LAYOUT_RIRIRIRI:
             return out.reshape(n, -1)
         c = out[..., 0] + 1j * out[..., 1]
-        return c if trans in "n*" else c.reshape(n, self.LN, self.LM)
+        return c if trans in "n*" else c.reshape(n, self.ln, self.lm)
 
     def get_blocks_device(self, device_ptr, blocks=None, trans="n", layout=LAYOUT_RIRIRIRI):
         idx, n = self._block_list(blocks)
@@ -677,11 +694,14 @@ def hash_shadow_vector(pr):
 
 
 def solve_problem(pr, precision="z", threshold=None, max_iterations=2000, transA="n", shadow_mode=SHADOW_HASH, stream=None,
-                  data_precision=None, three_products=False, preconditioner=PRECOND_NONE):
+                  data_precision=None, three_products=False, preconditioner=PRECOND_NONE, allow_padding=False):
     """createPlan .. getMatrix in one go; returns (status, X[nnzbX, LM, LN] complex, info dict).
-    preconditioner=PRECOND_BLOCK_JACOBI: info["n_identity"] = block rows whose M_ii is the unit matrix."""
+    preconditioner=PRECOND_BLOCK_JACOBI: info["n_identity"] = block rows whose M_ii is the unit matrix.
+    allow_padding=True (tfqmrgpu_ext.h section 18): any block shape up to 64 x 64; info["padded_shape"] = (lm, ln, LM, LN)."""
     with Solver(stream) as s:
         s.create_plan(pr)
+        if allow_padding:
+            s.allow_padding(True)
         nbytes = s.buffer_size(pr.LM, pr.LN, precision)
         if data_precision:
             s.data_precision = data_precision
@@ -700,6 +720,8 @@ def solve_problem(pr, precision="z", threshold=None, max_iterations=2000, transA
         info["bound_history"] = s.bound_history()
         info["refinement_history"] = s.refinement_history()
         info["buffer_bytes"] = nbytes
+        if allow_padding:
+            info["padded_shape"] = s.padded_shape()
         X = s.get_matrix()
     return status, X, info
 

@@ -118,17 +118,24 @@ static bool on_device(void const* ptr) {
 }
 
 static tfqmrgpuStatus_t transfer_blocks(Plan& p, hipStream_t s, int direction, bool userDbl, Target const& to,
-    void* host, uint32_t const* u2n, uint32_t nBlocks, int nR, int nC, int layout, bool trans, bool conj, Stage const* own = nullptr,
-    Target const* also = nullptr, uint32_t const* list = nullptr)
+    void* host, uint32_t const* u2n, uint32_t nBlocks, int nR, int nC, int uR, int uC, int layout, bool trans, bool conj, Stage const* own = nullptr,
+    Target const* also = nullptr, uint32_t const* list = nullptr, uint8_t const* unit = nullptr)
 {
+    // uR x uC: the caller's block shape.  It is the library's nR x nC unless the plan is padded (tfqmrgpu_ext.h section 18): then the
+    // two-shape kernels convert (tfq_pad.hip), and `unit` flags the diagonal blocks of A
+    bool const oneShape = (uR == nR && uC == nC);
+    auto convert = [&](int dir, Target const& t, void* stage, uint32_t first, uint32_t n, uint32_t const* l) {
+        if (oneShape) launch_convert(dir, userDbl, t.dbl, t.native, stage, u2n, first, n, nR, nC, layout, trans, conj, t.ilv, s, l);
+        else launch_convert_pad(dir, userDbl, t.dbl, t.native, stage, u2n, unit, first, n, nR, nC, uR, uC, layout, trans, conj, t.ilv, s, l);
+    };
     if (on_device(host)) {   // the caller's array is device memory: one conversion kernel straight from / into it, asynchronous on the stream
-        launch_convert(direction, userDbl, to.dbl, to.native, host, u2n, 0, nBlocks, nR, nC, layout, trans, conj, to.ilv, s, list);
-        if (also && 0 == direction) launch_convert(0, userDbl, also->dbl, also->native, host, u2n, 0, nBlocks, nR, nC, layout, trans, conj, also->ilv, s, list);
+        convert(direction, to, host, 0, nBlocks, list);
+        if (also && 0 == direction) convert(0, *also, host, 0, nBlocks, list);
         TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
         return TFQMRGPU_STATUS_SUCCESS;
     }
     Stage const st = own ? *own : stage_of(p);
-    size_t const blockBytes = size_t(2) * nR * nC * (userDbl ? 8 : 4);
+    size_t const blockBytes = size_t(2) * uR * uC * (userDbl ? 8 : 4);   // the stage is cut by the caller's blocks
     size_t const cap = st.bytes / blockBytes;
     if (cap < 1) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
     for (uint32_t first = 0; first < nBlocks; ) {
@@ -137,10 +144,10 @@ static tfqmrgpuStatus_t transfer_blocks(Plan& p, hipStream_t s, int direction, b
         uint32_t const* const l = list ? list + first : nullptr;
         if (0 == direction) {
             TFQ_HIP(hipMemcpyAsync(st.ptr, h, n * blockBytes, hipMemcpyHostToDevice, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
-            launch_convert(0, userDbl, to.dbl, to.native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, to.ilv, s, l);
-            if (also) launch_convert(0, userDbl, also->dbl, also->native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, also->ilv, s, l);
+            convert(0, to, st.ptr, first, n, l);
+            if (also) convert(0, *also, st.ptr, first, n, l);
         } else {
-            launch_convert(1, userDbl, to.dbl, to.native, st.ptr, u2n, first, n, nR, nC, layout, trans, conj, to.ilv, s, l);
+            convert(1, to, st.ptr, first, n, l);
             TFQ_HIP(hipMemcpyAsync(h, st.ptr, n * blockBytes, hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
         }
         // the stage is reused by the next batch and the host array belongs to the caller
@@ -153,7 +160,7 @@ static tfqmrgpuStatus_t transfer_blocks(Plan& p, hipStream_t s, int direction, b
 
 // an X-shaped native vector of the plan (float or double, as the caller's) <-> the caller's array [nnzbX][2][LM][LN] in its own block order
 static tfqmrgpuStatus_t transfer_x_vector(Plan& p, DevPlan const& d, hipStream_t s, int direction, bool dbl, void* native, void* user, Stage const* own = nullptr) {
-    return transfer_blocks(p, s, direction, dbl, Target{native, dbl, p.ilv}, user, d.u2i, p.nnzbX, p.LM, p.LN, TFQMRGPU_LAYOUT_RRRRIIII, false, false, own);
+    return transfer_blocks(p, s, direction, dbl, Target{native, dbl, p.ilv}, user, d.u2i, p.nnzbX, p.LM, p.LN, p.LM, p.LN, TFQMRGPU_LAYOUT_RRRRIIII, false, false, own);
 }
 
 tfqmrgpuStatus_t upload(void* dst, void const* src, size_t bytes, hipStream_t s) {
@@ -274,11 +281,14 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
     int const ldA, int const blockDim, int const ldB, int const RhsBlockDim, char const precision, size_t* pBufferSizeInBytes)
 {
     // reference tfqmrgpu.cu:364-412
-    int const LM = ldA, LN = ldB;
-    if (LM != blockDim)    return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
-    if (LM > LN)           return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
-    if (LN != RhsBlockDim) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
+    // a plan with padding on (tfqmrgpu_ext.h section 18): ldA, ldB are the CALLER's shape, which may have fewer right-hand sides than rows;
+    // the plan's shape is picked below, behind the checks, and everything behind the pick sees that shape only
     auto p = asPlan(plan);
+    bool const padding = p && p->allowPad;
+    int LM = ldA, LN = ldB;
+    if (LM != blockDim)    return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
+    if (!padding && LM > LN) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
+    if (LN != RhsBlockDim) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
     if (!p || !handle) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     char prec;
     switch (lower(precision)) {            // f,c -> c ; m -> m ; everything else -> z  (tfqmrgpu.cu:383-390)
@@ -287,10 +297,15 @@ tfqmrgpuStatus_t tfqmrgpu_bsrsv_bufferSize(tfqmrgpuHandle_t handle, tfqmrgpuBsrs
         default:  prec = 'z';
     }
     if (nullptr == pBufferSizeInBytes) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (padding) {
+        if (ldA < 1 || ldB < 1) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);
+        if (!paddedBlockSize(ldA, ldB, LM, LN)) return err(TFQMRGPU_BLOCKSIZE_MISSING, ldB, ldA);   // above 64: with the caller's lm and ln, as without padding
+    }
     if (!blockSizeAllowed(LM, LN)) return err(TFQMRGPU_BLOCKSIZE_MISSING, LN, LM); // tfqmrgpu.cu:70
     // 'm': accepted here AND solved (the reference accepts it here and refuses it in solve, tfqmrgpu.cu:42-44, 386): float vectors for
     // the iteration plus x, B and A in double (tfq_plan.cpp: layoutBuffer)
     tfqmrgpuStatus_t st;
+    p->lm = ldA; p->ln = ldB;              // the caller's shape, for the operand calls; layoutBuffer and all behind it see (LM, LN)
     try { st = layoutBuffer(*p, LM, LN, prec); }
     catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     a_new_layout(*p);                      // whatever was sized or cut for the previous layout, or held values of its buffer, ends here
@@ -365,14 +380,31 @@ static tfqmrgpuStatus_t layout_and_trans(tfqmrgpuDataLayout_t const layout, char
 }
 
 // an operand of the plan by its name, as far as the argument checks need it (no buffer yet)
-struct Operand { int which; uint32_t nnzb; int nC; };   // which: 0 A, 1 B, 2 X; blocks of LM x nC
+struct Operand { int which; uint32_t nnzb; int nC, uC; };   // which: 0 A, 1 B, 2 X; blocks of LM x nC, the caller's (section 18) of lm x uC
 static bool operand_of(Plan const& p, char const var, Operand& o) {
     switch (lower(var)) {
-        case 'a': o = Operand{0, p.nnzbA, p.LM}; return true;
-        case 'b': o = Operand{1, p.nnzbB, p.LN}; return true;
-        case 'x': o = Operand{2, p.nnzbX, p.LN}; return true;
+        case 'a': o = Operand{0, p.nnzbA, p.LM, p.lm}; return true;
+        case 'b': o = Operand{1, p.nnzbB, p.LN, p.ln}; return true;
+        case 'x': o = Operand{2, p.nnzbX, p.LN, p.ln}; return true;
         default: return false;
     }
+}
+
+// padded plans (tfqmrgpu_ext.h section 18): which blocks of A are diagonal blocks, by the caller's block index, in device memory.  Built
+// from the pattern at the first padded transfer of A and uploaded once
+static tfqmrgpuStatus_t pad_unit_flags(Plan& p, hipStream_t s) {
+    if (p.padUnit) return TFQMRGPU_STATUS_SUCCESS;
+    try {
+        std::vector<uint8_t> unit(size_t(p.nnzbA), 0);
+        for (size_t q = 0; q < unit.size(); ++q) unit[q] = (p.rowOfA[q] == p.colOfA[q]) ? 1 : 0;
+        if (auto const st = p.padUnit.reserve(unit.size())) return st;
+        // `unit` is a local: wait for the copy.  A copy that failed leaves no flags behind
+        if (hipSuccess != hipMemcpyAsync(p.padUnit.ptr, unit.data(), unit.size(), hipMemcpyHostToDevice, s) || hipSuccess != hipStreamSynchronize(s)) {
+            p.padUnit.release();
+            return TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
+        }
+    } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    return TFQMRGPU_STATUS_SUCCESS;
 }
 
 // setMatrix / getMatrix (reference tfqmrgpu::set_or_getMatrix, tfqmrgpu.cu:467-603) and setBlocks / getBlocks (tfqmrgpu_ext.h section 8)
@@ -444,8 +476,14 @@ static tfqmrgpuStatus_t operand_transfer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvP
         TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
         list = p->blockList.as<uint32_t>();      // (checked: 0 <= blocks[k] < nnzb, so int32 and uint32 read the same)
     }
-    auto const st = transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, nBlocks, p->LM, o.nC, layout, trans, conj, nullptr,
-                                    (mixed && isA && !is_get) ? &floatA : nullptr, list);
+    uint8_t const* unit = nullptr;               // a padded plan (section 18) puts 1 on the padded diagonal of A's diagonal blocks
+    tfqmrgpuStatus_t st = TFQMRGPU_STATUS_SUCCESS;
+    if (p->padded() && isA && !is_get) {
+        st = pad_unit_flags(*p, s);
+        unit = p->padUnit.as<uint8_t>();
+    }
+    if (!st) st = transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, nBlocks, p->LM, o.nC, p->lm, o.uC, layout, trans, conj, nullptr,
+                                    (mixed && isA && !is_get) ? &floatA : nullptr, list, unit);
     if (!listed && isA && !is_get) a_set_whole(*p, !st);
     return st;
 }
@@ -886,7 +924,8 @@ tfqmrgpuStatus_t tfqmrgpuExt_carry(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t 
     if (0 == d->LM || 0 == sp->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);   // bufferSize has not been called
     Operand od{}, os{};
     if (!operand_of(*d, var, od) || !operand_of(*sp, var, os)) return err(TFQMRGPU_VARIABLENAME_UNKNOWN, __LINE__ % 10000, var);
-    if (d->LM != sp->LM || d->LN != sp->LN) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'L');
+    // (padded plans, section 18: the callers' shapes as well)
+    if (d->LM != sp->LM || d->LN != sp->LN || d->lm != sp->lm || d->ln != sp->ln) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'L');
     if (!carry_map_ok(nBlocks, oldBlock, od.nnzb, os.nnzb)) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, var);
     if (0 == od.nnzb) return TFQMRGPU_STATUS_SUCCESS;               // nothing to carry: nothing is touched
     if (nullptr == d->buffer || nullptr == sp->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
@@ -921,6 +960,27 @@ tfqmrgpuStatus_t tfqmrgpuExt_carry(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t 
     if (ok && hipSuccess != hipGetLastError()) st = TFQ_ERR(TFQMRGPU_STATUS_LAUNCH_FAILED);
     if (isA) a_set_whole(*d, !st);
     return st;
+}
+
+// ---- padded plans: any block shape up to 64 x 64 on the listed kernels (tfqmrgpu_ext.h section 18) -------------------------------------------
+// The switch is read by bufferSize, which picks the plan's shape (tfq_plan.cpp: paddedBlockSize); the operand calls then convert between the
+// caller's shape and the plan's (operand_transfer, tfq_pad.hip).  Nothing else knows of it
+tfqmrgpuStatus_t tfqmrgpuExt_allowPadding(tfqmrgpuBsrsvPlan_t plan, int on) {
+    auto p = asPlan(plan);
+    if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    p->allowPad = (0 != on);
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_paddedShape(tfqmrgpuBsrsvPlan_t plan, int32_t* lm, int32_t* ln, int32_t* LM, int32_t* LN) {
+    auto p = asPlan(plan);
+    if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    if (0 == p->LM) return TFQ_ERR(TFQMRGPU_UNDOCUMENTED_ERROR);    // bufferSize has not been called
+    if (lm) *lm = p->lm;
+    if (ln) *ln = p->ln;
+    if (LM) *LM = p->LM;
+    if (LN) *LN = p->LN;
+    return TFQMRGPU_STATUS_SUCCESS;
 }
 
 tfqmrgpuStatus_t tfqmrgpuExt_setReduceCallback(tfqmrgpuHandle_t handle, tfqmrgpuReduceMax_t fn, void* ctx) {

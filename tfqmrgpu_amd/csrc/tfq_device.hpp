@@ -159,6 +159,11 @@ bool multiply_shape_allowed(char precision, int lm, int ln);              // the
 void launch_convert(int direction, bool userDbl, bool nativeDbl, void* native, void* stage, uint32_t const* u2n,
     uint32_t firstUser, uint32_t nBlocks, int nR, int nC, int layout, bool trans, bool conj, int ilv, hipStream_t s,
     uint32_t const* list = nullptr);
+// the same between two shapes (padded plans, tfqmrgpu_ext.h section 18; tfq_pad.hip): the caller's blocks are uR x uC, compact; unit (device
+// memory, by the caller's block index, or nullptr): this block of A is a diagonal block and gets 1 on the padded part of its diagonal
+void launch_convert_pad(int direction, bool userDbl, bool nativeDbl, void* native, void* stage, uint32_t const* u2n, uint8_t const* unit,
+    uint32_t firstUser, uint32_t nBlocks, int nR, int nC, int uR, int uC, int layout, bool trans, bool conj, int ilv, hipStream_t s,
+    uint32_t const* list = nullptr);
 void launch_shadow_hash(DevPlan const& d, hipStream_t s);
 
 } // namespace tfq

@@ -8,21 +8,9 @@
 // applies the user-order -> column-sorted block permutation of the X-shaped operators.
 // Transposed rectangular blocks are indexed as [nC][nR] (the reference mis-indexes them,
 // tfqmrgpu_linalg.hxx:322-328; identical for square blocks).
-#include "tfq_device.hpp"
+#include "tfq_convert.hpp"   // user_offset, shared with the two-shape conversions of tfq_pad.hip
 
 namespace tfq {
-
-// offset of part c of element (r, s) of an nR x nC block in the USER's array
-__device__ inline uint32_t user_offset(int layout, bool trans, int nR, int nC, int r, int s, int c) {
-    int const rows = trans ? nC : nR, cols = trans ? nR : nC;   // shape of the user's array
-    int const i = trans ? s : r, j = trans ? r : s;              // position inside it
-    (void)rows;
-    switch (layout) {
-        case TFQMRGPU_LAYOUT_RRRRIIII: return uint32_t(c * nR * nC + i * cols + j);
-        case TFQMRGPU_LAYOUT_RRIIRRII: return uint32_t(i * 2 * cols + c * cols + j);
-        default:                       return uint32_t((i * cols + j) * 2 + c);  // RIRIRIRI
-    }
-}
 
 // direction 0: nblock := op(ublock) ; direction 1: ublock := op^-1(nblock) -- one block, by the 256 threads of a work group
 template <typename R, typename U>   // R: library side, U: caller's side

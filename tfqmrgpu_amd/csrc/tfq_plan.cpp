@@ -29,6 +29,15 @@ bool blockSizeAllowed(int lm, int ln) {
     return false;
 }
 
+bool paddedBlockSize(int lm, int ln, int& LM, int& LN) {
+    bool found = false;
+    for (auto const& s : kAllowedBlockSizes) {
+        if (s[0] < lm || s[1] < ln) continue;
+        if (!found || s[0] < LM || (s[0] == LM && s[1] < LN)) { LM = s[0]; LN = s[1]; found = true; }
+    }
+    return found;
+}
+
 namespace {
 
 // per block row: (raw column index, position) sorted, to find the FIRST block with a given column

@@ -226,7 +226,8 @@ struct Plan {
 
     // ---- fixed by bufferSize -----------------------------------------------------------------
     int LM = 0, LN = 0;
-    char precision = 0;                // 'c', 'z' or 'm' (mixed: float inner iterations, double refinement; tfq_solve.cpp: run_mixed)
+    int lm = 0, ln = 0;                // the caller's block shape, as given to bufferSize: (LM, LN) unless the plan is padded (tfqmrgpu_ext.h section 18)
+    char precision = 0;               // 'c', 'z' or 'm' (mixed: float inner iterations, double refinement; tfq_solve.cpp: run_mixed)
     size_t realBytes = 0;              // 4 or 8 (the storage precision of the iteration vectors: 4 for 'm')
     size_t S = 0;                      // bytes of one X-shaped vector
     size_t bufferBytes = 0;
@@ -272,6 +273,10 @@ struct Plan {
     DropListing drop;                  // tfqmrgpuExt_dropCost (section 13): the pairs grouped by X block, built at the first call that needs it; patterns only, it outlives bufferSize
     void* warmR = nullptr;             // not null only while a warm solve runs: resolve() hands it to the driver as DevPlan::R
     int startDepth = 0;                // tfqmrgpuExt_keepStarts (section 17): the depth of the ring of kept starts; it stays, as the preconditioner kind does
+    bool allowPad = false;             // tfqmrgpuExt_allowPadding (section 18): bufferSize may pick a listed shape above the caller's; it stays, as the preconditioner kind does
+    DevMem padUnit;                    // padded plans: [nnzbA] bytes, 1 for the diagonal blocks of A (the caller's block order), built from diagOfRow and uploaded at the
+                                       // first padded transfer of A; the pattern's, so it outlives layouts and buffers
+    bool padded() const { return lm != LM || ln != LN; }
 
     // ---- device lists that only grow (reserve), each filled again by every call that reads it: they outlive layouts and buffers
     DevMem keepList;                   // [dirty rows | blocks of the dirty columns] of a partial set-up (tfq_precond_host.cpp: precond_update)
@@ -358,5 +363,8 @@ std::vector<IndexList> indexLists(Plan& p);
 // the 15 compiled (ldA, ldB) pairs of the reference (TFQ_SIZES)
 extern int const kAllowedBlockSizes[15][2];
 bool blockSizeAllowed(int lm, int ln);
+// padded plans (tfqmrgpu_ext.h section 18): the listed shape with LM >= lm and LN >= ln that has the smallest LM for which such an LN exists,
+// then the smallest such LN (the products cost LM^2 LN).  A listed shape picks itself.  false: there is none (lm or ln above 64)
+bool paddedBlockSize(int lm, int ln, int& LM, int& LN);
 
 } // namespace tfq

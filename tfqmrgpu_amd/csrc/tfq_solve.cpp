@@ -635,6 +635,8 @@ tfqmrgpuStatus_t run_solve(Handle& h, Plan& p, double tol, int maxIt) {
     tfqmrgpuStatus_t early = TFQMRGPU_STATUS_SUCCESS;
     if (!p.buffer) early = TFQ_ERR(TFQMRGPU_POINTER_INVALID);
     else if ('z' != p.precision && 'c' != p.precision) early = err(TFQMRGPU_PRECISION_MISSMATCH, __LINE__ % 10000, p.precision);
+    // a user-defined operator on a padded plan (tfqmrgpu_ext.h section 18): the callback contract names ONE block shape
+    if (!early && p.opFn && p.padded()) early = TFQ_ERR(TFQMRGPU_NO_IMPLEMENTATION);
     if (!early) early = precond_prepare(h, p);   // (off: returns at once; a refusal travels through the ranks' vote like the others)
     SolveOutcome o;
     if (auto const st = run_tfqmr(h, p, tol, maxIt, early, 1., o)) return st;
