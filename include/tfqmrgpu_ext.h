@@ -819,6 +819,97 @@ tfqmrgpuStatus_t tfqmrgpuExt_paddedShape(tfqmrgpuBsrsvPlan_t plan,
     int32_t *lm, int32_t *ln,      /* the caller's block shape, as given to bufferSize */
     int32_t *LM, int32_t *LN);     /* the plan's shape: one of the fifteen; any pointer may be NULL */
 
+/* ---- (19) energy mesh: shift A's diagonal, sum X, one call -------------------------------------------------------------------------- */
+/* Sections 8 to 18 serve one loop: solve at energy E1, change the diagonal blocks of A, solve at E2 from what is known.  Where the change
+ * is a multiple of the unit matrix, A(E) = A_base + sigma(E) 1, two steps of that loop still crossed the host at every energy: the caller
+ * added sigma on the host and sent all mb diagonal blocks through setBlocks('A'), and fetched X with getBlocks to add it into a weighted
+ * sum -- a contour integral wants sum_E w_E X(E) on the on-site blocks, not X(E).  shiftDiagonal and the sum do both on the device, and
+ * solveMesh runs the whole loop.  The energies run one after the other through the iteration kernels as they are: nothing that exists changes.
+ *
+ * (19a) shiftDiagonal(handle, plan, sigmaRe, sigmaIm): A := A_base + sigma 1.  Only the diagonal elements of the diagonal blocks of A are
+ *   written -- mb * lm complex numbers, which the device already holds.
+ * A_base is the diagonal of the caller's A as the last setMatrix('A'), setBlocks('A') or carry(.., 'A') (section 15) left it: mb * LM
+ *   complex numbers in the plan's storage precision ('m': double) in library-owned device memory.  The first shift behind such a write
+ *   captures it: from the buffer's A, or from the kept copy (section 9) while the buffer holds A M^-1.  Those three writes call it stale,
+ *   and only where they have written: a setMatrix('A') or carry that has written a whole A all of it, a setBlocks('A') that has succeeded
+ *   the block rows whose diagonal block it names -- their part of the base becomes the diagonal of the blocks it wrote, the other rows
+ *   keep theirs (the A around them may carry a shift), so that a patch between two energies patches A_base, however often it is made.  A
+ *   call that is refused (the wrong precision, no values, ...) has written nothing and leaves the base as it is.
+ *   Shifts do not accumulate: shift(sigma) followed by shift(0) gives back A_base (its bits, but for a -0.0 on the diagonal, which
+ *   -0.0 + 0.0 turns into +0.0 -- on the host as well).
+ * Arithmetic, per component (Re, Im), one rounding each: 'z' and the double A of an 'm' plan: base + sigma in double; 'c': sigma is
+ *   rounded to float once, then added in float; the float A of an 'm' plan gets the shifted DOUBLE value rounded to float (to nearest),
+ *   which is what setBlocks('A') with 'z' data writes there.
+ * Contract: the call is bit for bit setBlocks('A', all diagonal blocks, 'n') with A_base_ii + sigma 1 formed on the host as above --
+ *   in the A window(s) of the buffer, or in the kept copy on a plan whose A is scaled and kept; and in the plan's state: the float floor
+ *   of an 'm' plan is forgotten; on a kept plan every block row and block column that holds a diagonal block is marked, so that the next
+ *   set-up redoes them (section 9); "a whole A has been set" stays as it was.
+ * Padded plans (section 18): only the first lm diagonal elements of a block move; the ones on the padded diagonal stay:
+ *   A_pad = (A + sigma 1) (+) 1.
+ * All checks come before the first device call, in the order of section 8: plan / handle pointers: TFQMRGPU_POINTER_INVALID; no
+ *   bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; a user-defined operator (section 5): TFQMRGPU_NO_IMPLEMENTATION; no buffer:
+ *   TFQMRGPU_POINTER_INVALID; A never set whole on this buffer: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'A'; a block row of A
+ *   without a diagonal block in the pattern -- A + sigma 1 cannot be represented --: TFQMRGPU_UNDOCUMENTED_ERROR with the key character
+ *   'D'; A scaled and no copy kept: TFQMRGPU_NO_IMPLEMENTATION, as setBlocks('A').  After any error nothing has been written.
+ * Memory: the base (mb * LM complex numbers) and, unless the block-Jacobi set-up has uploaded it already (section 7), the list of the
+ *   diagonal blocks (mb indices) are device memory that the library owns, allocated by the first call, released by destroyPlan,
+ *   bufferSize and setBuffer.  A plan that never makes the call allocates nothing.
+ * Stream: one launch ('m': two, the double and the float A) of one thread per diagonal element on the handle's stream, no
+ *   synchronisation; the first call behind a write of A adds one launch that captures, and behind a setBlocks('A') the upload of the
+ *   list of its rows, which synchronises once.  Do not call it during a solve.  Several ranks (section 4): every rank holds all of A and shifts its own.
+ *
+ * (19b) the weighted sum S = sum w X on the nnzbB blocks of X that carry a block of B (tfqmrgpuPlanView_t::subset).
+ * keepSum(plan, on): default off.  Call it after bufferSize; it survives bufferSize and setBuffer as the depth of keepStarts does (the
+ *   sum itself does not: it holds values of one buffer).  Every call, on or off, ends the sum that is held (it waits for the device: the
+ *   call has no stream); behind keepSum(plan, 1) S is zero.  A plan that never calls it is bit for bit the plan it was and allocates nothing.
+ * addToSum(handle, plan, wRe, wIm): S += w X.  X is what getMatrix('X') would return at that moment -- the back-transformed solution on
+ *   a preconditioned plan, the double X of an 'm' plan.  S is complex double in every precision; 'c' data is converted on load (exactly).
+ *   Per element, in exactly this order, every operation rounded once to double, nothing contracted:
+ *     t1 = wRe * xRe;  t2 = wIm * xIm;  S.re += (t1 - t2);      t3 = wRe * xIm;  t4 = wIm * xRe;  S.im += (t3 + t4);
+ *   so that a host restatement in real double arithmetic gives the same bits.  One thread per complex element, no atomics; nothing is
+ *   written into the caller's buffer.
+ * getSum(handle, plan, values, nTerms): values is a HOST array [nnzbB][lm][ln][2] of double -- B's block order, blocks row-major,
+ *   (Re, Im); on a padded plan (section 18) the caller's compact shape, as getBlocks speaks it --; *nTerms the number of addToSum calls
+ *   since the sum was last zero.  Either pointer may be NULL.  It synchronises the stream once where `values` is given.
+ * clearSum(handle, plan): S := 0, *nTerms := 0.
+ * Checks of addToSum, getSum and clearSum, in the order of pushStart (section 17): plan / handle pointers: TFQMRGPU_POINTER_INVALID; no
+ *   bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; keepSum off: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'X'; no buffer:
+ *   TFQMRGPU_POINTER_INVALID.  A user-defined operator (section 5) is accepted: the sum only reads X.
+ * Memory: S, nnzbB * LM * LN complex doubles of library-owned device memory, allocated and cleared by the first addToSum, released by
+ *   destroyPlan, bufferSize, setBuffer and keepSum.  Stream: asynchronous on the handle's stream.  Several ranks (section 4): the sum
+ *   is local to the rank's own block columns; no collective.
+ *
+ * (19c) solveMesh: for e = 0 ... nE - 1 exactly these public calls, in this order:
+ *     1. shiftDiagonal(sigma[e]);
+ *     2. e == 0 and fromX == 0: tfqmrgpu_bsrsv_solve(threshold, maxIterations); otherwise projectStart(NULL, NULL) if startCount > 0,
+ *        then refineFrom(threshold, maxIterations) (section 16; on 'z' and 'c' plans that is solveFrom);
+ *     3. getInfo into iterations[e] and residual[e]; the status of the solve into status[e];
+ *     4. pushStart if startDepth > 0;
+ *     5. addToSum(weight[e]) if weight is given and the sum is kept.
+ *   The mesh is bit for bit the same loop written by the caller.  It stops behind the first energy whose solve returns neither
+ *   TFQMRGPU_STATUS_SUCCESS nor TFQMRGPU_STATUS_MAX_ITERATIONS (steps 4 and 5 of that energy do not run) and returns that status; a
+ *   status other than success of any other step ends it as well and is returned.  Otherwise it returns
+ *   TFQMRGPU_STATUS_MAX_ITERATIONS if the solve of any energy returned it, else TFQMRGPU_STATUS_SUCCESS.  *nDone is the number of
+ *   energies whose solve ran; the host arrays are written for those energies only.  A stays at the last sigma applied, X is the last solution.
+ * Checks in front of the loop, in this order: plan / handle pointers: TFQMRGPU_POINTER_INVALID (*nDone, if given, is 0 from here on);
+ *   sigma == NULL: TFQMRGPU_POINTER_INVALID; nE <= 0: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'E'; several ranks (section 4):
+ *   TFQMRGPU_NO_IMPLEMENTATION, decided from the handle's own rank count -- the same on every rank, no collective, nothing written --; a
+ *   user-defined operator (section 5): TFQMRGPU_NO_IMPLEMENTATION.  Then those of shiftDiagonal, by the call itself.
+ * iterations, residual, status and nDone may be NULL.  The call synchronises where its solves do. */
+tfqmrgpuStatus_t tfqmrgpuExt_shiftDiagonal(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double sigmaRe, double sigmaIm);
+tfqmrgpuStatus_t tfqmrgpuExt_keepSum(tfqmrgpuBsrsvPlan_t plan, int on);                        /* default 0 */
+tfqmrgpuStatus_t tfqmrgpuExt_addToSum(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double wRe, double wIm);
+tfqmrgpuStatus_t tfqmrgpuExt_getSum(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double *values   /* HOST [nnzbB][lm][ln][2] (Re, Im), may be NULL */,
+    int32_t *nTerms  /* may be NULL */);
+tfqmrgpuStatus_t tfqmrgpuExt_clearSum(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan);
+tfqmrgpuStatus_t tfqmrgpuExt_solveMesh(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, int32_t nE,
+    double const *sigma  /* HOST [nE][2] (Re, Im) */,
+    double const *weight /* HOST [nE][2] (Re, Im), may be NULL */,
+    double threshold, int maxIterations, int fromX,
+    int32_t *iterations, double *residual, tfqmrgpuStatus_t *status /* HOST [nE] each, may be NULL */,
+    int32_t *nDone       /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

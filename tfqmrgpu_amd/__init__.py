@@ -46,6 +46,8 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_refineFrom",
     "tfqmrgpuExt_keepStarts", "tfqmrgpuExt_pushStart", "tfqmrgpuExt_startCount", "tfqmrgpuExt_startDepth", "tfqmrgpuExt_projectStart",
     "tfqmrgpuExt_allowPadding", "tfqmrgpuExt_paddedShape",
+    "tfqmrgpuExt_shiftDiagonal", "tfqmrgpuExt_keepSum", "tfqmrgpuExt_addToSum", "tfqmrgpuExt_getSum", "tfqmrgpuExt_clearSum",
+    "tfqmrgpuExt_solveMesh",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -175,6 +177,12 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_projectStart.argtypes = [P, P, P, P]
     lib.tfqmrgpuExt_allowPadding.argtypes = [P, I]
     lib.tfqmrgpuExt_paddedShape.argtypes = [P] + [C.POINTER(C.c_int32)] * 4
+    lib.tfqmrgpuExt_shiftDiagonal.argtypes = [P, P, C.c_double, C.c_double]
+    lib.tfqmrgpuExt_keepSum.argtypes = [P, I]
+    lib.tfqmrgpuExt_addToSum.argtypes = [P, P, C.c_double, C.c_double]
+    lib.tfqmrgpuExt_getSum.argtypes = [P, P, P, C.POINTER(C.c_int32)]
+    lib.tfqmrgpuExt_clearSum.argtypes = [P, P]
+    lib.tfqmrgpuExt_solveMesh.argtypes = [P, P, C.c_int32, P, P, C.c_double, I, I, P, P, P, C.POINTER(C.c_int32)]
     return lib
 
 
@@ -445,6 +453,51 @@ class Solver:
         used = np.zeros((n, self.LN), np.int32)
         _check(lib.tfqmrgpuExt_projectStart(self.handle, self.plan, _ptr(g), _ptr(used)), "tfqmrgpuExt_projectStart")
         return dict(coefficients=(g[..., 0] + 1j * g[..., 1])[:, :, :depth], n_used=used)
+
+    # -- energy mesh (tfqmrgpu_ext.h section 19) ----------------------------------------------------------
+    def shift_diagonal(self, sigma):
+        """A := A_base + sigma * 1 on the device: the diagonal elements of A's diagonal blocks, from the diagonal that the last
+        set_matrix('A') / set_blocks('A') / carry_from(.., 'A') left; shifts do not accumulate.  Bit for bit set_blocks('A') of all
+        diagonal blocks with the sum formed on the host in the storage precision.  Returns the raw status"""
+        sigma = complex(sigma)
+        return _check(lib.tfqmrgpuExt_shiftDiagonal(self.handle, self.plan, sigma.real, sigma.imag), "tfqmrgpuExt_shiftDiagonal")
+
+    def keep_sum(self, on=True):
+        """keep a weighted sum of X on B's pattern in the plan (off by default); call after buffer_size.  Every call zeroes the sum"""
+        return _check(lib.tfqmrgpuExt_keepSum(self.plan, int(bool(on))), "tfqmrgpuExt_keepSum")
+
+    def add_to_sum(self, weight):
+        """S += weight * X on the blocks of X that carry a block of B, in double on the device; X is what get_matrix would return now"""
+        w = complex(weight)
+        return _check(lib.tfqmrgpuExt_addToSum(self.handle, self.plan, w.real, w.imag), "tfqmrgpuExt_addToSum")
+
+    def get_sum(self):
+        """(S as complex128 [nnzbB, lm, ln] in B's block order, the number of add_to_sum calls since the sum was last zero)"""
+        out = np.zeros((self.problem.nnzbB, self.lm, self.ln, 2), np.float64)
+        n = C.c_int32(0)
+        _check(lib.tfqmrgpuExt_getSum(self.handle, self.plan, C.c_void_p(out.ctypes.data), C.byref(n)), "tfqmrgpuExt_getSum")
+        return out.view(np.complex128)[..., 0], int(n.value)      # (Re, Im) pairs are complex128 as they lie: no arithmetic touches the bits
+
+    def clear_sum(self):
+        return _check(lib.tfqmrgpuExt_clearSum(self.handle, self.plan), "tfqmrgpuExt_clearSum")
+
+    def solve_mesh(self, sigma, weight, threshold, max_iterations, from_x=False):
+        """the energy loop in one call: per energy shift_diagonal(sigma[e]); solve (the first energy unless from_x) or project_start
+        where starts are held and refine_from; push_start where keep_starts is on; add_to_sum(weight[e]) where weights are given
+        and keep_sum is on.  sigma, weight: complex sequences (weight may be None).  Returns a dict: status (of the call: 0, 9, or what
+        ended the loop early), n_done, and per energy that ran iterations, residual, statuses"""
+        sg = np.ascontiguousarray(np.asarray(sigma, dtype=np.complex128).reshape(-1)).view(np.float64)
+        n = len(sg) // 2
+        wt = None if weight is None else np.ascontiguousarray(np.asarray(weight, dtype=np.complex128).reshape(-1)).view(np.float64)
+        if wt is not None and len(wt) != len(sg):
+            raise ValueError("solve_mesh: one weight per energy")
+        its, res, sts = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.int32)
+        done = C.c_int32(0)
+        st = lib.tfqmrgpuExt_solveMesh(self.handle, self.plan, n, _ptr(sg), None if wt is None else _ptr(wt), threshold, max_iterations,
+                                       int(bool(from_x)), _ptr(its), _ptr(res), _ptr(sts), C.byref(done))
+        _check(st, "tfqmrgpuExt_solveMesh", allowed=(0, 6, 9))
+        k = int(done.value)
+        return dict(status=st, n_done=k, iterations=its[:k].copy(), residual=res[:k].copy(), statuses=sts[:k].copy())
 
     # -- operands from another plan (tfqmrgpu_ext.h section 15) ---------------------------------------------
     def carry_from(self, src, var, old_block=None):

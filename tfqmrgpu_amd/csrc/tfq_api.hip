@@ -3,7 +3,8 @@
 // argument meaning and status codes); the implementation behind them is this library's own.
 // The solve itself -- the tfQMR driver, the refinement, the reset of Plan::last -- is tfq_solve.cpp; the preconditioner's set-up, the state of
 // the A in the buffer and the ends of Plan::layout (bufferSize) and Plan::held (bufferSize, setBuffer) are tfq_precond_host.cpp; the calls that
-// grade the caller's system (tfqmrgpu_ext.h sections 10 to 13) are tfq_grade_host.cpp; the start projection (section 17) is tfq_project_host.cpp.
+// grade the caller's system (tfqmrgpu_ext.h sections 10 to 13) are tfq_grade_host.cpp; the start projection (section 17) is tfq_project_host.cpp;
+// the energy mesh (section 19), its six entry points included, is tfq_mesh_host.cpp.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -485,6 +486,7 @@ static tfqmrgpuStatus_t operand_transfer(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvP
     if (!st) st = transfer_blocks(*p, s, is_get ? 1 : 0, user_double, to, values, u2n, nBlocks, p->LM, o.nC, p->lm, o.uC, layout, trans, conj, nullptr,
                                     (mixed && isA && !is_get) ? &floatA : nullptr, list, unit);
     if (!listed && isA && !is_get) a_set_whole(*p, !st);
+    if (listed && isA && !is_get && !st) a_patch_written(*p, blocks, nListed);
     return st;
 }
 

@@ -273,6 +273,7 @@ struct Plan {
     DropListing drop;                  // tfqmrgpuExt_dropCost (section 13): the pairs grouped by X block, built at the first call that needs it; patterns only, it outlives bufferSize
     void* warmR = nullptr;             // not null only while a warm solve runs: resolve() hands it to the driver as DevPlan::R
     int startDepth = 0;                // tfqmrgpuExt_keepStarts (section 17): the depth of the ring of kept starts; it stays, as the preconditioner kind does
+    bool keepSum = false;              // tfqmrgpuExt_keepSum (section 19b): the plan keeps a weighted sum of X on B's pattern; it stays, as the depth of the starts does
     bool allowPad = false;             // tfqmrgpuExt_allowPadding (section 18): bufferSize may pick a listed shape above the caller's; it stays, as the preconditioner kind does
     DevMem padUnit;                    // padded plans: [nnzbA] bytes, 1 for the diagonal blocks of A (the caller's block order), built from diagOfRow and uploaded at the
                                        // first padded transfer of A; the pattern's, so it outlives layouts and buffers
@@ -317,6 +318,17 @@ struct Plan {
                                        // it is the caller's A while precondInA != NONE, stale otherwise
         std::vector<uint8_t> dirtyRow, dirtyCol;   // [nRows] since the last set-up setBlocks('A') has written: the diagonal block of this row | a block of this column
         bool anyDirty = false;
+        // energy mesh (section 19; tfq_mesh_host.cpp).  shiftBase: [nRows][LM][2] the diagonal of the caller's A in the storage type ('m':
+        // double), captured by the first shiftDiagonal behind a WHOLE write of A (shiftBaseFresh: none since; a_set_whole clears it).
+        // shiftStaleRow [nRows], shiftAnyStale: setBlocks('A') has written the diagonal block of this row since (a_patch_written): the next
+        // shift captures these rows again, through the device list shiftRows.  shiftDiag: diagOfRow on the device where layout.precond has no
+        // copy of it.  All allocated by the shiftDiagonal that first needs them.
+        // sumMem: S [nnzbB][LM][LN][2] of double, allocated and cleared by the first addToSum; sumTerms: the addToSum calls since the last clear
+        DevMem shiftBase, shiftDiag, shiftRows;
+        bool shiftBaseFresh = false, shiftAnyStale = false;
+        std::vector<uint8_t> shiftStaleRow;
+        DevMem sumMem;
+        int32_t sumTerms = 0;
     } held;
 
     // ---- of the last solve: what it leaves for getInfo, the histories and the profile.  The start of the next solve ends it

@@ -41,6 +41,7 @@ void a_new_buffer(Plan& p);                             // setBuffer: ends Plan:
 void a_named(Plan& p);                                  // setMatrix('A'), before its argument checks
 void a_set_whole(Plan& p, bool ok);                     // setMatrix('A'), behind its transfer
 tfqmrgpuStatus_t a_patched(Plan& p, int32_t const* blocks, int32_t nBlocks, bool& intoKept);   // setBlocks('A'), behind its argument checks
+void a_patch_written(Plan& p, int32_t const* blocks, int32_t nBlocks);   // setBlocks('A'), behind its transfer, which succeeded
 tfqmrgpuStatus_t a_keep(Plan& p, bool on);              // keepOperator
 
 #pragma GCC visibility pop

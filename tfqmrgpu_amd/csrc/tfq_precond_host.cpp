@@ -89,10 +89,26 @@ void a_new_layout(Plan& p) {
 void a_named(Plan& p) { p.mixedFloor = 0; }
 
 // setMatrix('A') behind its transfer (ok: it succeeded): the A in the buffer is a new one and not scaled -- M^-1 of the last one is stale, and
-// so is a kept copy with its marks (the copy itself stays allocated: the next set-up fills it again)
+// so is a kept copy with its marks (the copy itself stays allocated: the next set-up fills it again).  The diagonal that shiftDiagonal has
+// captured (section 19a) was that of the last A: the next shift captures all of it again.  Here and not in a_named: a setMatrix('A') that
+// is refused has written nothing, and the A in the buffer may carry a shift that a capture would take for the base.  (A transfer that
+// failed leaves no whole A -- !ok -- and shiftDiagonal refuses until one has succeeded, which comes through here again)
 void a_set_whole(Plan& p, bool ok) {
     p.held.haveA = ok; p.held.precondInA = TFQMRGPU_PRECOND_NONE;
     forget_dirty(p);
+    p.held.shiftBaseFresh = false;
+    std::fill(p.held.shiftStaleRow.begin(), p.held.shiftStaleRow.end(), uint8_t(0)); p.held.shiftAnyStale = false;
+}
+
+// setBlocks('A') behind its transfer, which succeeded: the rows of the captured diagonal (section 19a) whose diagonal block it has written
+// are captured again by the next shift, from the blocks it wrote; the other rows keep their base -- the A around them may carry a shift.
+// One flag per block row (sized by the shift that captured the base; no base, no flags): patching one block any number of times is one flag
+void a_patch_written(Plan& p, int32_t const* blocks, int32_t nBlocks) {
+    if (!p.held.shiftBaseFresh || p.held.shiftStaleRow.size() != size_t(p.nRows)) return;
+    for (int32_t k = 0; k < nBlocks; ++k) {
+        uint32_t const q = uint32_t(blocks[k]), c = p.colOfA[q];
+        if (p.diagOfRow[c] == q) { p.held.shiftStaleRow[c] = 1; p.held.shiftAnyStale = true; }
+    }
 }
 
 // setBlocks('A') has passed its argument checks (0 <= blocks[k] < nnzbA, no block twice) and is about to write: where do the blocks go?
