@@ -57,6 +57,11 @@ class Case:
         return self.failed[self.col_of_block]
 
 
+def row_ids(rows):
+    """pytest ids of (kind, shape, precision) rows"""
+    return ["%s-%s-%s" % r for r in rows]
+
+
 def j_star(LN):
     return (5 * LN) // 8
 

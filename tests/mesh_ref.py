@@ -4,12 +4,7 @@ library's code nor its lists."""
 import numpy as np
 
 import tfqmrgpu_amd as T
-
-
-def diagonal_blocks(pr):
-    """positions (the caller's block order of A) of the blocks whose block row equals their block column"""
-    rows = np.repeat(np.arange(pr.mb), np.diff(pr.rowPtrA))
-    return np.flatnonzero(rows == np.asarray(pr.colIndA, dtype=np.int64) - pr.index_offset)
+from helpers import diagonal_blocks  # noqa: F401  (the tests reach it as mesh_ref.diagonal_blocks)
 
 
 def shifted_diagonal_blocks(A, diag, prec, sigma):

@@ -20,11 +20,7 @@ FOLD = [(kind, shape, prec) for prec in "zc" for shape in BC.FOLD_SHAPES[prec] f
 SEGMENTED = [(kind, "8x64seg3" if kind == "column" else "8x64seg", "z") for kind in BC.KINDS]
 
 
-def _ids(rows):
-    return ["%s-%s-%s" % r for r in rows]
-
-
-@pytest.mark.parametrize("kind,shape,prec", FOLD + SEGMENTED, ids=_ids(FOLD + SEGMENTED))
+@pytest.mark.parametrize("kind,shape,prec", FOLD + SEGMENTED, ids=BC.row_ids(FOLD + SEGMENTED))
 def test_fixture_reaches_its_branch(oracle, kind, shape, prec):
     c = BC.case(kind, shape)
     st, X, info = BC.oracle_solve(oracle, c, prec, status=True)

@@ -8,6 +8,7 @@ import pytest
 
 import tfqmrgpu_amd as T
 from conftest import offset1
+from helpers import exact_random_blocks, real_dtype, torch_cuda, user_array  # noqa: F401  (torch_cuda: a fixture)
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -21,36 +22,8 @@ TOL = {"z": 1e-9, "c": 1e-4, "m": 1e-9}
 MAXIT = 500
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "the gpu tests need a GPU; there is no CPU fallback"
-    torch.cuda.set_device(0)
-    return torch
-
-
 def _small(LM, LN):
     return PR.stencil_2d(4, 3, LM, LN, 3, seed=12, radius=1.6)   # the plans of test_set_get_matrix_layouts
-
-
-def _real(prec):
-    return np.float32 if prec == "c" else np.float64
-
-
-def _user_array(blocks, layout, trans):
-    """what a caller hands over for complex blocks [n, R, C] in that layout and transposition"""
-    m = {"n": blocks, "t": blocks.transpose(0, 2, 1), "*": blocks.conj(), "c": blocks.conj().transpose(0, 2, 1)}[trans]
-    if layout == T.LAYOUT_RIRIRIRI:
-        return np.stack([m.real, m.imag], axis=-1).reshape(len(m), -1)
-    if layout == T.LAYOUT_RRRRIIII:
-        return np.stack([m.real, m.imag], axis=1).reshape(len(m), -1)
-    return np.stack([m.real, m.imag], axis=2).reshape(len(m), -1)  # RRIIRRII
-
-
-def _random(rng, n, rows, cols, prec):
-    """complex blocks that the plan's precision holds exactly"""
-    v = rng.standard_normal((n, rows, cols)) + 1j * rng.standard_normal((n, rows, cols))
-    return v.astype(np.complex64).astype(np.complex128) if prec == "c" else v
 
 
 def _half_list(rng, n, twice):
@@ -112,9 +85,8 @@ def test_get_blocks_is_a_slice_of_get_matrix(prec, shape):
     rng = np.random.default_rng(100 * LM + LN)
     idx = _half_list(rng, pr.nnzbX, twice=True)
     assert len(set(idx)) == len(idx) - 1 and {0, pr.nnzbX - 1} <= set(idx) and np.any(np.diff(idx) < 0)
-    with T.Solver() as s:
-        _plan(s, pr, prec)
-        s.set_matrix("X", _random(rng, pr.nnzbX, LM, LN, prec))
+    with T.Solver.open(pr, prec) as s:
+        s.set_matrix("X", exact_random_blocks(rng, pr.nnzbX, LM, LN, prec))
         for layout in LAYOUTS:
             for tr in TRANS:
                 whole = s.get_matrix(trans=tr, layout=layout, raw=True)
@@ -133,15 +105,14 @@ def test_set_blocks_changes_the_listed_blocks_of_x_only(prec, shape):
     pr = _small(LM, LN)
     rng = np.random.default_rng(200 * LM + LN)
     idx = _half_list(rng, pr.nnzbX, twice=False)
-    X0, V = _random(rng, pr.nnzbX, LM, LN, prec), _random(rng, len(idx), LM, LN, prec)
+    X0, V = exact_random_blocks(rng, pr.nnzbX, LM, LN, prec), exact_random_blocks(rng, len(idx), LM, LN, prec)
     want = X0.copy()
     want[idx] = V
-    with T.Solver() as s:
-        _plan(s, pr, prec)
+    with T.Solver.open(pr, prec) as s:
         for layout in LAYOUTS:
             for tr in TRANS:
                 s.set_matrix("X", X0)
-                s.set_blocks("X", idx, _user_array(V, layout, tr).astype(_real(prec)), tr, layout)
+                s.set_blocks("X", idx, user_array(V, layout, tr).astype(real_dtype(prec)), tr, layout)
                 assert np.array_equal(s.get_matrix(), want), (layout, tr)
 
 
@@ -155,7 +126,7 @@ def test_set_blocks_of_b_is_set_matrix_of_b(prec, shape):
     rng = np.random.default_rng(300 * LM + LN)
     assert pr.nnzbB == 3
     some = np.array([2, 0], np.int32)
-    V = _random(rng, len(some), LM, LN, prec)
+    V = exact_random_blocks(rng, len(some), LM, LN, prec)
     B1 = pr.B.copy()
     B1[some] = V
     every = np.arange(pr.nnzbB, dtype=np.int32)[::-1]
@@ -172,7 +143,7 @@ def test_set_blocks_of_b_is_set_matrix_of_b(prec, shape):
         for layout in LAYOUTS:
             for tr in TRANS:
                 s.set_matrix("B", pr.B)
-                s.set_blocks("B", some, _user_array(V, layout, tr).astype(_real(prec)), tr, layout)
+                s.set_blocks("B", some, user_array(V, layout, tr).astype(real_dtype(prec)), tr, layout)
                 _same(_solve(s, prec), patched)
         s.set_matrix("B", B1)
         s.set_blocks("B", every, pr.B[every])
@@ -185,8 +156,7 @@ def test_diagonal_update_of_a_is_the_whole_update(prec, shape):
     LM, LN = shape
     pr = _small(LM, LN)
     diag, A1 = _other_diagonal(pr)
-    with T.Solver() as q:
-        _plan(q, pr, prec)
+    with T.Solver.open(pr, prec) as q:
         q.set_matrix("A", A1)
         q.set_matrix("B", pr.B)
         want = _solve(q, prec)
@@ -194,8 +164,7 @@ def test_diagonal_update_of_a_is_the_whole_update(prec, shape):
         assert not np.array_equal(_solve(q, prec)["X"], want["X"])      # the diagonal matters
     assert want["status"] == 0 and want["iterations"] <= 20
     for tr in "nt":
-        with T.Solver() as s:
-            _plan(s, pr, prec)
+        with T.Solver.open(pr, prec) as s:
             s.set_matrix("A", pr.A)
             s.set_blocks("A", diag, A1[diag] if tr == "n" else A1[diag].transpose(0, 2, 1), tr)
             s.set_matrix("B", pr.B)
@@ -208,8 +177,7 @@ def test_diagonal_update_of_a_is_the_whole_update(prec, shape):
 def test_blocks_on_the_pattern_of_b(prec, shape, off):
     pr = _small(*shape)
     pr = offset1(pr) if off else pr
-    with T.Solver() as s:
-        _plan(s, pr, prec)
+    with T.Solver.open(pr, prec) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(TOL[prec], MAXIT) == 0
@@ -251,9 +219,8 @@ def test_device_arrays_give_the_bytes_of_the_host_path(torch_cuda, prec):
     rng = np.random.default_rng(6)
     ctype = np.complex64 if prec == "c" else np.complex128
     idx = _half_list(rng, pr.nnzbX, twice=False)
-    X0, V = _random(rng, pr.nnzbX, LM, LN, prec), _random(rng, len(idx), LM, LN, prec)
-    with T.Solver() as s:
-        _plan(s, pr, prec)
+    X0, V = exact_random_blocks(rng, pr.nnzbX, LM, LN, prec), exact_random_blocks(rng, len(idx), LM, LN, prec)
+    with T.Solver.open(pr, prec) as s:
         for tr in "nc":
             s.set_matrix("X", X0)
             s.set_blocks("X", idx, V, tr)
@@ -307,8 +274,7 @@ def test_plans_that_do_not_call_it_see_nothing():
     pr = _small(16, 16)
     runs = []
     for calls in (False, True):
-        with T.Solver() as s:
-            _plan(s, pr, "z")
+        with T.Solver.open(pr, "z") as s:
             s.set_matrix("A", pr.A)
             s.set_matrix("B", pr.B)
             assert s.solve(TOL["z"], MAXIT) == 0

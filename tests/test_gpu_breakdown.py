@@ -22,17 +22,13 @@ import residual_ref as RR
 import tfqmrgpu_amd as T
 from conftest import ROOT
 from plan_paths import gpu_state, plan_paths, state_deviation, true_residual
-from test_gpu_families import C_BOUND, Z_BOUND
+from helpers import C_BOUND, Z_BOUND
 
 pytestmark = pytest.mark.gpu
 
 X_BOUND = {"z": 1e-7, "c": 1e-3}
 FOLD = [(kind, shape, prec) for prec in "zc" for shape in BC.FOLD_SHAPES[prec] for kind in BC.KINDS]
 SEGMENTED = [(kind, "8x64seg3" if kind == "column" else "8x64seg", "z") for kind in BC.KINDS]
-
-
-def _ids(rows):
-    return ["%s-%s-%s" % r for r in rows]
 
 
 @functools.lru_cache(maxsize=None)
@@ -73,14 +69,14 @@ def _against_the_oracle(oracle, kind, shape, prec):
             assert max(worst.values()) <= bounds[k], (k, worst)
 
 
-@pytest.mark.parametrize("kind,shape,prec", FOLD, ids=_ids(FOLD))
+@pytest.mark.parametrize("kind,shape,prec", FOLD, ids=BC.row_ids(FOLD))
 def test_folded_forms_against_the_oracle(oracle, kind, shape, prec):
     ch, seg, folds = plan_paths(_case(kind, shape).pr, prec)
     assert folds is True and len(ch) == 2
     _against_the_oracle(oracle, kind, shape, prec)
 
 
-@pytest.mark.parametrize("kind,shape,prec", SEGMENTED, ids=_ids(SEGMENTED))
+@pytest.mark.parametrize("kind,shape,prec", SEGMENTED, ids=BC.row_ids(SEGMENTED))
 def test_segmented_columns_against_the_oracle(oracle, kind, shape, prec):
     ch, seg, folds = plan_paths(_case(kind, shape).pr, prec)
     assert seg[0] > 1 and min(seg) > 1 and not folds

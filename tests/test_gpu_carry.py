@@ -6,6 +6,7 @@ import pytest
 
 import tfqmrgpu_amd as T
 from conftest import load_problem
+from helpers import same_typed_bits, with_a
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -17,31 +18,8 @@ FIXTURES = ["fd_4x4_2d", "fd_16x16_small", "fd_8x8_3d", "stencil_8x32", "dense_r
 REAL = {"z": np.float64, "m": np.float64, "c": np.float32}
 
 
-def _open(pr, prec, kind=None, keep=False):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    s.set_buffer(nbytes=nbytes)
-    return s
-
-
-def _loaded(pr, prec, A=None, **kw):
-    s = _open(pr, prec, **kw)
-    s.set_matrix("A", pr.A if A is None else A)
-    s.set_matrix("B", pr.B)
-    return s
-
-
 def _with_x(pr, rowPtrX, colIndX):
     return T.Problem(pr.rowPtrA, pr.colIndA, pr.A, rowPtrX, colIndX, pr.rowPtrB, pr.colIndB, pr.B, None, pr.tolerance, pr.index_offset)
-
-
-def _with_a(pr, A):
-    return T.Problem(pr.rowPtrA, pr.colIndA, A, pr.rowPtrX, pr.colIndX, pr.rowPtrB, pr.colIndB, pr.B, None, pr.tolerance, pr.index_offset)
 
 
 def _raw_x(s):
@@ -49,11 +27,6 @@ def _raw_x(s):
     x = s.get_matrix(raw=True)
     assert x.dtype == REAL[s.precision]
     return x
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def _mapped(x, old, dtype):
@@ -73,7 +46,7 @@ def _droppable(s, pr):
 
 def _carried_x(src, pattern, old, prec):
     """a fresh plan of `pattern` in precision `prec`, its X filled with ones, then carried into from src: what it returns"""
-    with _open(pattern, prec) as d:
+    with T.Solver.open(pattern, prec) as d:
         d.set_matrix("X", np.ones((pattern.nnzbX, pattern.LM, pattern.LN), dtype=complex))       # the zero blocks must be WRITTEN
         assert d.carry_from(src, "X", old) == 0
         return _raw_x(d)
@@ -100,17 +73,17 @@ def _patterns(src, pr):
 @pytest.mark.parametrize("name,prec", [(n, p) for n in FIXTURES for p in "zc"] + [("fd_16x16_small", "m"), ("fd_4x4_2d", "m")])
 def test_x_same_precision_bit_for_bit(name, prec):
     pr = load_problem(name)
-    with _loaded(pr, prec) as src:
+    with T.Solver.open(pr, prec).load() as src:
         src.solve(1e-30, 3)
         xs = _raw_x(src)
         assert np.abs(xs).max() > 0
         for what, pattern, old in _patterns(src, pr):
             got = _carried_x(src, pattern, old, prec)
-            assert _same_bits(got, _mapped(xs, old, REAL[prec])), (name, prec, what)
+            assert same_typed_bits(got, _mapped(xs, old, REAL[prec])), (name, prec, what)
         # no list: the identity, through the internal orders of both plans
-        with _open(pr, prec) as d:
+        with T.Solver.open(pr, prec) as d:
             assert d.carry_from(src, "X") == 0
-            assert _same_bits(_raw_x(d), xs)
+            assert same_typed_bits(_raw_x(d), xs)
 
 
 # ---- 2. X across precisions ------------------------------------------------------------------------------------------------------------------
@@ -120,12 +93,12 @@ def test_x_across_precisions(name, ps, pd):
     """float -> double is exact, double -> float rounds to nearest once (numpy's astype); 'm' stores X in double, as 'z' does.  The element
     order inside a block changes with the precision (16 x 16: quads in float, pairs in double)"""
     pr = load_problem(name)
-    with _loaded(pr, ps) as src:
+    with T.Solver.open(pr, ps).load() as src:
         src.solve(1e-30, 3)
         xs = _raw_x(src)
         for what, pattern, old in _patterns(src, pr)[:2]:
             got = _carried_x(src, pattern, old, pd)
-            assert _same_bits(got, _mapped(xs, old, REAL[pd])), (name, ps, pd, what)
+            assert same_typed_bits(got, _mapped(xs, old, REAL[pd])), (name, ps, pd, what)
 
 
 # ---- 3. A and B ------------------------------------------------------------------------------------------------------------------------------
@@ -147,7 +120,7 @@ def _same_record(got, want):
         if k in ("status", "info"):
             assert got[k] == want[k], k
         else:
-            assert _same_bits(got[k], want[k]), k
+            assert same_typed_bits(got[k], want[k]), k
     assert len(want["bounds"]) >= 1
 
 
@@ -159,7 +132,7 @@ def test_a_and_b_solve_as_a_twin_loaded_from_the_host(name, ps, pd):
     writes both copies of A: the float one drives the inner solves, the double one the refinement history"""
     pr = load_problem(name)
     stored = (lambda a: a.astype(np.complex64).astype(np.complex128)) if ps == "c" else (lambda a: a)
-    with _loaded(pr, ps) as src, _open(pr, pd) as dst, _open(pr, pd) as twin:
+    with T.Solver.open(pr, ps).load() as src, T.Solver.open(pr, pd) as dst, T.Solver.open(pr, pd) as twin:
         assert dst.carry_from(src, "A") == 0
         assert dst.carry_from(src, "B") == 0
         twin.set_matrix("A", stored(pr.A))
@@ -182,7 +155,7 @@ def test_source_a_of_a_preconditioned_plan_that_keeps_it(prec):
     has seen: the carried A is the caller's patched A"""
     pr = load_problem("fd_16x16_small")
     diag, A1 = _patched(pr)
-    with _loaded(pr, prec, kind=BJ, keep=True) as src, _open(pr, prec) as dst, _loaded(_with_a(pr, A1), prec) as twin:
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True).load() as src, T.Solver.open(pr, prec) as dst, T.Solver.open(with_a(pr, A1), prec).load() as twin:
         assert src.solve(pr.tolerance, 200) in (0, MAX_ITERATIONS)
         assert src.set_blocks("A", diag, A1[diag]) == 0
         assert dst.carry_from(src, "A") == 0
@@ -192,19 +165,19 @@ def test_source_a_of_a_preconditioned_plan_that_keeps_it(prec):
 
 def test_source_a_scaled_and_not_kept_is_refused():
     pr = load_problem("fd_16x16_small")
-    with _loaded(pr, "z", kind=BJ) as src, _loaded(pr, "z") as dst:
+    with T.Solver.open(pr, "z", preconditioner=BJ).load() as src, T.Solver.open(pr, "z").load() as dst:
         assert src.solve(pr.tolerance, 200) == 0
         want = _solve_record(dst, pr)
         before = (dst.get_info(), src.get_info())
         status = T.lib.tfqmrgpuExt_carry(dst.handle, dst.plan, src.plan, b"A", pr.nnzbA, None)
         assert T.decode(status)[::2] == (NO_IMPLEMENTATION, 0)
-        assert (dst.get_info(), src.get_info()) == before and _same_bits(_raw_x(dst), want["X"])
+        assert (dst.get_info(), src.get_info()) == before and same_typed_bits(_raw_x(dst), want["X"])
         _same_record(_solve_record(dst, pr), want)              # dst still holds its A
         # B and X need no A of src
         assert dst.carry_from(src, "B") == 0 and dst.carry_from(src, "X") == 0
-        assert _same_bits(_raw_x(dst), _raw_x(src))
+        assert same_typed_bits(_raw_x(dst), _raw_x(src))
     # A never set whole on src: key character 'A'; a user-defined operator on src: refused before that
-    with _open(pr, "z") as src, _loaded(pr, "z") as dst:
+    with T.Solver.open(pr, "z") as src, T.Solver.open(pr, "z").load() as dst:
         raw = lambda: T.decode(T.lib.tfqmrgpuExt_carry(dst.handle, dst.plan, src.plan, b"A", pr.nnzbA, None))[::2]      # noqa: E731
         assert raw() == (UNDOCUMENTED, ord("A"))
         src.set_operator(lambda *a: 0.0)
@@ -223,12 +196,12 @@ def test_preconditioned_destination_sets_up_again():
         out["Minv"], n_identity = s.get_preconditioner()
         out["info"] = dict(out["info"], n_identity=n_identity)
         return out
-    with _loaded(_with_a(pr, A1), "z") as src, _loaded(pr, "z", kind=BJ) as dst, _loaded(_with_a(pr, A1), "z", kind=BJ) as twin:
+    with T.Solver.open(with_a(pr, A1), "z").load() as src, T.Solver.open(pr, "z", preconditioner=BJ).load() as dst, T.Solver.open(with_a(pr, A1), "z", preconditioner=BJ).load() as twin:
         first = record(dst)
         assert dst.carry_from(src, "A") == 0
         got, want = record(dst), record(twin)
         _same_record(got, want)
-        assert not _same_bits(got["Minv"], first["Minv"])
+        assert not same_typed_bits(got["Minv"], first["Minv"])
 
 
 # ---- 5. the loop end to end, with no host values ----------------------------------------------------------------------------------------------------
@@ -249,23 +222,23 @@ def _chain():
 
 def test_the_loop_end_to_end_without_host_values():
     pr = _chain()
-    with _loaded(pr, "z") as src:
+    with T.Solver.open(pr, "z").load() as src:
         assert src.solve(1e-9, 200) == 0
         pr.X = src.get_matrix()
         grown = src.grow_problem(pr, [0])
         rp, ci, old = src.grow_pattern([0])
         assert grown.nnzbX == 4 and list(old) == [0, 1, 2, -1]
         # the host route of the existing test
-        with _loaded(grown, "z") as host:
+        with T.Solver.open(grown, "z").load() as host:
             host.set_matrix("X", grown.X)
             assert host.solve_from(1e-9, 200) == 0
             want = dict(X=_raw_x(host), info=host.get_info(), bounds=host.bound_history(), residual2=host.residual()["residual2"])
         # the device route: no values cross the bus
-        with _open(grown, "z") as dev:
+        with T.Solver.open(grown, "z") as dev:
             assert dev.adopt(src, old) == 0
             assert dev.solve_from(1e-9, 200) == 0
-            assert _same_bits(_raw_x(dev), want["X"]) and dev.get_info() == want["info"] and _same_bits(dev.bound_history(), want["bounds"])
-            assert _same_bits(dev.residual()["residual2"], want["residual2"])
+            assert same_typed_bits(_raw_x(dev), want["X"]) and dev.get_info() == want["info"] and same_typed_bits(dev.bound_history(), want["bounds"])
+            assert same_typed_bits(dev.residual()["residual2"], want["residual2"])
             assert np.all(dev.truncation_leak()["leak2"] == 0.0)
             assert dev.residual()["worst"] <= 1.01e-9
 
@@ -274,19 +247,19 @@ def test_the_loop_end_to_end_without_host_values():
 @pytest.mark.parametrize("name,prec", [("fd_16x16_small", "z"), ("fd_8x8_3d", "c")])
 def test_nothing_else_moves(name, prec):
     pr = load_problem(name)
-    with _loaded(pr, prec) as src, _loaded(pr, prec) as bystander, _open(pr, prec) as dst:
+    with T.Solver.open(pr, prec).load() as src, T.Solver.open(pr, prec).load() as bystander, T.Solver.open(pr, prec) as dst:
         cold = _solve_record(src, pr)
         rp, ci, old = src.grow_pattern(None)
-        with _open(_with_x(pr, rp, ci), prec) as grown:
+        with T.Solver.open(_with_x(pr, rp, ci), prec) as grown:
             assert grown.adopt(src, old) == 0
             first = _raw_x(grown)
             assert grown.carry_from(src, "X", old) == 0          # two carries: the same bits
-            assert _same_bits(_raw_x(grown), first)
+            assert same_typed_bits(_raw_x(grown), first)
         assert dst.adopt(src) == 0
         # src is as the solve left it: X and the work vectors, and its next cold solve is the one before
-        assert _same_bits(_raw_x(src), cold["X"])
+        assert same_typed_bits(_raw_x(src), cold["X"])
         for w in (4, 5, 6, 7, 8, 9):
-            assert _same_bits(src.get_work_vector(w), cold["v%d" % w]), w
+            assert same_typed_bits(src.get_work_vector(w), cold["v%d" % w]), w
         _same_record(_solve_record(src, pr), cold)
         # a plan that never made or served the call solves the same bits, and so does the one that was carried into
         _same_record(_solve_record(bystander, pr), cold)

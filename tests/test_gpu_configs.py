@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import tfqmrgpu_amd as T
+from helpers import torch_cuda  # noqa: F401  (a fixture)
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -56,14 +57,6 @@ def _check_solution_on_device(torch, oracle, pr, prec, X, info, tol):
         mult(2.5 * Xn + Z, Y3)
         eps = 1e-11 if prec == "z" else 1e-3
         assert (Y3 - (2.5 * Y + Y2)).abs().max().item() <= eps * Y3.abs().max().item()
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "the gpu tests need a GPU; there is no CPU fallback"
-    torch.cuda.set_device(0)
-    return torch
 
 
 def test_config2_P2_full_size(torch_cuda, oracle):

@@ -10,8 +10,8 @@ import pytest
 import drop_cost_ref as DR
 import residual_ref as RR
 import tfqmrgpu_amd as T
-from conftest import load_problem
-from test_plan_layout import unordered_pattern
+from conftest import load_problem, offset1
+from helpers import random_x, unordered_pattern
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -21,30 +21,6 @@ SHAPES = [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8,
 NO_INFO_PASSED, POINTER_INVALID, UNDOCUMENTED, NO_IMPLEMENTATION = 3, 7, 14, 19
 BJ = T.PRECOND_BLOCK_JACOBI
 SENTINEL = -12345.0
-
-
-def _open(pr, prec, kind=None, keep=False, shadow=T.SHADOW_HASH, buffer=True):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    s.set_shadow_mode(shadow)
-    if buffer:
-        s.set_buffer(nbytes=nbytes)
-    return s
-
-
-def _random_x(pr, seed):
-    shape = (pr.nnzbX, pr.LM, pr.LN)
-    return PR.hashed_uniform(seed, shape) - 0.5 + 1j * (PR.hashed_uniform(seed + 1, shape) - 0.5)
-
-
-def _offset1(pr):
-    return T.Problem(pr.rowPtrA + 1, pr.colIndA + 1, pr.A, pr.rowPtrX + 1, pr.colIndX + 1, pr.rowPtrB + 1, pr.colIndB + 1, pr.B, None,
-                     pr.tolerance, 1)
 
 
 def _compare(got, ref, what=""):
@@ -64,7 +40,7 @@ def _compare(got, ref, what=""):
 
 def _graded(pr, prec, X, what=""):
     """set A, B and a caller's X on a fresh plan, do not solve, compare with numpy on the data as the plan stores it"""
-    with _open(pr, prec) as s:
+    with T.Solver.open(pr, prec) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         s.set_matrix("X", X)
@@ -79,7 +55,7 @@ def _graded(pr, prec, X, what=""):
 @pytest.mark.parametrize("LM,LN", SHAPES)
 def test_every_shape_and_precision(LM, LN, prec):
     pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=100 * LM + LN, radius=[None, 1.1, 2.3])
-    got, ref = _graded(pr, prec, _random_x(pr, 7 * LM + LN))
+    got, ref = _graded(pr, prec, random_x(pr, 7 * LM + LN))
     assert np.all(ref["products_per_block"] > 0) and np.all(got["cost2"] > 0) and np.all(got["weight2"] > 0)
 
 
@@ -90,7 +66,7 @@ def test_a_block_without_products_costs_exactly_zero():
     A = PR.hashed_uniform(1, (5, LM, LM)) + 1j * PR.hashed_uniform(2, (5, LM, LM))
     B = PR.hashed_uniform(3, (1, LM, LN)) + 0j
     pr = T.Problem([0, 1, 3, 5], [0, 0, 2, 1, 2], A, [0, 1, 2, 2], [0, 0], [0, 1, 1, 1], [0], B)
-    got, ref = _graded(pr, "z", _random_x(pr, 4))
+    got, ref = _graded(pr, "z", random_x(pr, 4))
     assert ref["products_per_block"].tolist() == [2, 0] and np.all(got["cost2"][1] == 0.0) and np.all(got["weight2"][1] > 0)
 
 
@@ -104,9 +80,9 @@ def test_one_block_per_column_is_the_residual(oracle, LM, LN, prec):
     cols = np.unique(pr.colIndX, return_inverse=True)[1]
     chosen = [int(np.flatnonzero(cols == c)[len(np.flatnonzero(cols == c)) // 2]) for c in range(3)]
     X = np.zeros((pr.nnzbX, LM, LN), dtype=np.complex128)
-    X[chosen] = _random_x(pr, 17)[chosen]
+    X[chosen] = random_x(pr, 17)[chosen]
     B0 = np.zeros_like(pr.B)
-    with _open(pr, prec) as s:
+    with T.Solver.open(pr, prec) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", B0)
         s.set_matrix("X", X)
@@ -126,8 +102,8 @@ def test_one_block_per_column_is_the_residual(oracle, LM, LN, prec):
 @pytest.mark.parametrize("LM,LN,prec", [(4, 5, "z"), (8, 8, "c"), (16, 16, "z"), (16, 32, "m")])
 def test_index_offset(LM, LN, prec):
     pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=LM + LN, radius=[None, 1.1, 2.3])
-    zero, _ = _graded(pr, prec, _random_x(pr, 3))
-    one, _ = _graded(_offset1(pr), prec, _random_x(pr, 3), " 1-based")
+    zero, _ = _graded(pr, prec, random_x(pr, 3))
+    one, _ = _graded(offset1(pr), prec, random_x(pr, 3), " 1-based")
     for key in ("cost2", "weight2"):                                 # the same listing, the same sums, the same bits
         assert np.array_equal(zero[key], one[key]), key
 
@@ -143,7 +119,7 @@ def test_callers_block_order_unordered_pattern():
     pr = T.Problem(pat.rowPtrA, pat.colIndA, A, pat.rowPtrX, pat.colIndX, pat.rowPtrB, pat.colIndB, B)
     rows = np.repeat(np.arange(pr.mb), np.diff(pr.rowPtrX))
     assert np.any((np.diff(pr.colIndX) < 0) & (np.diff(rows) == 0))
-    got, ref = _graded(pr, "z", _random_x(pr, 15), " unordered")
+    got, ref = _graded(pr, "z", random_x(pr, 15), " unordered")
     assert len(set(ref["products_per_block"].tolist())) > 2          # blocks of different product counts: a permuted answer would show
 
 
@@ -154,14 +130,14 @@ def test_callers_block_order_reversed_rows(LM, LN, prec):
     ciX = np.concatenate([pr.colIndX[pr.rowPtrX[r]:pr.rowPtrX[r + 1]][::-1] for r in range(pr.mb)])
     assert not np.array_equal(ciX, pr.colIndX)
     rev = T.Problem(pr.rowPtrA, pr.colIndA, pr.A, pr.rowPtrX, ciX, pr.rowPtrB, pr.colIndB, pr.B)
-    _graded(rev, prec, _random_x(rev, 16), " reversed rows")
+    _graded(rev, prec, random_x(rev, 16), " reversed rows")
 
 
 # ---- 5. many products per block, many blocks per work group ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", ["z", "c"])
 def test_many_products_per_block(prec):
     pr = load_problem("dense_random")                                # A dense: mb products per X block
-    got, ref = _graded(pr, prec, _random_x(pr, 23), " dense")
+    got, ref = _graded(pr, prec, random_x(pr, 23), " dense")
     assert np.all(ref["products_per_block"] == pr.mb) and pr.mb == 5
 
 
@@ -170,7 +146,7 @@ def test_many_blocks_per_work_group():
     work group, eight per wave in the first, and a second work group that is partly filled"""
     pr = PR.stencil_2d(9, 9, 16, 16, ncols=3, seed=88, radius=2.3)
     assert 32 + 4 < pr.nnzbX < 64 and pr.nnzbX % 4 != 0
-    _graded(pr, "z", _random_x(pr, 89), " many blocks per work group")
+    _graded(pr, "z", random_x(pr, 89), " many blocks per work group")
 
 
 # ---- 6. preconditioned plans ---------------------------------------------------------------------------------------------------------------
@@ -178,7 +154,7 @@ def test_many_blocks_per_work_group():
 def test_preconditioned_plan(prec, LM):
     pr = PR.stencil_2d(4, 4, LM, LM, 2, seed=LM, radius=[1.5, 2.1])
     # without the kept copy the caller's A is gone after the first solve: status 19 for cost2, nothing written; the weights need no A
-    with _open(pr, prec, kind=BJ) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 200) == 0
@@ -195,7 +171,7 @@ def test_preconditioned_plan(prec, LM):
         ref = DR.drop_cost(pr, pr.A, X)
         assert np.all(np.abs(got["weight2"] - ref["weight2"]) <= ref["bound_w"])
     # with it: the caller's A and the back-transformed X, not the Y of the scaled system
-    with _open(pr, prec, kind=BJ, keep=True) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 200) == 0
@@ -219,7 +195,7 @@ def test_non_destructive_and_deterministic(prec, LM, LN):
     tol = 1e-9 if prec == "z" else 1e-4
 
     def run(with_call):
-        with _open(pr, prec) as s:
+        with T.Solver.open(pr, prec) as s:
             s.set_matrix("A", pr.A)
             s.set_matrix("B", pr.B)
             assert s.solve(tol, 200) == 0
@@ -289,7 +265,7 @@ def test_chain_end_to_end():
             A[q] += 2.0 * np.eye(LM)
     B = PR.hashed_uniform(3, (1, LM, LN)) + 1j * PR.hashed_uniform(4, (1, LM, LN))
     pr = T.Problem(rpA, ciA, A, np.arange(mb + 1), np.zeros(mb, np.int32), [0] + [1] * mb, [0], B)
-    with _open(pr, "z") as s:
+    with T.Solver.open(pr, "z") as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(threshold, 200) == 0
@@ -305,7 +281,7 @@ def test_chain_end_to_end():
         pr.X = X
         small = s.shrink_problem(pr, drop)
         assert small.nnzbX == len(keep) and np.array_equal(small.X, X[keep])
-    with _open(small, "z") as s:
+    with T.Solver.open(small, "z") as s:
         s.set_matrix("A", small.A)
         s.set_matrix("B", small.B)
         assert s.solve(threshold, 200) == 0                          # the shrunk plan converges
@@ -335,12 +311,12 @@ def test_statuses_change_nothing():
             assert count.value == (s.plan_view()["nPairs"] if st == 0 else 777)
         return st
 
-    with _open(pr, "z", buffer=False) as s:                         # no buffer
+    with T.Solver.open(pr, "z", buffer=False) as s:                         # no buffer
         assert call(s, cost=False, weight=False, with_count=False) == NO_INFO_PASSED       # ... comes behind the look at the outputs
         assert call(s, cost=False, weight=False) == 0               # the count needs neither a buffer nor A
         assert T.decode(call(s))[::2] == (POINTER_INVALID, 0)
         assert T.decode(call(s, cost=False))[::2] == (POINTER_INVALID, 0)
-    with _open(pr, "z") as s:                                       # no A
+    with T.Solver.open(pr, "z") as s:                                       # no A
         s.set_matrix("B", pr.B)
         x_before = s.get_work_vector(1)
         s.set_operator(lambda *a: 0.0)                              # a user-defined operator comes before the missing A
@@ -358,7 +334,7 @@ def test_statuses_change_nothing():
         assert T.decode(call(s))[::2] == (NO_IMPLEMENTATION, 0)
         s.set_operator(None)
         assert np.array_equal(s.get_work_vector(1), x_before, equal_nan=True)
-        X = _random_x(pr, 5)
+        X = random_x(pr, 5)
         s.set_matrix("X", X)
         got = s.drop_cost()                                         # ... and the call works again
         _compare(got, DR.drop_cost(pr, pr.A, X), "after the refusals")

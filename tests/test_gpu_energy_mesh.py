@@ -10,6 +10,7 @@ import pytest
 import mesh_ref as MR
 import tfqmrgpu_amd as T
 from conftest import load_problem
+from helpers import bits, same_typed_bits
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -21,44 +22,6 @@ FIXTURES = ["fd_4x4_2d", "fd_16x16_small", "fd_8x8_3d", "stencil_8x32", "dense_r
 PRECISIONS = ["z", "c", "m"]
 SIGMA = 1e-3 * (1 + 0.5j)
 W1, W2 = 0.75 - 0.5j, -0.3 + 1.25j
-
-
-def _open(pr, prec, kind=None, keep=False, buffer=True, pad=False, depth=0, keep_sum=False):
-    s = T.Solver()
-    s.create_plan(pr)
-    if pad:
-        s.allow_padding(True)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    if depth:
-        s.keep_starts(depth)
-    if keep_sum:
-        s.keep_sum(True)
-    if buffer == "torch":                                                # a buffer of the test's own: it can be looked at, byte for byte
-        import torch
-        s.torch_buffer = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-        s.set_buffer(device_ptr=s.torch_buffer.data_ptr())
-    elif buffer:
-        s.set_buffer(nbytes=nbytes)
-    return s
-
-
-def _loaded(pr, prec, **kw):
-    s = _open(pr, prec, **kw)
-    s.set_matrix("A", pr.A)
-    s.set_matrix("B", pr.B)
-    return s
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 def _stored(A, prec):
@@ -87,9 +50,9 @@ def _solved(s, iterations=3):
 
 def _same_operator(p, q, X0):
     """the same product, and the same three iterations: the second reads the float A of an 'm' plan as well"""
-    assert _same_bits(_product(p, X0), _product(q, X0))
+    assert same_typed_bits(_product(p, X0), _product(q, X0))
     (xp, hp), (xq, hq) = _solved(p), _solved(q)
-    assert _same_bits(xp, xq) and _same_bits(hp, hq)
+    assert same_typed_bits(xp, xq) and same_typed_bits(hp, hq)
 
 
 def _padded_problem():
@@ -105,11 +68,11 @@ def test_shift_is_set_blocks_of_the_diagonal(name, prec):
     pr = load_problem(name)
     diag, X0 = MR.diagonal_blocks(pr), _x0(pr)
     assert len(diag) == pr.mb
-    with _loaded(pr, prec) as p, _loaded(pr, prec) as q, _loaded(pr, prec) as u:
+    with T.Solver.open(pr, prec).load() as p, T.Solver.open(pr, prec).load() as q, T.Solver.open(pr, prec).load() as u:
         assert p.shift_diagonal(SIGMA) == 0
         q.set_blocks("A", diag, MR.shifted_diagonal_blocks(pr.A, diag, prec, SIGMA))
         _same_operator(p, q, X0)
-        assert not _same_bits(_product(p, X0), _product(u, X0))          # and it is another operator than before
+        assert not same_typed_bits(_product(p, X0), _product(u, X0))          # and it is another operator than before
         # shifts do not accumulate
         for sigma in (SIGMA, 2 * SIGMA, 0.0):
             assert p.shift_diagonal(sigma) == 0
@@ -126,30 +89,30 @@ def test_shift_on_a_preconditioned_plan_that_keeps_a(name, prec):
     set-up redoes them through the partial set-up: M^-1 and the solve have the bits of the twin that got set_blocks('A')"""
     pr = load_problem(name)
     diag = MR.diagonal_blocks(pr)
-    with _loaded(pr, prec, kind=BJ, keep=True) as p, _loaded(pr, prec, kind=BJ, keep=True) as q:
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True).load() as p, T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True).load() as q:
         (xp, _), (xq, _) = _solved(p), _solved(q)
-        assert _same_bits(xp, xq)
+        assert same_typed_bits(xp, xq)
         assert p.shift_diagonal(SIGMA) == 0
         q.set_blocks("A", diag, MR.shifted_diagonal_blocks(pr.A, diag, prec, SIGMA))
         (mp, ip), (mq, iq) = p.get_preconditioner(), q.get_preconditioner()
-        assert ip == iq == 0 and _same_bits(mp, mq)
+        assert ip == iq == 0 and same_typed_bits(mp, mq)
         (xp2, hp), (xq2, hq) = _solved(p), _solved(q)
-        assert _same_bits(xp2, xq2) and _same_bits(hp, hq) and not _same_bits(xp2, xp)
+        assert same_typed_bits(xp2, xq2) and same_typed_bits(hp, hq) and not same_typed_bits(xp2, xp)
         # and a second shift builds on the caller's diagonal, not on the shifted one
         assert p.shift_diagonal(2 * SIGMA) == 0
         q.set_blocks("A", diag, MR.shifted_diagonal_blocks(pr.A, diag, prec, 2 * SIGMA))
-        assert _same_bits(p.get_preconditioner()[0], q.get_preconditioner()[0])
-        assert _same_bits(_solved(p)[0], _solved(q)[0])
+        assert same_typed_bits(p.get_preconditioner()[0], q.get_preconditioner()[0])
+        assert same_typed_bits(_solved(p)[0], _solved(q)[0])
 
 
 def test_shift_on_a_scaled_plan_without_a_copy_is_refused():
     pr = load_problem("fd_16x16_small")
-    with _loaded(pr, "z", kind=BJ) as s:
+    with T.Solver.open(pr, "z", preconditioner=BJ).load() as s:
         x, h = _solved(s)
         m = s.get_preconditioner()[0]
         assert T.decode(T.lib.tfqmrgpuExt_shiftDiagonal(s.handle, s.plan, SIGMA.real, SIGMA.imag))[::2] == (NO_IMPLEMENTATION, 0)
         x2, h2 = _solved(s)                                              # nothing has been written: the same operator, the same M^-1
-        assert _same_bits(x, x2) and _same_bits(h, h2) and _same_bits(m, s.get_preconditioner()[0])
+        assert same_typed_bits(x, x2) and same_typed_bits(h, h2) and same_typed_bits(m, s.get_preconditioner()[0])
 
 
 @pytest.mark.parametrize("prec", PRECISIONS)
@@ -163,7 +126,7 @@ def test_shift_builds_on_the_base_that_the_last_write_left(prec):
     patched[diag[1]] = patch[0]
     other = _stored(pr.A, prec)
     other[diag] *= 1.25
-    with _loaded(pr, prec) as p, _loaded(pr, prec) as q, _loaded(pr, prec) as src:
+    with T.Solver.open(pr, prec).load() as p, T.Solver.open(pr, prec).load() as q, T.Solver.open(pr, prec).load() as src:
         assert p.shift_diagonal(SIGMA) == 0                              # captures the diagonal of pr.A
         p.set_blocks("A", diag[1:2], patch)
         assert p.shift_diagonal(2 * SIGMA) == 0
@@ -196,7 +159,7 @@ def test_shifts_do_not_accumulate_through_patches_and_refused_writes(prec):
     patch += 8 * np.eye(pr.LM)
     patched = _stored(pr.A, prec)
     patched[diag[2]] = patch[0]
-    with _loaded(pr, prec) as p, _loaded(pr, prec) as q:
+    with T.Solver.open(pr, prec).load() as p, T.Solver.open(pr, prec).load() as q:
         assert p.shift_diagonal(SIGMA) == 0
         for _ in range(pr.mb + 1):
             p.set_blocks("A", diag[2:3], patch)
@@ -204,7 +167,7 @@ def test_shifts_do_not_accumulate_through_patches_and_refused_writes(prec):
         q.set_blocks("A", diag[2:3], patch)
         q.set_blocks("A", diag, MR.shifted_diagonal_blocks(patched, diag, prec, 3 * SIGMA))
         _same_operator(p, q, X0)
-    with _loaded(pr, prec) as p, _loaded(pr, prec) as q:
+    with T.Solver.open(pr, prec).load() as p, T.Solver.open(pr, prec).load() as q:
         assert p.shift_diagonal(SIGMA) == 0
         raw = np.zeros((pr.nnzbA, pr.LM, pr.LM, 2), np.float64)
         wrong = b"z" if prec == "c" else b"c"
@@ -223,25 +186,25 @@ def test_shift_on_a_padded_plan(prec):
     pr = _padded_problem()
     diag, X0 = MR.diagonal_blocks(pr), _x0(pr)
     assert len(diag) == pr.mb
-    with _loaded(pr, prec, pad=True) as p, _loaded(pr, prec, pad=True) as q:
+    with T.Solver.open(pr, prec, allow_padding=True).load() as p, T.Solver.open(pr, prec, allow_padding=True).load() as q:
         assert p.padded_shape() == (9, 9, 16, 16)
         assert p.shift_diagonal(SIGMA) == 0
         q.set_blocks("A", diag, MR.shifted_diagonal_blocks(pr.A, diag, prec, SIGMA))
         _same_operator(p, q, X0)
-    with _loaded(pr, prec, pad=True, kind=BJ, keep=True) as p, _loaded(pr, prec, pad=True, kind=BJ, keep=True) as q:
+    with T.Solver.open(pr, prec, allow_padding=True, preconditioner=BJ, keep_operator=True).load() as p, T.Solver.open(pr, prec, allow_padding=True, preconditioner=BJ, keep_operator=True).load() as q:
         _solved(p), _solved(q)
         assert p.shift_diagonal(SIGMA) == 0
         q.set_blocks("A", diag, MR.shifted_diagonal_blocks(pr.A, diag, prec, SIGMA))
         (mp, ip), (mq, _) = p.get_preconditioner(), q.get_preconditioner()
-        assert ip == 0 and _same_bits(mp, mq) and mp.shape == (pr.mb, 16, 16)
+        assert ip == 0 and same_typed_bits(mp, mq) and mp.shape == (pr.mb, 16, 16)
         assert np.all(mp[:, 9:, 9:] == np.eye(7)) and np.all(mp[:, 9:, :9] == 0) and np.all(mp[:, :9, 9:] == 0)
-        assert _same_bits(_solved(p)[0], _solved(q)[0])
+        assert same_typed_bits(_solved(p)[0], _solved(q)[0])
 
 
 def test_shift_statuses_that_need_a_device():
     raw = lambda s: T.decode(T.lib.tfqmrgpuExt_shiftDiagonal(s.handle, s.plan, SIGMA.real, SIGMA.imag))[::2]      # noqa: E731
     pr = load_problem("fd_4x4_2d")
-    with _open(pr, "z") as s:                                            # A has never been set whole on this buffer
+    with T.Solver.open(pr, "z") as s:                                            # A has never been set whole on this buffer
         s.set_matrix("B", pr.B)
         assert raw(s) == (UNDOCUMENTED, ord("A"))
         s.set_blocks("A", [0], pr.A[:1])                                 # a patch makes no whole A
@@ -250,9 +213,9 @@ def test_shift_statuses_that_need_a_device():
     nd = MR.no_diagonal_problem()
     X0 = _x0(nd)
     for prec in PRECISIONS:
-        with _loaded(nd, prec) as s, _loaded(nd, prec) as u:
+        with T.Solver.open(nd, prec).load() as s, T.Solver.open(nd, prec).load() as u:
             assert raw(s) == (UNDOCUMENTED, ord("D"))
-            assert _same_bits(_product(s, X0), _product(u, X0))
+            assert same_typed_bits(_product(s, X0), _product(u, X0))
             s.set_operator(lambda *a: 0.0)                               # the operator is looked at first
             assert raw(s) == (NO_IMPLEMENTATION, 0)
 
@@ -263,7 +226,10 @@ def test_shift_statuses_that_need_a_device():
 def test_sum_is_its_restatement_in_real_arithmetic(name, prec):
     pr = load_problem(name)
     import torch
-    with _loaded(pr, prec, keep_sum=True, buffer="torch") as s:
+    with T.Solver.open(pr, prec, keep_sum=True, buffer=False) as s:
+        s.torch_buffer = torch.zeros(s.buffer_bytes, dtype=torch.uint8, device="cuda")      # a buffer of the test's own: it can be looked at, byte for byte
+        s.set_buffer(device_ptr=s.torch_buffer.data_ptr())
+        s.load()
         S, n = s.get_sum()
         assert n == 0 and S.shape == (pr.nnzbB, pr.LM, pr.LN) and not S.any()       # no term yet: zeros, and nothing allocated
         terms = []
@@ -279,39 +245,39 @@ def test_sum_is_its_restatement_in_real_arithmetic(name, prec):
             torch.cuda.synchronize()
             assert torch.equal(snapshot, s.torch_buffer)                 # the buffer is untouched
             for v in before:
-                assert _same_bits(before[v], s.get_work_vector(v)), v
-            assert _same_bits(h, s.bound_history()) and s.get_info() == info
+                assert same_typed_bits(before[v], s.get_work_vector(v)), v
+            assert same_typed_bits(h, s.bound_history()) and s.get_info() == info
             terms.append((w, s.get_blocks()))                            # (get_blocks stages through the work vectors: behind the check)
         S, n = s.get_sum()
         want = MR.weighted_sum(terms, S.shape)
-        assert n == 2 and S.dtype == np.complex128 and _same_bits(S, want)
+        assert n == 2 and S.dtype == np.complex128 and same_typed_bits(S, want)
         assert np.abs(S).max() > 0
         assert s.clear_sum() == 0
         S, n = s.get_sum()
         assert n == 0 and not S.any()
         assert s.add_to_sum(W2) == 0                                     # and it sums again from zero
-        assert _same_bits(s.get_sum()[0], MR.weighted_sum(terms[1:], S.shape))
+        assert same_typed_bits(s.get_sum()[0], MR.weighted_sum(terms[1:], S.shape))
         assert s.keep_sum(True) == 0 and s.get_sum()[1] == 0 and not s.get_sum()[0].any()
 
 
 @pytest.mark.parametrize("prec", PRECISIONS)
 def test_sum_on_a_padded_and_on_a_preconditioned_plan(prec):
     pr = _padded_problem()
-    with _loaded(pr, prec, pad=True, keep_sum=True) as s:                # the caller's compact shape
+    with T.Solver.open(pr, prec, allow_padding=True, keep_sum=True).load() as s:                # the caller's compact shape
         terms = []
         for w, its in ((W1, 2), (W2, 3)):
             assert s.solve(1e-30, its) == MAX_ITERATIONS
             s.add_to_sum(w)
             terms.append((w, s.get_blocks()))
         S, n = s.get_sum()
-        assert n == 2 and S.shape == (pr.nnzbB, 9, 9) and _same_bits(S, MR.weighted_sum(terms, S.shape)) and np.abs(S).max() > 0
+        assert n == 2 and S.shape == (pr.nnzbB, 9, 9) and same_typed_bits(S, MR.weighted_sum(terms, S.shape)) and np.abs(S).max() > 0
     pr = load_problem("fd_16x16_small")
-    with _loaded(pr, prec, kind=BJ, keep_sum=True) as s:                 # the back-transformed X, as get_blocks returns it
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_sum=True).load() as s:                 # the back-transformed X, as get_blocks returns it
         assert s.solve(1e-30, 3) == MAX_ITERATIONS
         s.add_to_sum(W1)
         S, n = s.get_sum()
-        assert n == 1 and _same_bits(S, MR.weighted_sum([(W1, s.get_blocks())], S.shape))
-    with _loaded(pr, prec) as s:                                         # keepSum is off: refused, as pushStart without a depth
+        assert n == 1 and same_typed_bits(S, MR.weighted_sum([(W1, s.get_blocks())], S.shape))
+    with T.Solver.open(pr, prec).load() as s:                                         # keepSum is off: refused, as pushStart without a depth
         assert T.decode(T.lib.tfqmrgpuExt_addToSum(s.handle, s.plan, 1.0, 0.0))[::2] == (UNDOCUMENTED, ord("X"))
 
 
@@ -349,18 +315,18 @@ def _loop(q, sigmas, weights, threshold, max_iterations, from_x):
 @pytest.mark.parametrize("name", ["fd_16x16_small", "fd_4x4_2d"])
 def test_mesh_is_the_loop_of_the_public_calls(name, prec, depth, from_x):
     pr = load_problem(name)
-    with _loaded(pr, prec, depth=depth, keep_sum=True) as p, _loaded(pr, prec, depth=depth, keep_sum=True) as q:
+    with T.Solver.open(pr, prec, keep_starts=depth or None, keep_sum=True).load() as p, T.Solver.open(pr, prec, keep_starts=depth or None, keep_sum=True).load() as q:
         if from_x:                                                       # an X to start from: the same on both
             _solved(p, 2), _solved(q, 2)
         out = p.solve_mesh(SIGMAS, WEIGHTS, 1e-30, 3, from_x=from_x)
         its, res, sts = _loop(q, SIGMAS, WEIGHTS, 1e-30, 3, from_x)
         assert out["status"] == MAX_ITERATIONS and out["n_done"] == NE and np.all(out["statuses"] == MAX_ITERATIONS)
-        assert np.array_equal(out["statuses"], sts) and np.array_equal(out["iterations"], its) and _same_bits(out["residual"], res)
-        assert _same_bits(p.get_matrix(), q.get_matrix())
+        assert np.array_equal(out["statuses"], sts) and np.array_equal(out["iterations"], its) and same_typed_bits(out["residual"], res)
+        assert same_typed_bits(p.get_matrix(), q.get_matrix())
         (sp, np_), (sq, nq) = p.get_sum(), q.get_sum()
-        assert np_ == nq == NE and _same_bits(sp, sq) and np.abs(sp).max() > 0
+        assert np_ == nq == NE and same_typed_bits(sp, sq) and np.abs(sp).max() > 0
         assert p.start_count() == q.start_count() == min(depth, NE)
-        assert _same_bits(p.bound_history(), q.bound_history())
+        assert same_typed_bits(p.bound_history(), q.bound_history())
 
 
 def test_mesh_converges_on_a_preconditioned_plan():
@@ -368,16 +334,16 @@ def test_mesh_converges_on_a_preconditioned_plan():
     last system to `threshold` -- residual() reads the caller's A, the kept copy"""
     pr = load_problem("fd_16x16_small")
     thr = pr.tolerance
-    with _loaded(pr, "z", kind=BJ, keep=True, depth=2, keep_sum=True) as p, _loaded(pr, "z", kind=BJ, keep=True, depth=2, keep_sum=True) as q:
+    with T.Solver.open(pr, "z", preconditioner=BJ, keep_operator=True, keep_starts=2, keep_sum=True).load() as p, T.Solver.open(pr, "z", preconditioner=BJ, keep_operator=True, keep_starts=2, keep_sum=True).load() as q:
         out = p.solve_mesh(SIGMAS, WEIGHTS, thr, 500)
         its, res, sts = _loop(q, SIGMAS, WEIGHTS, thr, 500, 0)
         print("mesh, fd_16x16_small z block-Jacobi depth 2: iterations %s, residual %s" % (list(out["iterations"]), list(out["residual"])))
         assert out["status"] == 0 and out["n_done"] == NE and np.all(out["statuses"] == 0)
-        assert np.array_equal(out["iterations"], its) and _same_bits(out["residual"], res) and np.all(out["residual"] <= thr)
+        assert np.array_equal(out["iterations"], its) and same_typed_bits(out["residual"], res) and np.all(out["residual"] <= thr)
         worst = p.residual()["worst"]
         print("mesh: residual()['worst'] of the last energy %.3e, threshold %.1e" % (worst, thr))
         assert worst <= thr
-        assert _same_bits(p.get_matrix(), q.get_matrix()) and _same_bits(p.get_sum()[0], q.get_sum()[0])
+        assert same_typed_bits(p.get_matrix(), q.get_matrix()) and same_typed_bits(p.get_sum()[0], q.get_sum()[0])
 
 
 def _raw_mesh(p, threshold, max_iterations):
@@ -396,14 +362,14 @@ def test_mesh_stops_at_the_first_energy_that_fails():
     energies is written, and steps 4 and 5 of that energy do not run"""
     pr = load_problem("fd_16x16_small")
     pr.A[:] = 0
-    with _loaded(pr, "z", depth=2, keep_sum=True) as p, _loaded(pr, "z") as q:
+    with T.Solver.open(pr, "z", keep_starts=2, keep_sum=True).load() as p, T.Solver.open(pr, "z").load() as q:
         want = T.lib.tfqmrgpu_bsrsv_solve(q.handle, q.plan, 1e-9, 50)
         assert want == BREAKDOWN
         got, done, its, res, sts = _raw_mesh(p, 1e-9, 50)
         assert got == want and done == 1 and sts[0] == want and np.all(sts[1:] == -7) and np.all(its[1:] == -7) and np.all(res[1:] == -7.0)
         info = q.get_info()
-        assert its[0] == info["iterations"] and _same_bits(res[:1], np.array([info["residual"]]))
-        assert _same_bits(p.get_matrix(), q.get_matrix())
+        assert its[0] == info["iterations"] and same_typed_bits(res[:1], np.array([info["residual"]]))
+        assert same_typed_bits(p.get_matrix(), q.get_matrix())
         assert p.start_count() == 0 and p.get_sum()[1] == 0
 
 
@@ -415,13 +381,13 @@ def test_mesh_with_an_entry_of_b_that_is_not_finite(prec):
     that solve gives for that B on a twin plan, and everything behind it has the twin's bits, the NaNs included"""
     pr = load_problem("fd_16x16_small")
     pr.B[0, 1, 2] = np.nan
-    with _loaded(pr, prec, keep_sum=True) as p, _loaded(pr, prec, keep_sum=True) as q, _loaded(pr, prec) as cold:
+    with T.Solver.open(pr, prec, keep_sum=True).load() as p, T.Solver.open(pr, prec, keep_sum=True).load() as q, T.Solver.open(pr, prec).load() as cold:
         want = T.lib.tfqmrgpu_bsrsv_solve(cold.handle, cold.plan, 1e-9, 50)
         got, done, its, res, sts = _raw_mesh(p, 1e-9, 50)
         its_q, res_q, sts_q = _loop(q, SIGMAS, WEIGHTS, 1e-9, 50, 0)
         print("NaN in B, %s: solve returns %d; the mesh returns %d after %d energies, statuses %s" % (prec, want, got, done, list(sts[:done])))
         assert sts[0] == want and its[0] == cold.get_info()["iterations"]
-        assert done == len(sts_q) and np.array_equal(sts[:done], sts_q) and np.array_equal(its[:done], its_q) and _same_bits(res[:done], res_q)
+        assert done == len(sts_q) and np.array_equal(sts[:done], sts_q) and np.array_equal(its[:done], its_q) and same_typed_bits(res[:done], res_q)
         if want not in (0, MAX_ITERATIONS):
-            assert got == want and done == 1 and _same_bits(p.get_matrix(), cold.get_matrix())
-        assert _same_bits(p.get_matrix(), q.get_matrix()) and _same_bits(p.get_sum()[0], q.get_sum()[0]) and p.get_sum()[1] == q.get_sum()[1]
+            assert got == want and done == 1 and same_typed_bits(p.get_matrix(), cold.get_matrix())
+        assert same_typed_bits(p.get_matrix(), q.get_matrix()) and same_typed_bits(p.get_sum()[0], q.get_sum()[0]) and p.get_sum()[1] == q.get_sum()[1]

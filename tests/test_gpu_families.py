@@ -19,13 +19,11 @@ import pytest
 
 from tfqmrgpu_amd import problems as PR
 from conftest import load_problem
+from helpers import C_BOUND, Z_BOUND
 from plan_paths import FOLD_MAX, gpu_state, plan_paths, state_deviation, true_residual
 import tfqmrgpu_amd as T
 
 pytestmark = pytest.mark.gpu
-
-Z_BOUND = {1: 7e-14, 2: 2e-10}     # tests/test_gpu_hash_mode.py: Z_STATE
-C_BOUND = {1: 1e-4}
 
 st = PR.stencil_2d
 # (id, problem, precision, family, path: "fold" | "unfold" | "segmented", three-product multiply)

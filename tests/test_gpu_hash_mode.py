@@ -12,24 +12,11 @@ import pytest
 
 import tfqmrgpu_amd as T
 from conftest import ROOT, load_problem, offset1
+from solve_helpers import HASH_CASES as CASES
+from solve_helpers import STATE_CASES, STATE_ITERATIONS
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
-
-CASES = {
-    "fd_16x16_2d": lambda: load_problem("fd_16x16_2d"),
-    "fd_16x16_small": lambda: load_problem("fd_16x16_small"),
-    "fd_8x8_3d": lambda: load_problem("fd_8x8_3d"),
-    "fd_4x4_2d": lambda: load_problem("fd_4x4_2d"),
-    "dense_random": lambda: load_problem("dense_random"),
-    "stencil_8x8": lambda: load_problem("stencil_8x8"),
-    "stencil_8x32": lambda: load_problem("stencil_8x32"),
-    "st16x16": lambda: PR.stencil_2d(12, 12, 16, 16, 4, seed=7),          # the bench kernels' shape, 4 block columns
-    "st16x16_ragged": lambda: PR.stencil_2d(9, 7, 16, 16, 3, seed=9, radius=3.3),
-    "st16x16_onecol": lambda: PR.stencil_2d(12, 12, 16, 16, 1, seed=7),   # one block column: A is used once and streamed past the caches (k_spmm_ilv16 / ilv16f <..., ANT>)
-    "st32x32": lambda: PR.stencil_2d(6, 6, 32, 32, 2, seed=3),
-}
-
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_device_shadow_vector_is_the_documented_hash(name):
@@ -273,14 +260,7 @@ def test_native_16x16_multiply_through_the_lds_patch_changes_no_bit(tmp_path):
 # (tests/parity_report.py -> profiles/r02_parity_report.txt, both hash definitions): after one iteration every vector agrees to
 # 14 digits (5 in float); later the recurrences amplify the rounding differences while the vectors themselves shrink with the residual
 # (st32x32 converges by two digits per iteration: in float its vectors are rounding noise at k = 5, not compared).
-Z_STATE = {1: 7e-14, 2: 2e-10, 5: 1e-9}       # observed 1.6e-14 (st16x16_ragged) / 3.6e-11 (stencil_8x32) / 2.4e-10 (st32x32, stencil_8x32)
-STATE_CASES = [("fd_16x16_2d", "z", Z_STATE), ("st16x16_ragged", "z", Z_STATE), ("stencil_8x8", "z", Z_STATE), ("stencil_8x32", "z", Z_STATE),
-               ("st32x32", "z", Z_STATE), ("fd_4x4_2d", "z", Z_STATE),
-               # float: a dot product with the shadow vector that cancels amplifies the 1e-7 differences of v4 / v5 into alfa, beta
-               # and from there into x (seen at k = 2 with the second hash definition: x 1.1e-3, gone again at k = 5)
-               ("fd_16x16_2d", "c", {1: 1.2e-6, 2: 5e-3, 5: 7e-2}),     # observed 2.7e-7 / 1.1e-3 / 1.7e-2
-               ("st32x32", "c", {1: 6e-5, 2: 1.2e-2})]                 # observed 1.3e-5 / 2.9e-3
-STATE_ITERATIONS = [1, 2, 5]
+# (the table itself: tests/solve_helpers.py, shared with tests/parity_report.py)
 
 
 @pytest.mark.parametrize("name,prec,bounds", STATE_CASES)

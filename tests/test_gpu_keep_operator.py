@@ -7,88 +7,17 @@ import numpy as np
 import pytest
 
 import precond_ref as PC
-import test_gpu_precond as TP
 import tfqmrgpu_amd as T
+from helpers import user_array, with_a
+from solve_helpers import (BJ, MAXIT, TOL, changed, fresh_solve, patch_blocks, present_diagonal, same_record, solve_and_check_residual,
+                           solve_record, system_with_two_unit_rows)
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
 
-BJ = T.PRECOND_BLOCK_JACOBI
-TOL = {"z": 1e-9, "c": 1e-4, "m": 1e-9}
-MAXIT = 200
-
-
 def _system(LM, seed=None):
     """the smallest system with more than one block per block column and per work group: 4 x 4 grid, 16 block rows, 64 blocks of A"""
     return PR.stencil_2d(4, 4, LM, LM, 2, seed=LM if seed is None else seed)
-
-
-def _with(pr, A):
-    return T.Problem(pr.rowPtrA, pr.colIndA, A, pr.rowPtrX, pr.colIndX, pr.rowPtrB, pr.colIndB, pr.B, None, pr.tolerance, pr.index_offset)
-
-
-def _diagonal(pr):
-    d = PC.diagonal_blocks(pr)
-    return d[d >= 0].astype(np.int32)
-
-
-def _changed(pr, A, blocks, seed):
-    """a copy of A with the listed blocks changed by a few per cent of a unit matrix plus noise: the system stays block diagonally dominant"""
-    A1 = A.copy()
-    shape = (len(blocks), pr.LM, pr.LM)
-    A1[blocks] += 0.3 * np.eye(pr.LM) * (1 + 0.5j) + 0.05 * (PR.hashed_uniform(seed, shape) + 1j * PR.hashed_uniform(seed + 1, shape))
-    return A1
-
-
-def _user_array(blocks, layout, trans):
-    """what a caller hands over for complex blocks [n, R, C] in that layout and transposition"""
-    m = {"n": blocks, "t": blocks.transpose(0, 2, 1)}[trans]
-    if layout == T.LAYOUT_RIRIRIRI:
-        return np.ascontiguousarray(m)
-    assert layout == T.LAYOUT_RRRRIIII
-    return np.stack([m.real, m.imag], axis=1).reshape(len(m), -1)
-
-
-def _plan(s, pr, prec, kind=BJ, keep=True):
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    s.set_buffer(nbytes=nbytes)
-
-
-def _solve(s, prec, precond=True):
-    """everything a solve leaves behind, for exact comparison"""
-    st = s.solve(TOL[prec], MAXIT)
-    info = s.get_info()
-    out = dict(status=st, iterations=info["iterations"], residual=info["residual"], bounds=s.bound_history(), X=s.get_matrix())
-    if precond:
-        out["Minv"], out["n_identity"] = s.get_preconditioner()
-    if prec == "m":
-        out["refinement"], out["cycle_iterations"] = s.refinement_history(with_iterations=True)
-    return out
-
-
-def _fresh(pr, A, prec, kind=BJ, trans="n", layout=T.LAYOUT_RIRIRIRI):
-    """the yardstick: a plan that knows nothing of section 9, the whole matrix, one solve"""
-    with T.Solver() as s:
-        _plan(s, pr, prec, kind, keep=False)
-        s.set_matrix("A", _user_array(A, layout, trans), trans, layout)
-        s.set_matrix("B", pr.B)
-        return _solve(s, prec, precond=(kind == BJ))
-
-
-def _same(got, want):
-    assert got.keys() == want.keys()
-    for k in want:
-        assert np.array_equal(got[k], want[k]), k
-    assert len(want["bounds"]) >= 1 and want["iterations"] >= 1
-
-
-def _set_blocks(s, blocks, A, trans="n", layout=T.LAYOUT_RIRIRIRI):
-    assert s.set_blocks("A", blocks, _user_array(A[blocks], layout, trans), trans, layout) == 0
 
 
 # ---- 1. all diagonal blocks: the energy loop -----------------------------------------------------------------------------------------
@@ -104,16 +33,15 @@ def energy_loop():
     def run(prec, LM):
         if (prec, LM) not in cache:
             pr = _system(LM)
-            diag = _diagonal(pr)
+            diag = present_diagonal(pr)
             assert len(diag) == pr.mb
-            A1 = _changed(pr, pr.A, diag, seed=70 + LM)
-            with T.Solver() as s:
-                _plan(s, pr, prec)
+            A1 = changed(pr, pr.A, diag, seed=70 + LM)
+            with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
                 s.set_matrix("A", pr.A)
                 s.set_matrix("B", pr.B)
-                first = _solve(s, prec)
-                _set_blocks(s, diag, A1)                                 # status 19 without the kept copy
-                second = _solve(s, prec)
+                first = solve_record(s, prec)
+                patch_blocks(s, diag, A1)                                 # status 19 without the kept copy
+                second = solve_record(s, prec)
             cache[(prec, LM)] = (pr, A1, first, second)
         return cache[(prec, LM)]
     return run
@@ -122,8 +50,8 @@ def energy_loop():
 @pytest.mark.parametrize("prec,LM", CASES)
 def test_all_diagonal_blocks_patched(energy_loop, prec, LM):
     pr, A1, first, second = energy_loop(prec, LM)
-    _same(first, _fresh(pr, pr.A, prec))                                 # the copy does not change the first solve
-    _same(second, _fresh(pr, A1, prec))
+    same_record(first, fresh_solve(pr, pr.A, prec))                                 # the copy does not change the first solve
+    same_record(second, fresh_solve(pr, A1, prec))
     assert second["status"] == 0 and second["n_identity"] == 0
     assert not np.array_equal(second["Minv"], first["Minv"]) and not np.array_equal(second["X"], first["X"])
 
@@ -135,14 +63,14 @@ def test_patched_solve_by_the_float64_residual(oracle, energy_loop):
     residual that the library reports ('z')"""
     prec, tol = "z", TOL["z"]
     pr, A1, _, second = energy_loop(prec, 16)
-    worst = PC.worst_relative_residual(oracle, _with(pr, A1), second["X"])
+    worst = PC.worst_relative_residual(oracle, with_a(pr, A1), second["X"])
     print("keep_operator residual: %d iterations, threshold %.0e, reported %.6e, recomputed %.6e (%.2e of it apart)" % (
         second["iterations"], tol, second["residual"], worst, abs(worst - second["residual"]) / second["residual"]))
     assert second["status"] == 0
     assert worst <= tol, worst
     assert abs(worst - second["residual"]) <= 1e-4 * second["residual"], (worst, second["residual"])
     # and the helper itself on the patched system: the fresh solve it runs ends at the same residual
-    _, info = TP._solve_and_check_residual(oracle, _with(pr, A1), prec, tol, maxit=MAXIT)
+    _, info = solve_and_check_residual(oracle, with_a(pr, A1), prec, tol, maxit=MAXIT)
     assert info["residual"] == second["residual"] and info["iterations"] == second["iterations"]
 
 
@@ -157,16 +85,15 @@ def test_sparse_patch(LM, trans, layout):
     off = int(np.flatnonzero((cols == 9) & (rows != 9))[0])
     blocks = np.array([diag[13], off, diag[2]], dtype=np.int32)          # not in ascending order
     assert len({int(cols[b]) for b in blocks}) == 3
-    A1 = _changed(pr, pr.A, blocks, seed=31)
-    with T.Solver() as s:
-        _plan(s, pr, prec)
-        s.set_matrix("A", _user_array(pr.A, layout, trans), trans, layout)
+    A1 = changed(pr, pr.A, blocks, seed=31)
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
+        s.set_matrix("A", user_array(pr.A, layout, trans), trans, layout)
         s.set_matrix("B", pr.B)
-        first = _solve(s, prec)
-        _set_blocks(s, blocks, A1, trans, layout)
-        second = _solve(s, prec)
-    want = _fresh(pr, A1, prec, trans=trans, layout=layout)
-    _same(second, want)
+        first = solve_record(s, prec)
+        patch_blocks(s, blocks, A1, trans, layout)
+        second = solve_record(s, prec)
+    want = fresh_solve(pr, A1, prec, trans=trans, layout=layout)
+    same_record(second, want)
     untouched = np.setdiff1d(np.arange(pr.mb), [13, 2])
     assert np.array_equal(second["Minv"][untouched], first["Minv"][untouched])
     assert not np.array_equal(second["Minv"][13], first["Minv"][13]) and not np.array_equal(second["Minv"][2], first["Minv"][2])
@@ -180,21 +107,20 @@ def test_patches_accumulate():
     rows, cols = PC.block_rows(pr.rowPtrA), pr.colIndA
     off = int(np.flatnonzero((cols == 6) & (rows != 6))[0])
     list1, list2, list3 = diag[[1, 4]], np.array([diag[11], off, diag[4]], dtype=np.int32), diag[[4, 15]]   # block diag[4] in all three
-    A1 = _changed(pr, pr.A, list1, seed=41)
-    A2 = _changed(pr, A1, list2, seed=43)
-    A3 = _changed(pr, A2, list3, seed=45)
-    with T.Solver() as s:
-        _plan(s, pr, prec)
+    A1 = changed(pr, pr.A, list1, seed=41)
+    A2 = changed(pr, A1, list2, seed=43)
+    A3 = changed(pr, A2, list3, seed=45)
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        _solve(s, prec)
-        _set_blocks(s, list1, A1)
-        _set_blocks(s, list2, A2)
-        second = _solve(s, prec)
-        _set_blocks(s, list3, A3)
-        third = _solve(s, prec)
-    _same(second, _fresh(pr, A2, prec))
-    _same(third, _fresh(pr, A3, prec))
+        solve_record(s, prec)
+        patch_blocks(s, list1, A1)
+        patch_blocks(s, list2, A2)
+        second = solve_record(s, prec)
+        patch_blocks(s, list3, A3)
+        third = solve_record(s, prec)
+    same_record(second, fresh_solve(pr, A2, prec))
+    same_record(third, fresh_solve(pr, A3, prec))
     assert not np.array_equal(third["X"], second["X"])
 
 
@@ -202,67 +128,63 @@ def test_patches_accumulate():
 def test_singular_rows_follow_the_patches():
     """tests/test_gpu_precond.py: _system_with_two_unit_rows: block row 3 has no diagonal block, that of block row 7 a zero row"""
     prec = "z"
-    pr = TP._system_with_two_unit_rows()
+    pr = system_with_two_unit_rows()
     diag = PC.diagonal_blocks(pr)
     A1 = pr.A.copy()
     A1[diag[7], 1, :] = 0.01
     A1[diag[7], 1, 1] = 2.0                                              # regular again
     A2 = A1.copy()
     A2[diag[12]] = 0                                                     # no pivot at all
-    with T.Solver() as s:
-        _plan(s, pr, prec)
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        first = _solve(s, prec)
-        _set_blocks(s, np.array([diag[7]], dtype=np.int32), A1)
-        second = _solve(s, prec)
-        _set_blocks(s, np.array([diag[12]], dtype=np.int32), A2)
-        third = _solve(s, prec)
+        first = solve_record(s, prec)
+        patch_blocks(s, np.array([diag[7]], dtype=np.int32), A1)
+        second = solve_record(s, prec)
+        patch_blocks(s, np.array([diag[12]], dtype=np.int32), A2)
+        third = solve_record(s, prec)
     assert (first["n_identity"], second["n_identity"], third["n_identity"]) == (2, 1, 2)
     assert np.array_equal(second["Minv"][3], np.eye(8)) and not np.array_equal(second["Minv"][7], np.eye(8))
     assert np.array_equal(third["Minv"][12], np.eye(8))
     for got, A in ((first, pr.A), (second, A1), (third, A2)):
-        _same(got, _fresh(pr, A, prec))
+        same_record(got, fresh_solve(pr, A, prec))
 
 
 # ---- 5. the kind changes without a new matrix -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", ["z", "m"])
 def test_kind_switch_without_a_new_matrix(prec):
     pr = _system(16)
-    with T.Solver() as s:
-        _plan(s, pr, prec)
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        scaled = _solve(s, prec)
+        scaled = solve_record(s, prec)
         s.set_preconditioner(T.PRECOND_NONE)                             # status 14, key 'A', without the kept copy
-        plain = _solve(s, prec, precond=False)
+        plain = solve_record(s, prec, precond=False)
         s.set_preconditioner(BJ)
-        again = _solve(s, prec)
-    _same(plain, _fresh(pr, pr.A, prec, kind=None))
-    _same(again, scaled)
-    _same(scaled, _fresh(pr, pr.A, prec))
+        again = solve_record(s, prec)
+    same_record(plain, fresh_solve(pr, pr.A, prec, kind=None))
+    same_record(again, scaled)
+    same_record(scaled, fresh_solve(pr, pr.A, prec))
 
 
 # ---- 6. off is off -------------------------------------------------------------------------------------------------------------------
 def test_off_is_off():
     prec = "z"
     pr = _system(16)
-    diag = _diagonal(pr)
-    with T.Solver() as s:
-        _plan(s, pr, prec, keep=False)
+    diag = present_diagonal(pr)
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.keep_operator(True)
         s.keep_operator(False)
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        _same(_solve(s, prec), _fresh(pr, pr.A, prec))
+        same_record(solve_record(s, prec), fresh_solve(pr, pr.A, prec))
         st = T.lib.tfqmrgpuExt_setBlocks(s.handle, s.plan, b"A", 1, T._ptr(diag[:1]), T._ptr(np.ascontiguousarray(pr.A[diag[:1]])), b"z", b"n",
                                          T.LAYOUT_RIRIRIRI)
         assert T.decode(st)[0] == 19                                     # TFQMRGPU_NO_IMPLEMENTATION, as ever
-    with T.Solver() as s:                                                # switched off AFTER the copy was made: the copy goes, 19 again
-        _plan(s, pr, prec)
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:        # switched off AFTER the copy was made: the copy goes, 19 again
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        _solve(s, prec)
+        solve_record(s, prec)
         s.keep_operator(False)
         st = T.lib.tfqmrgpuExt_setBlocks(s.handle, s.plan, b"A", 1, T._ptr(diag[:1]), T._ptr(np.ascontiguousarray(pr.A[diag[:1]])), b"z", b"n",
                                          T.LAYOUT_RIRIRIRI)
@@ -277,22 +199,20 @@ def test_on_without_a_patch_changes_nothing(prec):
     B2 = pr.B * (1.5 - 0.5j)
     got = []
     for keep in (False, True):
-        with T.Solver() as s:
-            _plan(s, pr, prec, keep=keep)
+        with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=keep) as s:
             s.set_matrix("A", pr.A)
             s.set_matrix("B", pr.B)
-            a = _solve(s, prec)
+            a = solve_record(s, prec)
             s.set_matrix("B", B2)                                        # same A: nothing is set up again
-            got.append((a, _solve(s, prec)))
-    _same(got[1][0], got[0][0])
-    _same(got[1][1], got[0][1])
+            got.append((a, solve_record(s, prec)))
+    same_record(got[1][0], got[0][0])
+    same_record(got[1][1], got[0][1])
 
 
 # ---- 7. errors -----------------------------------------------------------------------------------------------------------------------
 def test_switching_on_a_scaled_plan_is_refused():
     pr = _system(16)
-    with T.Solver() as s:
-        _plan(s, pr, "z", keep=False)
+    with T.Solver.open(pr, "z", preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, MAXIT) == 0                                  # the A in the buffer is A M^-1 now, and nobody kept A
@@ -301,22 +221,21 @@ def test_switching_on_a_scaled_plan_is_refused():
         s.keep_operator(True)
         assert s.solve(1e-9, MAXIT) == 0
         s.keep_operator(True)                                            # on and kept: nothing to refuse
-        _set_blocks(s, _diagonal(pr)[:2], pr.A)
+        patch_blocks(s, present_diagonal(pr)[:2], pr.A)
 
 
 def test_a_refused_list_changes_nothing():
     prec = "z"
     pr = _system(16)
-    diag = _diagonal(pr)
-    A1 = _changed(pr, pr.A, diag, seed=5)
+    diag = present_diagonal(pr)
+    A1 = changed(pr, pr.A, diag, seed=5)
     twice = np.array([diag[3], diag[8], diag[3]], dtype=np.int32)
-    with T.Solver() as s:
-        _plan(s, pr, prec)
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        first = _solve(s, prec)
+        first = solve_record(s, prec)
         for bad in (twice, np.array([diag[3], pr.nnzbA], dtype=np.int32)):
             with pytest.raises(T.TfqmrError) as e:
                 s.set_blocks("A", bad, A1[np.minimum(bad, pr.nnzbA - 1)])
             assert T.decode(e.value.status)[::2] == (14, ord("A"))
-        _same(_solve(s, prec), first)
+        same_record(solve_record(s, prec), first)

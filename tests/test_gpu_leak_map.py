@@ -9,6 +9,8 @@ import pytest
 import leak_map_ref as MR
 import leak_ref as LR
 import tfqmrgpu_amd as T
+from conftest import offset1
+from helpers import random_x
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -18,30 +20,6 @@ SHAPES = [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8,
 NO_INFO_PASSED, POINTER_INVALID, UNDOCUMENTED, NO_IMPLEMENTATION = 3, 7, 14, 19
 BJ = T.PRECOND_BLOCK_JACOBI
 SENTINEL = -12345.0
-
-
-def _open(pr, prec, kind=None, keep=False, shadow=T.SHADOW_HASH, buffer=True):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    s.set_shadow_mode(shadow)
-    if buffer:
-        s.set_buffer(nbytes=nbytes)
-    return s
-
-
-def _random_x(pr, seed):
-    shape = (pr.nnzbX, pr.LM, pr.LN)
-    return PR.hashed_uniform(seed, shape) - 0.5 + 1j * (PR.hashed_uniform(seed + 1, shape) - 0.5)
-
-
-def _offset1(pr):
-    return T.Problem(pr.rowPtrA + 1, pr.colIndA + 1, pr.A, pr.rowPtrX + 1, pr.colIndX + 1, pr.rowPtrB + 1, pr.colIndB + 1, pr.B, None,
-                     pr.tolerance, 1)
 
 
 def _compare(got, ref, what=""):
@@ -58,7 +36,7 @@ def _compare(got, ref, what=""):
 
 def _graded(pr, prec, X, what=""):
     """set A, B and a caller's X on a fresh plan, do not solve, compare with numpy on the data as the plan stores it"""
-    with _open(pr, prec) as s:
+    with T.Solver.open(pr, prec) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         s.set_matrix("X", X)
@@ -95,7 +73,7 @@ def _sum_rule(pr, prec, X, got, ref, leak, what=""):
 def test_every_shape_and_precision(LM, LN, prec):
     """one full column -- it contributes no position -- and two truncated ones"""
     pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=100 * LM + LN, radius=[None, 1.1, 2.3])
-    X = _random_x(pr, 7 * LM + LN)
+    X = random_x(pr, 7 * LM + LN)
     got, ref, leak = _graded(pr, prec, X)
     assert got["n_leak_blocks"] > 0 and 0 not in got["cols"] and {1, 2} == set(got["cols"].tolist())
     assert np.all(got["pos2"] > 0)
@@ -106,8 +84,8 @@ def test_every_shape_and_precision(LM, LN, prec):
 @pytest.mark.parametrize("LM,LN,prec", [(4, 5, "z"), (8, 8, "c"), (16, 16, "z"), (16, 32, "m")])
 def test_index_offset(LM, LN, prec):
     pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=LM + LN, radius=[None, 1.1, 2.3])
-    zero, _, _ = _graded(pr, prec, _random_x(pr, 3))
-    one, _, _ = _graded(_offset1(pr), prec, _random_x(pr, 3), " 1-based")
+    zero, _, _ = _graded(pr, prec, random_x(pr, 3))
+    one, _, _ = _graded(offset1(pr), prec, random_x(pr, 3), " 1-based")
     for key in ("rows", "cols", "pos2"):                             # the same listing, the same sums, the same bits
         assert np.array_equal(zero[key], one[key]), key
 
@@ -118,10 +96,10 @@ def test_long_shells(prec):
     """40 x 40 block rows of 4 x 4, the 13-point stencil, two block columns cut at 24.5 grid steps: 184 positions with one to four
     products each -- several work units of section 11 per column, several work groups and rounds of the map"""
     pr = PR.stencil_2d(40, 40, 4, 4, ncols=2, seed=40, radius=24.5, points=13)
-    X = _random_x(pr, 41)
+    X = random_x(pr, 41)
     got, ref, leak = _graded(pr, prec, X)
     assert got["n_leak_blocks"] >= 180 and np.all(leak["units"] > 1)
-    with _open(pr, prec, buffer=False) as s:
+    with T.Solver.open(pr, prec, buffer=False) as s:
         view = s.plan_view()
     assert leak["n_leak_pairs"] > got["n_leak_blocks"] and view["nCols"] == 2      # positions of different product counts
     _sum_rule(pr, prec, X, got, ref, leak, "long shells %s" % prec)
@@ -131,7 +109,7 @@ def test_many_positions_per_wave():
     """16 x 16 `z`: a wave takes a whole position, and every fourth position of its work group's run of 32 -- 38 positions: eight per
     wave in the first work group, a second work group whose last two waves have one position and the others two"""
     pr = PR.stencil_2d(9, 9, 16, 16, ncols=3, seed=88, radius=2.3)
-    X = _random_x(pr, 89)
+    X = random_x(pr, 89)
     got, ref, leak = _graded(pr, "z", X)
     assert 32 + 4 < got["n_leak_blocks"] < 64
     _sum_rule(pr, "z", X, got, ref, leak, "many positions per wave")
@@ -142,7 +120,7 @@ def test_many_positions_per_wave():
 def test_preconditioned_plan(prec, LM):
     pr = PR.stencil_2d(4, 4, LM, LM, 2, seed=LM, radius=[1.5, 2.1])
     # without the kept copy the caller's A is gone after the first solve: status 19, nothing written; the positions need no A
-    with _open(pr, prec, kind=BJ) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         before = s.leak_map()                                        # not scaled yet: the buffer's A
@@ -157,7 +135,7 @@ def test_preconditioned_plan(prec, LM):
         again = s.leak_map(values=False)
         assert np.array_equal(again["rows"], before["rows"]) and np.array_equal(again["cols"], before["cols"])
     # with it: the caller's A and the back-transformed X
-    with _open(pr, prec, kind=BJ, keep=True) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 200) == 0
@@ -181,7 +159,7 @@ def test_non_destructive_and_deterministic(prec, LM, LN):
     tol = 1e-9 if prec == "z" else 1e-4
 
     def run(with_call):
-        with _open(pr, prec) as s:
+        with T.Solver.open(pr, prec) as s:
             s.set_matrix("A", pr.A)
             s.set_matrix("B", pr.B)
             assert s.solve(tol, 200) == 0
@@ -226,7 +204,7 @@ def test_chain_end_to_end():
             A[q] += 2.0 * np.eye(LM)
     B = PR.hashed_uniform(3, (1, LM, LN)) + 1j * PR.hashed_uniform(4, (1, LM, LN))
     pr = T.Problem(rpA, ciA, A, [0, 1, 2, 3, 3], [0, 0, 0], [0, 0, 1, 1, 1], [0], B)
-    with _open(pr, "z") as s:
+    with T.Solver.open(pr, "z") as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 200) == 0
@@ -235,7 +213,7 @@ def test_chain_end_to_end():
         _compare(got, MR.leak_map(pr, pr.A, s.get_matrix()), "chain")
         grown = s.grow_problem(pr, [0])
         assert np.array_equal(grown.rowPtrX, [0, 1, 2, 3, 4]) and np.array_equal(grown.colIndX, [0, 0, 0, 0])
-    with _open(grown, "z") as s:
+    with T.Solver.open(grown, "z") as s:
         assert s.leak_counts() == (0, 0)
         s.set_matrix("A", grown.A)
         s.set_matrix("B", grown.B)
@@ -267,11 +245,11 @@ def test_statuses_change_nothing():
             assert nb.value == (n if T.decode(st)[2] == ord("X") else 777)
         return st
 
-    with _open(pr, "z", buffer=False) as s:                         # no buffer
+    with T.Solver.open(pr, "z", buffer=False) as s:                         # no buffer
         assert call(s, null=True) == NO_INFO_PASSED                 # ... comes behind the look at the outputs
         assert T.decode(call(s))[::2] == (POINTER_INVALID, 0)
         call(s, patterns_only=True)                                 # the positions need neither a buffer nor A
-    with _open(pr, "z") as s:                                       # no A
+    with T.Solver.open(pr, "z") as s:                                       # no A
         s.set_matrix("B", pr.B)
         x_before = s.get_work_vector(1)
         s.set_operator(lambda *a: 0.0)                              # a user-defined operator comes before the missing A

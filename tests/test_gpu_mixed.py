@@ -12,37 +12,13 @@ import pytest
 
 import tfqmrgpu_amd as T
 from conftest import load_problem
+from helpers import true_residual
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8, 64),
          (16, 16), (16, 32), (16, 64), (32, 32), (32, 64), (64, 64)]
-
-
-def true_residual(pr, X):
-    """max_rhs |A X - B| / |B| on the pattern of X, dense numpy arithmetic in double (small systems only)"""
-    mb, LM, LN = pr.mb, pr.LM, pr.LN
-    off = pr.index_offset
-    cols = sorted(set((pr.colIndX - off).tolist()))
-    cid = {c: i for i, c in enumerate(cols)}
-    Xd = np.zeros((mb, len(cols), LM, LN), complex)
-    mask = np.zeros((mb, len(cols)), bool)
-    rows = np.repeat(np.arange(mb), np.diff(pr.rowPtrX))
-    for q, (r, c) in enumerate(zip(rows, pr.colIndX - off)):
-        Xd[r, cid[c]] = X[q]; mask[r, cid[c]] = True
-    Bd = np.zeros_like(Xd)
-    rowsB = np.repeat(np.arange(mb), np.diff(pr.rowPtrB))
-    for q, (r, c) in enumerate(zip(rowsB, pr.colIndB - off)):
-        Bd[r, cid[c]] = pr.B[q]
-    Y = np.zeros_like(Xd)
-    rowsA = np.repeat(np.arange(mb), np.diff(pr.rowPtrA))
-    for q, (r, k) in enumerate(zip(rowsA, pr.colIndA - off)):
-        Y[r] += np.einsum("ik,ckj->cij", pr.A[q], Xd[k])
-    R = (Y - Bd) * mask[:, :, None, None]                       # products outside the pattern of X are dropped (SURVEY App. C)
-    r2 = (np.abs(R) ** 2).sum(axis=(0, 2))                      # [cols, LN]
-    b2 = (np.abs(Bd) ** 2).sum(axis=(0, 2))
-    return float(np.sqrt((r2 / b2).max()))
 
 
 @pytest.mark.parametrize("name", ["fd_16x16_2d", "fd_16x16_small", "dense_random", "dense_random_rect", "stencil_8x8", "stencil_8x32", "julia_kat"])

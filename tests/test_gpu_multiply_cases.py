@@ -15,19 +15,12 @@ import pytest
 import multiply_cases as MC
 import tfqmrgpu_amd as T
 from conftest import GOLDEN, ROOT
+from helpers import torch_cuda  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 
 PLAN = os.path.join(GOLDEN, "plan_unordered.14-287-16.gz")
 BENCH = os.path.join(ROOT, "tfqmrgpu_amd", "lib", "bench_tfqmrgpu")
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "the gpu tests need a GPU; there is no CPU fallback"
-    torch.cuda.set_device(0)
-    return torch
 
 
 def _run(torch, s, prec, LM, LN, starts, pairs, dA, dX, nY, fill, order=None):

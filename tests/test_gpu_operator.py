@@ -8,29 +8,11 @@ import pytest
 
 import tfqmrgpu_amd as T
 from conftest import load_problem
+from helpers import torch_cuda  # noqa: F401  (a fixture)
+from solve_helpers import DevArray, builtin_as_operator, native_A  # noqa: F401
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "the gpu tests need a GPU; there is no CPU fallback"
-    torch.cuda.set_device(0)
-    return torch
-
-
-class _DevArray:
-    """wraps a raw device pointer so that torch can see it (no copy)"""
-    def __init__(self, ptr, shape, typestr):
-        self.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2)
-
-
-def _native_A(torch, pr, prec):
-    real = torch.float64 if prec == "z" else torch.float32
-    At = pr.A.transpose(0, 2, 1)      # the multiply expects A blocks transposed, [k][i]
-    return torch.from_numpy(np.ascontiguousarray(np.stack([At.real, At.imag], axis=1))).to(real).cuda()
 
 
 CASES = [("fd_16x16_small", "z"), ("fd_16x16_small", "c"), ("julia_kat", "z"), ("stencil_8x8", "z"), ("stencil_8x32", "c"),
@@ -42,24 +24,6 @@ PROFILE_CASE = "fd_16x16_small"
 
 def _problem(name):
     return PR.stencil_2d(6, 6, 32, 32, 2, seed=3) if name == "st32x32" else load_problem(name)
-
-
-def _builtin_as_operator(torch, s, pr, prec, view, seen):
-    """a callback that computes the same block-sparse product with tfqmrgpuExt_multiply on the caller's block order;
-    seen: gets one record of what the first call was handed"""
-    An = _native_A(torch, pr, prec)
-    dS = torch.from_numpy(view["starts"].view(np.int32)).cuda()
-    dP = torch.from_numpy(view["pairs"].view(np.int32)).cuda()
-    colindx = view["colindx"].copy()
-
-    def multiply(y, x, cols, nnzbX, nCols, lm, ln, precision, stream):
-        if not seen:                       # what the reference hands to action_t::multiply
-            got = torch.as_tensor(_DevArray(cols, (nnzbX,), "<u2"), device="cuda").cpu().numpy()
-            seen.append((np.array_equal(got, colindx), nnzbX, nCols, lm, ln, precision))
-        T._check(T.lib.tfqmrgpuExt_multiply(s.handle, precision.encode(), lm, ln, nnzbX, dS.data_ptr(), dP.data_ptr(),
-                                            An.data_ptr(), x, y), "tfqmrgpuExt_multiply")
-        return view["nPairs"] * 8.0 * lm * lm * ln
-    return multiply
 
 
 @pytest.mark.parametrize("name,prec", CASES)
@@ -77,7 +41,7 @@ def test_operator_that_repeats_the_builtin_multiply(torch_cuda, name, prec):
         s.set_matrix("A", 0 * pr.A)            # the values of the built-in operator are not used
         s.set_matrix("B", pr.B)
         seen = []
-        s.set_operator(_builtin_as_operator(torch, s, pr, prec, view, seen))
+        s.set_operator(builtin_as_operator(torch, s, pr, prec, view, seen))
         st = s.solve(tol, 2000)
         info, X = s.get_info(), s.get_matrix()
         assert seen == [(True, pr.nnzbX, view["nCols"], pr.LM, pr.LN, prec)]
@@ -108,7 +72,7 @@ def test_profile_counts_the_probes_of_an_operator_solve_like_the_builtin_ones(to
         s.set_profiling(1)
         assert s.solve(pr.tolerance, 2000) == 0
         it0, builtin = s.get_info()["iterations"], s.profile()
-        s.set_operator(_builtin_as_operator(torch, s, pr, "z", view, []))
+        s.set_operator(builtin_as_operator(torch, s, pr, "z", view, []))
         assert s.solve(pr.tolerance, 2000) == 0
         it1, through = s.get_info()["iterations"], s.profile()
     print("iterations", it0, it1, "probes", builtin["probe"][0], through["probe"][0])
@@ -139,8 +103,8 @@ def test_matrix_free_operator(torch_cuda):
         s.set_matrix("B", eye.B)
 
         def multiply(y, x, cols, nnzbX, nCols, lm, ln, precision, stream):
-            X = torch.as_tensor(_DevArray(x, (nnzbX, 2, lm, ln), "<f8"), device="cuda")
-            Y = torch.as_tensor(_DevArray(y, (nnzbX, 2, lm, ln), "<f8"), device="cuda")
+            X = torch.as_tensor(DevArray(x, (nnzbX, 2, lm, ln), "<f8"), device="cuda")
+            Y = torch.as_tensor(DevArray(y, (nnzbX, 2, lm, ln), "<f8"), device="cuda")
             dr, di = dX.real[:, :, None], dX.imag[:, :, None]
             Y[:, 0] = dr * X[:, 0] - di * X[:, 1]
             Y[:, 1] = dr * X[:, 1] + di * X[:, 0]

@@ -12,6 +12,7 @@ import pytest
 import pad_ref as PD
 import tfqmrgpu_amd as T
 from conftest import ROOT, torchrun
+from helpers import exact_random_blocks, real_dtype, torch_cuda  # noqa: F401  (torch_cuda: a fixture)
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -28,26 +29,8 @@ NO_IMPLEMENTATION = 19
 BJ = T.PRECOND_BLOCK_JACOBI
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "the gpu tests need a GPU; there is no CPU fallback"
-    torch.cuda.set_device(0)
-    return torch
-
-
 def _problem(lm, ln, radius=None):
     return PR.stencil_2d(4, 3, lm, ln, 3, seed=100 * lm + ln, radius=radius)
-
-
-def _real(data):
-    return np.float32 if data == "c" else np.float64
-
-
-def _random(rng, n, rows, cols, data):
-    """complex blocks that the caller's precision holds exactly"""
-    v = rng.standard_normal((n, rows, cols)) + 1j * rng.standard_normal((n, rows, cols))
-    return v.astype(np.complex64).astype(np.complex128) if data == "c" else v
 
 
 def _user(blocks, layout, trans, data, pad=None, unit=None):
@@ -68,7 +51,7 @@ def _user(blocks, layout, trans, data, pad=None, unit=None):
     if trans in "tc":
         re, im = re.transpose(0, 2, 1), im.transpose(0, 2, 1)
     axis = {T.LAYOUT_RIRIRIRI: -1, T.LAYOUT_RRRRIIII: 1, T.LAYOUT_RRIIRRII: 2}[layout]
-    return np.ascontiguousarray(np.stack([re, im], axis=axis).reshape(len(blocks), -1), dtype=_real(data))
+    return np.ascontiguousarray(np.stack([re, im], axis=axis).reshape(len(blocks), -1), dtype=real_dtype(data))
 
 
 class Pair:
@@ -210,8 +193,8 @@ def test_transfers(torch_cuda, lm, ln, prec, data):
             for layout in LAYOUTS:
                 for tr in TRANS:
                     what = (lm, ln, prec, data, device, hex(layout), tr)
-                    vals = dict(A=_random(rng, pr.nnzbA, lm, lm, data), B=_random(rng, pr.nnzbB, lm, ln, data),
-                                X=_random(rng, pr.nnzbX, lm, ln, data))
+                    vals = dict(A=exact_random_blocks(rng, pr.nnzbA, lm, lm, data), B=exact_random_blocks(rng, pr.nnzbB, lm, ln, data),
+                                X=exact_random_blocks(rng, pr.nnzbX, lm, ln, data))
                     alive = []
                     for var, blocks in vals.items():
                         cols = lm if var == "A" else ln
@@ -276,9 +259,9 @@ def test_listed_blocks(torch_cuda, lm, ln, prec, data, kind):
         _both(pair, lambda s: s.solve(TOL[prec], MAXIT), "after setBlocks('A')")
         # B and X: a scattered list, out of order; device values for X
         ib = rng.permutation(pr.nnzbB)[:2].astype(np.int32)
-        pair.set_blocks("B", ib, _random(rng, len(ib), lm, ln, data))
+        pair.set_blocks("B", ib, exact_random_blocks(rng, len(ib), lm, ln, data))
         ix = rng.permutation(pr.nnzbX)[: pr.nnzbX // 2].astype(np.int32)
-        Xnew = _random(rng, len(ix), lm, ln, data)
+        Xnew = exact_random_blocks(rng, len(ix), lm, ln, data)
         before = pair.same_x()
         for layout, tr in ((T.LAYOUT_RRRRIIII, "t"), (T.LAYOUT_RRIIRRII, "c")):
             dp = torch.from_numpy(_user(Xnew, layout, tr, data)).cuda()

@@ -13,20 +13,13 @@ import pytest
 
 import tfqmrgpu_amd as T
 from conftest import ALL_NAMES, GOLDEN, golden_solves, load_golden, load_problem
+from helpers import torch_cuda, user_array  # noqa: F401  (torch_cuda: a fixture)
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8, 64),
          (16, 16), (16, 32), (16, 64), (32, 32), (32, 64), (64, 64)]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "the gpu tests need a GPU; there is no CPU fallback"
-    torch.cuda.set_device(0)
-    return torch
 
 
 def _tol(prec):
@@ -113,16 +106,6 @@ def test_trans_flags_of_A(trans):
     assert st == 0 and np.abs(X - want).max() < 1e-8 * np.abs(want).max()
 
 
-def _user_array(blocks, layout, trans):
-    """what a caller would hand to setMatrix for complex blocks [n, R, C]"""
-    m = {"n": blocks, "t": blocks.transpose(0, 2, 1), "*": blocks.conj(), "c": blocks.conj().transpose(0, 2, 1)}[trans]
-    if layout == T.LAYOUT_RIRIRIRI:
-        return np.stack([m.real, m.imag], axis=-1).reshape(len(m), -1)
-    if layout == T.LAYOUT_RRRRIIII:
-        return np.stack([m.real, m.imag], axis=1).reshape(len(m), -1)
-    return np.stack([m.real, m.imag], axis=2).reshape(len(m), -1)  # RRIIRRII
-
-
 @pytest.mark.parametrize("prec", ["z", "c"])
 @pytest.mark.parametrize("shape", [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8, 64), (16, 16), (16, 32), (32, 32), (16, 64), (32, 64), (64, 64)])   # all 15 shapes; 16 x 16, 8 x 8 | 9 | 10 | 32 | 64 z / 16 x 16, 8 | 16 | 32 | 64 x 8 | 32 | 64 c: plans with groups of rows interleaved
 def test_set_get_matrix_layouts(prec, shape):
@@ -136,11 +119,11 @@ def test_set_get_matrix_layouts(prec, shape):
         s.set_buffer(nbytes=s.buffer_size(LM, LN, prec))
         for lay_in in (T.LAYOUT_RIRIRIRI, T.LAYOUT_RRRRIIII, T.LAYOUT_RRIIRRII):
             for tr_in in "nt*c":
-                s.set_matrix("X", _user_array(Xv, lay_in, tr_in).astype(real), tr_in, lay_in)
+                s.set_matrix("X", user_array(Xv, lay_in, tr_in).astype(real), tr_in, lay_in)
                 for lay_out in (T.LAYOUT_RIRIRIRI, T.LAYOUT_RRRRIIII, T.LAYOUT_RRIIRRII):
                     for tr_out in "nt*c":
                         got = s.get_matrix(trans=tr_out, layout=lay_out, raw=True)
-                        want = _user_array(Xv, lay_out, tr_out).astype(real)
+                        want = user_array(Xv, lay_out, tr_out).astype(real)
                         assert np.array_equal(got, want), (lay_in, tr_in, lay_out, tr_out)
 
 

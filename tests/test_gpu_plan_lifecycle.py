@@ -10,8 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_keep_operator as KO
-import test_gpu_operator as TO
+import solve_helpers as SH
 import tfqmrgpu_amd as T
 from conftest import load_problem
 from tfqmrgpu_amd import problems as PR
@@ -29,9 +28,9 @@ def system():
     assert (pr.LM, pr.LN) == (4, 4) and pr.nnzbA > pr.mb
     B8 = np.concatenate([pr.B, pr.B[:, :, ::-1] * (0.5 - 0.25j)], axis=2)     # the data of the other allowed shape: LN = 8
     pr8 = T.Problem(pr.rowPtrA, pr.colIndA, pr.A, pr.rowPtrX, pr.colIndX, pr.rowPtrB, pr.colIndB, B8, None, pr.tolerance, pr.index_offset)
-    diag = KO._diagonal(pr)
+    diag = SH.present_diagonal(pr)
     assert len(diag) == pr.mb
-    return pr, pr8, diag, KO._changed(pr, pr.A, diag, seed=11)
+    return pr, pr8, diag, SH.changed(pr, pr.A, diag, seed=11)
 
 
 class _Plan(T.Solver):
@@ -64,9 +63,9 @@ def _kept_patched_plan(s, pr, diag, A1, prec):
     s.new_buffer(nbytes)
     s.set_matrix("A", pr.A)
     s.set_matrix("B", pr.B)
-    KO._solve(s, prec)
-    KO._set_blocks(s, diag, A1)
-    return KO._solve(s, prec), nbytes
+    SH.solve_record(s, prec)
+    SH.patch_blocks(s, diag, A1)
+    return SH.solve_record(s, prec), nbytes
 
 
 @pytest.fixture(scope="module")
@@ -78,7 +77,7 @@ def fresh(system):
     def get(prec, LN=4, A=None):
         key = (prec, LN, None if A is None else hash(A.tobytes()))
         if key not in cache:
-            cache[key] = KO._fresh(pr8 if 8 == LN else pr, pr.A if A is None else A, prec)
+            cache[key] = SH.fresh_solve(pr8 if 8 == LN else pr, pr.A if A is None else A, prec)
         return cache[key]
     return get
 
@@ -89,13 +88,13 @@ def test_second_buffer_size_with_another_shape(system, fresh, prec):
     pr, pr8, diag, A1 = system
     with _Plan() as s:
         second, _ = _kept_patched_plan(s, pr, diag, A1, prec)
-        KO._same(second, fresh(prec, 4, A1))
+        SH.same_record(second, fresh(prec, 4, A1))
         s.new_buffer(s.buffer_size(4, 8, prec))                          # 4 x 4 -> 4 x 8: M^-1, the kept copy and the dirty marks are the old shape's
         s.set_matrix("A", A1)
         s.set_matrix("B", pr8.B)
-        KO._same(KO._solve(s, prec), fresh(prec, 8, A1))
-        KO._set_blocks(s, diag, pr.A)                                    # the plan still keeps: a copy of the new shape takes the patch
-        KO._same(KO._solve(s, prec), fresh(prec, 8))
+        SH.same_record(SH.solve_record(s, prec), fresh(prec, 8, A1))
+        SH.patch_blocks(s, diag, pr.A)                                    # the plan still keeps: a copy of the new shape takes the patch
+        SH.same_record(SH.solve_record(s, prec), fresh(prec, 8))
 
 
 # ---- 2. a second setBuffer without a new bufferSize ----------------------------------------------------------------------------------------
@@ -106,12 +105,12 @@ def test_second_set_buffer_on_a_new_workspace(system, fresh, prec):
         _, nbytes = _kept_patched_plan(s, pr, diag, A1, prec)
         s.new_buffer(nbytes)
         # the new buffer holds no A: the set-up has nothing to scale (status 14, key 'A'), and nothing to patch
-        assert T.decode(T.lib.tfqmrgpu_bsrsv_solve(s.handle, s.plan, KO.TOL[prec], KO.MAXIT))[::2] == (14, ord("A"))
+        assert T.decode(T.lib.tfqmrgpu_bsrsv_solve(s.handle, s.plan, SH.TOL[prec], SH.MAXIT))[::2] == (14, ord("A"))
         s.set_matrix("A", A1)
         s.set_matrix("B", pr.B)
-        KO._same(KO._solve(s, prec), fresh(prec, 4, A1))
-        KO._set_blocks(s, diag, pr.A)
-        KO._same(KO._solve(s, prec), fresh(prec, 4))
+        SH.same_record(SH.solve_record(s, prec), fresh(prec, 4, A1))
+        SH.patch_blocks(s, diag, pr.A)
+        SH.same_record(SH.solve_record(s, prec), fresh(prec, 4))
 
 
 # ---- 3. keepOperator(0) after patches -----------------------------------------------------------------------------------------------------
@@ -120,13 +119,13 @@ def test_keep_operator_off_after_patches(system, fresh, prec):
     pr, _, diag, A1 = system
     with _Plan() as s:
         _kept_patched_plan(s, pr, diag, A1, prec)
-        KO._set_blocks(s, diag[:3], pr.A)                                # marks that no set-up has seen go with the copy
+        SH.patch_blocks(s, diag[:3], pr.A)                                # marks that no set-up has seen go with the copy
         s.keep_operator(False)
         with pytest.raises(T.TfqmrError) as e:                           # as on a plan that never kept: A M^-1 cannot be patched
             s.set_blocks("A", diag[:1], pr.A[diag[:1]])
         assert T.decode(e.value.status)[0] == 19
         s.set_matrix("A", pr.A)
-        KO._same(KO._solve(s, prec), fresh(prec, 4))
+        SH.same_record(SH.solve_record(s, prec), fresh(prec, 4))
 
 
 # ---- 4. lists that grow -----------------------------------------------------------------------------------------------------------------
@@ -134,7 +133,7 @@ def test_keep_operator_off_after_patches(system, fresh, prec):
 def test_block_list_and_dirty_list_grow(system, fresh, prec):
     pr, _, diag, A1 = system
     every = np.arange(pr.nnzbA, dtype=np.int32)
-    one = KO._changed(pr, pr.A, diag[5:6], seed=23)
+    one = SH.changed(pr, pr.A, diag[5:6], seed=23)
     with _Plan() as s:
         s.create_plan(pr)
         nbytes = s.buffer_size(pr.LM, pr.LN, prec)
@@ -143,11 +142,11 @@ def test_block_list_and_dirty_list_grow(system, fresh, prec):
         s.new_buffer(nbytes)
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        KO._same(KO._solve(s, prec), fresh(prec, 4))
-        KO._set_blocks(s, diag[5:6], one)                                # a list of one block; the set-up redoes one row and one column
-        KO._same(KO._solve(s, prec), fresh(prec, 4, one))
-        KO._set_blocks(s, every, A1)                                     # every block: both device lists are longer than before
-        KO._same(KO._solve(s, prec), fresh(prec, 4, A1))
+        SH.same_record(SH.solve_record(s, prec), fresh(prec, 4))
+        SH.patch_blocks(s, diag[5:6], one)                                # a list of one block; the set-up redoes one row and one column
+        SH.same_record(SH.solve_record(s, prec), fresh(prec, 4, one))
+        SH.patch_blocks(s, every, A1)                                     # every block: both device lists are longer than before
+        SH.same_record(SH.solve_record(s, prec), fresh(prec, 4, A1))
         assert np.array_equal(s.get_blocks(np.arange(pr.nnzbX, dtype=np.int32)), s.get_matrix())
 
 
@@ -155,8 +154,8 @@ def test_block_list_and_dirty_list_grow(system, fresh, prec):
 def _operator_solve(torch, s, pr, prec="z"):
     s.set_matrix("A", 0 * pr.A)
     s.set_matrix("B", pr.B)
-    s.set_operator(TO._builtin_as_operator(torch, s, pr, prec, s.plan_view(), []))
-    st = s.solve(pr.tolerance, KO.MAXIT)
+    s.set_operator(SH.builtin_as_operator(torch, s, pr, prec, s.plan_view(), []))
+    st = s.solve(pr.tolerance, SH.MAXIT)
     return dict(status=st, iterations=s.get_info()["iterations"], bounds=s.bound_history(), X=s.get_matrix())
 
 
@@ -174,7 +173,7 @@ def test_operator_plan_changes_its_shape(system):
         with _Plan() as f:
             f.create_plan(p)
             f.new_buffer(f.buffer_size(p.LM, p.LN, "z"))
-            KO._same(got, _operator_solve(torch, f, p))
+            SH.same_record(got, _operator_solve(torch, f, p))
     assert second["X"].shape[2] == 8 and first["X"].shape[2] == 4
 
 
@@ -189,7 +188,7 @@ def test_multiply_order_life_cycle():
         nY = pr.nnzbX
         dS = torch.from_numpy(view["starts"].view(np.int32)).cuda()
         dP = torch.from_numpy(view["pairs"].view(np.int32)).cuda()
-        dA = TO._native_A(torch, pr, "z")
+        dA = SH.native_A(torch, pr, "z")
         dX = torch.from_numpy(PR.hashed_uniform(3, (nY, 2, 16, 16))).cuda()
         dY, dZ = torch.zeros_like(dX), torch.zeros_like(dX)
         args = (b"z", 16, 16, nY, dS.data_ptr(), dP.data_ptr())
@@ -230,13 +229,13 @@ def test_destroy_in_every_state(system, steps):
         if steps >= 3:
             s.set_matrix("A", pr.A)                                      # 3: operands, no set-up
             s.set_matrix("B", pr.B)
-            KO._set_blocks(s, diag[:2], A1)                              # (not scaled yet: the patch goes into the buffer; a block list exists)
+            SH.patch_blocks(s, diag[:2], A1)                              # (not scaled yet: the patch goes into the buffer; a block list exists)
         if steps >= 4:
             s.get_preconditioner(values=False)                           # 4: set up and kept, never solved
         if steps >= 5:
-            KO._set_blocks(s, diag[2:4], A1)                             # 5: solved, with marks that no set-up has seen
+            SH.patch_blocks(s, diag[2:4], A1)                             # 5: solved, with marks that no set-up has seen
             s.solve(1e-9, 5)
-            KO._set_blocks(s, diag[4:6], A1)
+            SH.patch_blocks(s, diag[4:6], A1)
 
 
 def test_destroy_a_handle_with_a_vote_buffer():
@@ -286,7 +285,7 @@ def _left(s, status, prec):
 
 
 def _warm(s, prec):
-    return (s.refine_from if prec == "m" else s.solve_from)(KO.TOL[prec], WARM_MAXIT)
+    return (s.refine_from if prec == "m" else s.solve_from)(SH.TOL[prec], WARM_MAXIT)
 
 
 def _everything_alive(s, pr, prec, kept):
@@ -295,14 +294,14 @@ def _everything_alive(s, pr, prec, kept):
     cplx = lambda seed, shape: PR.hashed_uniform(seed, shape) - 0.5 + 1j * (PR.hashed_uniform(seed + 1, shape) - 0.5)   # noqa: E731
     s.set_matrix("A", pr.A)
     s.set_matrix("B", pr.B)
-    out["solve"] = _left(s, s.solve(KO.TOL[prec], WARM_MAXIT), prec)
+    out["solve"] = _left(s, s.solve(SH.TOL[prec], WARM_MAXIT), prec)
     if kept:
         out["Minv"], out["n_identity"] = s.get_preconditioner()
     out["residual"], out["leak"], out["map"], out["drop"] = s.residual(), s.truncation_leak(), s.leak_map(), s.drop_cost()
     s.keep_starts(2)
     s.push_start()
     s.set_matrix("B", pr.B[:, :, ::-1] * (0.5 - 0.25j))
-    out["solve2"] = _left(s, s.solve(KO.TOL[prec], WARM_MAXIT), prec)
+    out["solve2"] = _left(s, s.solve(SH.TOL[prec], WARM_MAXIT), prec)
     s.push_start()
     out["starts"] = (s.start_count(), s.start_depth())
     s.set_matrix("B", pr.B + 0.3 * cplx(51, pr.B.shape))                # not in the span of the two: the warm solve has work to do
@@ -387,7 +386,7 @@ def test_second_set_buffer_with_everything_alive(stencils, alive_fresh, prec, ke
     with _Plan() as never:                                               # a plan whose A was never set
         never.create_plan(pr)
         _lay_out(never, 4, prec, kept)
-        refused = warm(never.handle, never.plan, KO.TOL[prec], WARM_MAXIT)
+        refused = warm(never.handle, never.plan, SH.TOL[prec], WARM_MAXIT)
     assert T.decode(refused)[::2] == (14, ord("A"))
     with _Plan() as s:
         s.create_plan(pr)
@@ -395,5 +394,5 @@ def test_second_set_buffer_with_everything_alive(stencils, alive_fresh, prec, ke
         _same_entries(_everything_alive(s, pr, prec, kept), want)
         s.new_buffer(nbytes)
         assert (s.start_count(), s.start_depth()) == (0, 2)
-        assert warm(s.handle, s.plan, KO.TOL[prec], WARM_MAXIT) == refused   # the new buffer holds no A, and no X0 of the old one
+        assert warm(s.handle, s.plan, SH.TOL[prec], WARM_MAXIT) == refused   # the new buffer holds no A, and no X0 of the old one
         _same_entries(_everything_alive(s, pr, prec, kept), want)

@@ -8,6 +8,7 @@ import pytest
 import precond_ref as PC
 import tfqmrgpu_amd as T
 from conftest import ALL_NAMES, FD_NAMES, load_problem
+from solve_helpers import solve_and_check_residual, system_with_two_unit_rows
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -15,16 +16,6 @@ pytestmark = pytest.mark.gpu
 BJ = T.PRECOND_BLOCK_JACOBI
 SIZES = [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8, 64),
          (16, 16), (16, 32), (16, 64), (32, 32), (32, 64), (64, 64)]
-
-
-def _plan(s, pr, prec, kind=None, shadow=T.SHADOW_HASH):
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    s.set_shadow_mode(shadow)
-    s.set_buffer(nbytes=nbytes)
-    return nbytes
 
 
 # ---- M^-1 itself ----------------------------------------------------------------------------------------------------------------
@@ -48,8 +39,7 @@ def _diagonal_system(LM, seed):
 def test_inverse_of_the_diagonal_blocks(prec, LM):
     """|M^-1 M - 1|_inf <= K LM eps kappa_inf(M), eps of the precision M^-1 is stored in (tests/precond_ref.py: MINV_K)"""
     pr = _diagonal_system(LM, seed=100 + LM)
-    with T.Solver() as s:
-        _plan(s, pr, prec, BJ)
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         Minv, n_identity = s.get_preconditioner()
     assert n_identity == 0
@@ -67,24 +57,12 @@ def test_inverse_of_the_diagonal_blocks(prec, LM):
 
 
 # ---- the solve, judged without an oracle ---------------------------------------------------------------------------------------
-def _solve_and_check_residual(oracle, pr, prec, tol, maxit=2000, shadow=T.SHADOW_HASH):
-    st, X, info = T.solve_problem(pr, prec, threshold=tol, max_iterations=maxit, preconditioner=BJ, shadow_mode=shadow)
-    worst = PC.worst_relative_residual(oracle, pr, X)
-    print("precond solve %s %dx%d: %d iterations, threshold %.0e, reported %.6e, recomputed %.6e (%.2e of it apart)" % (
-        prec, pr.LM, pr.LN, info["iterations"], tol, info["residual"], worst, abs(worst - info["residual"]) / info["residual"]))
-    assert st == 0
-    assert worst <= tol, worst
-    # right preconditioning leaves the residual unchanged: the bounds of tests/test_gpu_configs.py: _check_solution_on_device
-    assert abs(worst - info["residual"]) <= (2e-2 if prec == "c" else 1e-4) * info["residual"], (worst, info["residual"])
-    return X, info
-
-
 # every system with stored results under tests/golden but julia_kat: its solve ends at 5e-15, in the rounding noise of double
 # (tests/tolerances.py: "converges to 5e-15"), where no two summation orders agree to 1e-4 of the residual -- with or without M^-1
 # (its diagonal blocks are unit matrices: the preconditioner does nothing there)
 @pytest.mark.parametrize("name", [n for n in ALL_NAMES if n != "julia_kat"])
 def test_solve_of_the_fixtures_by_the_float64_residual(oracle, name):
-    _solve_and_check_residual(oracle, load_problem(name), "z", 1e-9)
+    solve_and_check_residual(oracle, load_problem(name), "z", 1e-9)
 
 
 # complex<float> cases.  A float residual can only be held against the float64 residual of the returned X to 2e-2 where it is far above
@@ -124,7 +102,7 @@ def _check_flop_count(oracle, pr, info):
 def test_solve_of_every_block_shape_by_the_float64_residual(oracle, size):
     LM, LN = size
     pr = PR.stencil_2d(4, 4, LM, LN, 2, seed=LM + LN, radius=2.3)
-    _, info = _solve_and_check_residual(oracle, pr, "z", 1e-9, maxit=100)
+    _, info = solve_and_check_residual(oracle, pr, "z", 1e-9, maxit=100)
     assert info["n_identity"] == 0
     _check_flop_count(oracle, pr, info)
 
@@ -133,7 +111,7 @@ def test_solve_of_every_block_shape_by_the_float64_residual(oracle, size):
 def test_float_solve_of_every_block_shape_by_the_float64_residual(oracle, size):
     LM, LN = size
     pr, tol, info0 = _float_case(oracle, LM, LN)
-    _, info = _solve_and_check_residual(oracle, pr, "c", tol, maxit=100, shadow=T.SHADOW_GLIBC_RAND)
+    _, info = solve_and_check_residual(oracle, pr, "c", tol, maxit=100, shadow=T.SHADOW_GLIBC_RAND)
     print("precond float case %dx%d: oracle %d iterations, residual %.3e" % (LM, LN, info0["iterations"], info0["residual"]))
     assert info["n_identity"] == 0
     _check_flop_count(oracle, pr, info)
@@ -146,8 +124,7 @@ def test_solve_matches_the_oracle_fed_with_the_librarys_inverse(oracle, name):
     numpy) and X = M^-1 Y: equal iteration counts, X within 1e-7 max|X| (the tolerance of tests/test_gpu_parity.py for 'z')"""
     pr = load_problem(name)
     tol = 1e-9
-    with T.Solver() as s:
-        _plan(s, pr, "z", BJ, T.SHADOW_GLIBC_RAND)
+    with T.Solver.open(pr, "z", preconditioner=BJ, shadow_mode=T.SHADOW_GLIBC_RAND) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         Minv, n_identity = s.get_preconditioner()
@@ -182,8 +159,8 @@ def test_off_is_bit_identical_to_never_asked(prec, name):
     tol = 1e-4 if prec == "c" else 1e-9
     got = []
     for kind in (None, T.PRECOND_NONE):
-        with T.Solver() as s:
-            nbytes = _plan(s, pr, prec, kind)
+        with T.Solver.open(pr, prec, preconditioner=kind) as s:
+            nbytes = s.buffer_bytes
             s.set_matrix("A", pr.A)
             s.set_matrix("B", pr.B)
             st = s.solve(tol, 500)
@@ -191,8 +168,8 @@ def test_off_is_bit_identical_to_never_asked(prec, name):
     a, b = got
     assert a[0] == b[0] == 0 and a[1] == b[1] and a[2] == b[2]
     assert np.array_equal(a[3], b[3]) and np.array_equal(a[4], b[4]) and np.array_equal(a[5], b[5])
-    with T.Solver() as s:                                            # and a plan with block Jacobi has the same buffer
-        assert _plan(s, pr, prec, BJ) == a[1]
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:                 # and a plan with block Jacobi has the same buffer
+        assert s.buffer_bytes == a[1]
 
 
 # ---- reuse ------------------------------------------------------------------------------------------------------------------------
@@ -204,14 +181,12 @@ def test_reuse_over_solves_and_a_new_matrix(oracle, prec):
     A2 = pr.A * (1 + 0.05 * rng.standard_normal(pr.A.shape))
 
     def fresh(A, B):
-        with T.Solver() as s:
-            _plan(s, pr, prec, BJ)
+        with T.Solver.open(pr, prec, preconditioner=BJ) as s:
             s.set_matrix("A", A)
             s.set_matrix("B", B)
             assert s.solve(1e-9, 500) == 0
             return s.get_info(), s.get_matrix(), s.bound_history()
-    with T.Solver() as s:
-        _plan(s, pr, prec, BJ)
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 500) == 0
@@ -236,24 +211,11 @@ def test_reuse_over_solves_and_a_new_matrix(oracle, prec):
 
 
 # ---- edge cases -------------------------------------------------------------------------------------------------------------------
-def _system_with_two_unit_rows():
-    """block row 3 has no diagonal block in the pattern of A, the diagonal block of block row 7 has a zero row (a zero pivot whatever
-    the exchanges)"""
-    pr = PR.stencil_2d(5, 4, 8, 8, 2, seed=9)
-    rows = PC.block_rows(pr.rowPtrA)
-    keep = ~((rows == pr.colIndA) & (rows == 3))
-    rp = np.concatenate([[0], np.cumsum(np.bincount(rows[keep], minlength=pr.mb))])
-    cut = T.Problem(rp, pr.colIndA[keep], pr.A[keep].copy(), pr.rowPtrX, pr.colIndX, pr.rowPtrB, pr.colIndB, pr.B, None, 1e-9)
-    cut.A[PC.diagonal_blocks(cut)[7], 1, :] = 0
-    return cut
-
-
 @pytest.mark.parametrize("prec", ["z", "c"])
 def test_rows_without_an_invertible_diagonal_block(oracle, prec):
-    pr = _system_with_two_unit_rows()
+    pr = system_with_two_unit_rows()
     tol = 1e-9 if prec == "z" else 1e-4
-    with T.Solver() as s:
-        _plan(s, pr, prec, BJ)
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(tol, 500) == 0
@@ -272,8 +234,7 @@ def test_non_finite_diagonal_block_gets_the_unit_matrix():
     pr = _diagonal_system(16, seed=5)
     pr.A[6, 2, 3] = np.nan
     pr.A[9, 0, 0] = np.inf
-    with T.Solver() as s:
-        _plan(s, pr, "z", BJ)
+    with T.Solver.open(pr, "z", preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         Minv, n_identity = s.get_preconditioner()
     assert n_identity == 2 and np.array_equal(Minv[6], np.eye(16)) and np.array_equal(Minv[9], np.eye(16))
@@ -286,8 +247,7 @@ def test_inverse_that_overflows_its_storage_gets_the_unit_matrix(prec, tiny):
     stored in -- nothing but finite numbers is stored, the row is counted"""
     pr = _diagonal_system(8, seed=6)
     pr.A[5] *= tiny
-    with T.Solver() as s:
-        _plan(s, pr, prec, BJ)
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         Minv, n_identity = s.get_preconditioner()
     assert np.all(np.isfinite(Minv))
@@ -297,8 +257,7 @@ def test_inverse_that_overflows_its_storage_gets_the_unit_matrix(prec, tiny):
 def test_user_operator_plans_refuse():
     pr = load_problem("fd_16x16_small")
     for prec in "zc":
-        with T.Solver() as s:
-            _plan(s, pr, prec, BJ)
+        with T.Solver.open(pr, prec, preconditioner=BJ) as s:
             s.set_matrix("A", pr.A)
             s.set_matrix("B", pr.B)
             s.set_operator(lambda *a: 0.0)
@@ -310,8 +269,7 @@ def test_user_operator_plans_refuse():
 
 def test_switching_the_kind_needs_a_new_matrix():
     pr = load_problem("fd_16x16_small")
-    with T.Solver() as s:
-        _plan(s, pr, "z", BJ)
+    with T.Solver.open(pr, "z", preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 500) == 0
@@ -329,8 +287,7 @@ def test_switching_the_kind_needs_a_new_matrix():
     st0, X0, info0 = T.solve_problem(pr, "z", threshold=1e-9, max_iterations=500)
     assert plain[0] == info0["iterations"] and np.array_equal(plain[1], X0)
     assert again[0] == with_bj[0] and np.array_equal(again[1], with_bj[1])
-    with T.Solver() as s:                                            # never set: the getter refuses
-        _plan(s, pr, "z")
+    with T.Solver.open(pr, "z") as s:                                            # never set: the getter refuses
         assert T.decode(T.lib.tfqmrgpuExt_getPreconditioner(s.handle, s.plan, None, None))[0] == 14
         s.set_preconditioner(BJ)                                     # no A yet
         assert T.decode(T.lib.tfqmrgpuExt_getPreconditioner(s.handle, s.plan, None, None))[::2] == (14, ord("A"))
@@ -340,8 +297,7 @@ def test_work_vector_and_stopped_solves_return_x(oracle):
     """getWorkVector(1) is X like getMatrix('X'); a solve that ends at maxIterations is back-transformed too: its X is M^-1 times the Y
     that the oracle has after the same iterations"""
     pr = load_problem("fd_16x16_small")
-    with T.Solver() as s:
-        _plan(s, pr, "z", BJ, T.SHADOW_GLIBC_RAND)
+    with T.Solver.open(pr, "z", preconditioner=BJ, shadow_mode=T.SHADOW_GLIBC_RAND) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         Minv = s.get_preconditioner()[0]
@@ -357,8 +313,7 @@ def test_apply_operator_multiplies_with_the_scaled_matrix(oracle):
     rng = np.random.default_rng(2)
     X = rng.standard_normal((pr.nnzbX, 16, 16)) + 1j * rng.standard_normal((pr.nnzbX, 16, 16))
     an = oracle.analyse(pr)
-    with T.Solver() as s:
-        _plan(s, pr, "z", BJ)
+    with T.Solver.open(pr, "z", preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         Minv = s.get_preconditioner()[0]                             # scales A
         s.set_matrix("X", X)

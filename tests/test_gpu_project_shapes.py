@@ -14,20 +14,9 @@ import project_cases as PC
 import project_ref as P
 import tfqmrgpu_amd as T
 from conftest import offset1
-from test_gpu_project_start import _deviations, _same_bits
+from helpers import deviations, same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _open(pr, prec, depth):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    assert s.keep_starts(depth) == 0
-    s.set_buffer(nbytes=nbytes)
-    s.set_matrix("A", pr.A)
-    s.set_matrix("B", pr.B)
-    return s
 
 
 def _push(s, starts_newest_first):
@@ -47,7 +36,7 @@ def _project(s):
 
 def _run(cs, depth=None, pr=None):
     """(gamma, n_used, X) of a fresh plan that had the starts of the case pushed in plain order"""
-    with _open(cs.pr if pr is None else pr, cs.prec, cs.K if depth is None else depth) as s:
+    with T.Solver.open(cs.pr if pr is None else pr, cs.prec, keep_starts=cs.K if depth is None else depth).load() as s:
         back = _push(s, cs.starts)
         assert s.start_count() == cs.K and all(np.array_equal(a, b) for a, b in zip(back, cs.starts))      # stored(): nothing left to round
         return _project(s)
@@ -57,7 +46,7 @@ def _compare(what, cs, ref, starts, gamma, used, X):
     """the existing comparison; prints before it asserts.  Returns the two deviations as fractions of their allowance"""
     assert np.array_equal(used, ref["n_used"]), what
     assert np.all(np.isfinite(gamma)) and np.all(np.isfinite(X)), what
-    dg, bg, dx, bx = _deviations(cs.pr, ref, dict(coefficients=gamma), X, starts, cs.prec)
+    dg, bg, dx, bx = deviations(cs.pr, ref, dict(coefficients=gamma), X, starts, cs.prec)
     fg, fx = float((dg / bg).max()), float((dx / bx).max())
     print("project shapes %-34s gamma %.3e of allowed (abs %.2e), X %.3e of allowed (abs %.2e)" % (what, fg, dg.max(), fx, dx.max()))
     assert np.all(dg <= bg), (what, fg)
@@ -125,20 +114,20 @@ def test_ring_position_does_not_enter_the_arithmetic(oracle, key):
     S = cs.starts[::-1]                                     # six different arrays, in the order in which they are pushed
 
     def fresh(survivors_oldest_first):
-        with _open(cs.pr, cs.prec, len(survivors_oldest_first)) as t:
+        with T.Solver.open(cs.pr, cs.prec, keep_starts=len(survivors_oldest_first)).load() as t:
             _push(t, survivors_oldest_first[::-1])
             return _project(t)
 
     def check(step, s, survivors_oldest_first):
         assert s.start_count() == len(survivors_oldest_first)
         got, want = _project(s), fresh(survivors_oldest_first)
-        assert all(_same_bits(a, b) for a, b in zip(got, want)), (key, step)
+        assert all(same_bits(a, b) for a, b in zip(got, want)), (key, step)
         newest_first = survivors_oldest_first[::-1]
         ref = P.project(oracle, cs.pr, cs.A, newest_first, cs.B, cs.prec)
         assert np.all(ref["n_used"] == len(newest_first)) and ref["ratio"].min() >= PC.KEPT_RATIO_MIN
         _compare("%s ring step %d" % (PC.case_id(key), step), cs, ref, newest_first, *got)
 
-    with _open(cs.pr, cs.prec, 3) as s:
+    with T.Solver.open(cs.pr, cs.prec, keep_starts=3).load() as s:
         for X in S[:5]:
             s.set_matrix("X", X)
             s.push_start()
@@ -184,8 +173,8 @@ def test_zero_column_of_b_on_a_ragged_shape(oracle):
 @pytest.mark.parametrize("key", PC.CASES_F, ids=PC.case_id)
 def test_two_calls_give_the_same_bits(oracle, key):
     cs, _ = _case(oracle, key)
-    with _open(cs.pr, cs.prec, cs.K) as s:
+    with T.Solver.open(cs.pr, cs.prec, keep_starts=cs.K).load() as s:
         _push(s, cs.starts)
         first, second = _project(s), _project(s)
-    assert all(_same_bits(a, b) for a, b in zip(first, second)), key
-    assert all(_same_bits(a, b) for a, b in zip(first, _run(cs))), key          # ... and those of another plan
+    assert all(same_bits(a, b) for a, b in zip(first, second)), key
+    assert all(same_bits(a, b) for a, b in zip(first, _run(cs))), key          # ... and those of another plan

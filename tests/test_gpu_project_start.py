@@ -13,6 +13,7 @@ import project_ref as P
 import residual_ref as RR
 import tfqmrgpu_amd as T
 from conftest import ROOT, load_problem, torchrun
+from helpers import deviations, same_bits
 from precond_ref import _product, diagonal_blocks
 
 pytestmark = pytest.mark.gpu
@@ -20,29 +21,6 @@ pytestmark = pytest.mark.gpu
 POINTER_INVALID, UNDOCUMENTED, NO_IMPLEMENTATION = 7, 14, 19
 BJ = T.PRECOND_BLOCK_JACOBI
 THR = {"z": 1e-9, "c": 1e-4, "m": 1e-9}      # what "converged" means for the starts
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _open(pr, prec, depth=None, kind=None, keep=False):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    if depth is not None:
-        s.keep_starts(depth)
-    s.set_buffer(nbytes=nbytes)
-    s.set_matrix("B", pr.B)
-    return s
 
 
 def _converged(s, prec, what):
@@ -54,7 +32,8 @@ def _energy_loop(name, prec, fifth=False):
     back, newest first; A and B as the plan stores them"""
     pr = load_problem(name)
     sig = P.shifts(pr, name, fifth)
-    s = _open(pr, prec, depth=len(sig) - 1)
+    s = T.Solver.open(pr, prec, keep_starts=len(sig) - 1)
+    s.set_matrix("B", pr.B)
     starts = []
     for k, sigma in enumerate(sig[:-1]):
         s.set_matrix("A", P.shifted(pr, sigma))
@@ -64,17 +43,6 @@ def _energy_loop(name, prec, fifth=False):
         starts.insert(0, s.get_matrix())
     s.set_matrix("A", P.shifted(pr, sig[-1]))
     return pr, s, starts, RR.stored(P.shifted(pr, sig[-1]), prec), RR.stored(pr.B, prec)
-
-
-def _deviations(pr, ref, got, X, starts, prec):
-    """(worst gamma deviation / its bound, worst X deviation / its bound) over all right-hand sides"""
-    tol = P.gamma_tolerance(ref, prec)                                   # [nCols, LN], relative to the largest |gamma_i|
-    gmax = np.abs(ref["gamma"]).max(axis=-1)
-    dg = np.abs(got["coefficients"] - ref["gamma"]).max(axis=-1)
-    col = ref["an"]["colindx"].astype(np.int64)
-    reach = sum(np.abs(np.asarray(S)) for S in starts)                   # sum |S_i| per element
-    bound_x = (tol * gmax)[col][:, None, :] * reach + P.EPS[prec] * np.abs(ref["X"]) + 1e-300
-    return dg, tol * gmax + 1e-300, np.abs(X - ref["X"]), bound_x
 
 
 # ---- 1. parity ---------------------------------------------------------------------------------------------------------------------------
@@ -92,7 +60,7 @@ def test_parity_with_the_reference(oracle, name, prec):
         assert s.start_count() == 3
     ref = P.project(oracle, pr, A, starts, B, prec)
     assert np.array_equal(got["n_used"], ref["n_used"]) and np.all(got["n_used"] == 3)
-    dg, bg, dx, bx = _deviations(pr, ref, got, X, starts, prec)
+    dg, bg, dx, bx = deviations(pr, ref, got, X, starts, prec)
     print("project parity %-18s %s: gamma %.2e of allowed (abs %.2e), X %.2e of allowed (abs %.2e)" % (
         name, prec, (dg / bg).max(), dg.max(), (dx / bx).max(), dx.max()))
     assert np.all(dg <= bg), (name, prec, (dg / bg).max())
@@ -148,7 +116,8 @@ def test_edge_cases_of_the_pivot_rule(oracle, prec):
     an = oracle.analyse(pr)
     col = an["colindx"].astype(np.int64)
     live = [j for j in range(pr.LN) if j != 5]
-    with _open(pr, prec, depth=1) as s:
+    with T.Solver.open(pr, prec, keep_starts=1) as s:
+        s.set_matrix("B", pr.B)
         s.set_matrix("A", P.shifted(pr, sig[0]))
         _converged(s, prec, "start")
         s.push_start()
@@ -175,14 +144,14 @@ def test_edge_cases_of_the_pivot_rule(oracle, prec):
         twice = s.project_start()
         assert np.all(twice["n_used"][:, live] == 1) and np.all(twice["coefficients"][:, :, 1:] == 0)
         assert np.all(np.isfinite(twice["coefficients"])) and np.all(np.isfinite(s.get_matrix()))
-        assert _same_bits(twice["coefficients"][:, :, 0], g)
+        assert same_bits(twice["coefficients"][:, :, 0], g)
         # a zero start, the newest: dropped, the start behind it is used
         s.set_matrix("X", np.zeros_like(S0))
         s.push_start()
         assert s.start_count() == 3
         zero = s.project_start()
         assert np.all(zero["n_used"][:, live] == 1) and np.all(zero["coefficients"][:, :, 0] == 0) and np.all(zero["coefficients"][:, :, 2] == 0)
-        assert _same_bits(zero["coefficients"][:, :, 1], g)
+        assert same_bits(zero["coefficients"][:, :, 1], g)
         # shrinking the depth drops the oldest starts: the zero start alone is left, and nothing can be used
         assert s.keep_starts(1) == 0 and s.start_count() == 1
         none = s.project_start()
@@ -198,7 +167,7 @@ def test_depth_four(oracle, prec):
         X = s.get_matrix()
     ref = P.project(oracle, pr, A, starts, B, prec)
     assert np.all(got["n_used"] == 4) and np.array_equal(got["n_used"], ref["n_used"])
-    dg, bg, dx, bx = _deviations(pr, ref, got, X, starts, prec)
+    dg, bg, dx, bx = deviations(pr, ref, got, X, starts, prec)
     print("project depth 4 stencil_8x32 %s: gamma %.2e of allowed, X %.2e of allowed" % (prec, (dg / bg).max(), (dx / bx).max()))
     assert np.all(dg <= bg) and np.all(dx <= bx)
 
@@ -209,7 +178,8 @@ def test_preconditioned_plan_reads_the_kept_copy_with_its_patch(oracle):
     pr = load_problem(name)
     sig = P.shifts(pr, name)
     diag = diagonal_blocks(pr)
-    with _open(pr, prec, depth=2, kind=BJ, keep=True) as s:
+    with T.Solver.open(pr, prec, keep_starts=2, preconditioner=BJ, keep_operator=True) as s:
+        s.set_matrix("B", pr.B)
         starts = []
         s.set_matrix("A", P.shifted(pr, sig[0]))
         for k in (0, 1):
@@ -224,18 +194,19 @@ def test_preconditioned_plan_reads_the_kept_copy_with_its_patch(oracle):
     A, B = RR.stored(P.shifted(pr, sig[3]), prec), RR.stored(pr.B, prec)
     ref = P.project(oracle, pr, A, starts, B, prec)
     assert np.array_equal(got["n_used"], ref["n_used"])
-    dg, bg, dx, bx = _deviations(pr, ref, got, X, starts, prec)
+    dg, bg, dx, bx = deviations(pr, ref, got, X, starts, prec)
     print("project preconditioned: gamma %.2e of allowed, X %.2e of allowed" % ((dg / bg).max(), (dx / bx).max()))
     assert np.all(dg <= bg) and np.all(dx <= bx)
     # scaled and no copy kept: refused, X untouched
-    with _open(pr, prec, depth=2, kind=BJ) as s:
+    with T.Solver.open(pr, prec, keep_starts=2, preconditioner=BJ) as s:
+        s.set_matrix("B", pr.B)
         s.set_matrix("A", P.shifted(pr, sig[0]))
         _converged(s, prec, "start")
         s.push_start()
         X0 = s.get_matrix()
         g = np.full((int(s.plan_view()["nCols"]), pr.LN, 2, 2), 7.0)
         assert T.decode(T.lib.tfqmrgpuExt_projectStart(s.handle, s.plan, g.ctypes.data_as(C.c_void_p), None))[::2] == (NO_IMPLEMENTATION, 0)
-        assert _same_bits(s.get_matrix(), X0) and np.all(g == 7.0)
+        assert same_bits(s.get_matrix(), X0) and np.all(g == 7.0)
 
 
 # ---- 5. determinism and side effects -------------------------------------------------------------------------------------------------------
@@ -251,23 +222,24 @@ def test_deterministic_and_without_side_effects(name, prec):
         s.push_start()
         assert s.keep_starts(3) == 0 and s.start_count() == 3
         after = (vectors(), s.bound_history(), s.get_info(), s.refinement_history())
-        assert all(_same_bits(before[0][w], after[0][w]) for w in before[0])
-        assert _same_bits(before[1], after[1]) and before[2] == after[2] and _same_bits(before[3], after[3])
+        assert all(same_bits(before[0][w], after[0][w]) for w in before[0])
+        assert same_bits(before[1], after[1]) and before[2] == after[2] and same_bits(before[3], after[3])
         # two calls give the same bits (the ring: the projected X on top of the two newest starts)
         out = []
         for _ in range(2):
             got = s.project_start()
             out.append((got["coefficients"], got["n_used"], s.get_matrix()))
-        assert all(_same_bits(a, b) for a, b in zip(out[0], out[1]))
-        assert not _same_bits(out[0][2], starts[0]) and np.all(np.isfinite(first["coefficients"]))
+        assert all(same_bits(a, b) for a, b in zip(out[0], out[1]))
+        assert not same_bits(out[0][2], starts[0]) and np.all(np.isfinite(first["coefficients"]))
         # a cold solve on this plan is the cold solve of a plan that keeps nothing
         st = s.solve(THR[prec], 7)
         cold = (st, s.get_matrix(), s.bound_history(), s.get_info()["residual"], s.get_info()["iterations"])
-        with _open(pr, prec) as t:
+        with T.Solver.open(pr, prec) as t:
+            t.set_matrix("B", pr.B)
             t.set_matrix("A", P.shifted(pr, P.shifts(pr, name)[-1]))
             st = t.solve(THR[prec], 7)
             plain = (st, t.get_matrix(), t.bound_history(), t.get_info()["residual"], t.get_info()["iterations"])
-        assert cold[0] == plain[0] and _same_bits(cold[1], plain[1]) and _same_bits(cold[2], plain[2]) and cold[3:] == plain[3:]
+        assert cold[0] == plain[0] and same_bits(cold[1], plain[1]) and same_bits(cold[2], plain[2]) and cold[3:] == plain[3:]
         # keep_starts(0) releases everything
         assert s.keep_starts(0) == 0 and s.start_count() == 0
         assert T.decode(T.lib.tfqmrgpuExt_projectStart(s.handle, s.plan, None, None))[::2] == (UNDOCUMENTED, ord("X"))
@@ -277,7 +249,8 @@ def test_deterministic_and_without_side_effects(name, prec):
 def test_statuses_that_need_a_device():
     pr = load_problem("dense_random_rect")
     raw = lambda s: T.decode(T.lib.tfqmrgpuExt_projectStart(s.handle, s.plan, None, None))[::2]      # noqa: E731
-    with _open(pr, "z", depth=2) as s:
+    with T.Solver.open(pr, "z", keep_starts=2) as s:
+        s.set_matrix("B", pr.B)
         X0 = s.get_matrix()
         s.push_start()
         assert raw(s) == (UNDOCUMENTED, ord("A"))           # A never set whole
@@ -285,7 +258,7 @@ def test_statuses_that_need_a_device():
         s.set_operator(lambda *a: 0.0)
         assert raw(s) == (NO_IMPLEMENTATION, 0)
         s.set_operator(None)
-        assert _same_bits(s.get_matrix(), X0)
+        assert same_bits(s.get_matrix(), X0)
         # the starts belong to the buffer: setBuffer releases them, the depth stays
         s.set_buffer(nbytes=s.buffer_size(pr.LM, pr.LN, "z"))
         assert s.start_count() == 0
@@ -310,7 +283,7 @@ def test_two_ranks_give_the_bits_of_one(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     g = np.load(out)
     assert len(g["n_cols"]) == 2 and all(n > 0 for n in g["n_cols"]) and list(g["calls"]) == [0, 0]      # local: no collective
-    assert _same_bits(g["gamma"], got["coefficients"]) and np.array_equal(g["used"], got["n_used"]) and _same_bits(g["X"], X)
+    assert same_bits(g["gamma"], got["coefficients"]) and np.array_equal(g["used"], got["n_used"]) and same_bits(g["X"], X)
 
 
 # ---- 7. the loop ---------------------------------------------------------------------------------------------------------------------------

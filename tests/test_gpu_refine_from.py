@@ -11,6 +11,7 @@ import pytest
 
 import tfqmrgpu_amd as T
 from conftest import load_problem
+from helpers import bits, diagonal_blocks, same_bits, true_residual
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -19,59 +20,6 @@ POINTER_INVALID, BREAKDOWN, MAX_ITERATIONS, UNDOCUMENTED, NO_IMPLEMENTATION = 7,
 BJ = T.PRECOND_BLOCK_JACOBI
 SIZES = [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8, 64),
          (16, 16), (16, 32), (16, 64), (32, 32), (32, 64), (64, 64)]
-
-
-def true_residual(pr, X):
-    """max_rhs |A X - B| / |B| on the pattern of X, dense numpy arithmetic in double (small systems only)"""
-    mb, LM, LN = pr.mb, pr.LM, pr.LN
-    off = pr.index_offset
-    cols = sorted(set((pr.colIndX - off).tolist()))
-    cid = {c: i for i, c in enumerate(cols)}
-    Xd = np.zeros((mb, len(cols), LM, LN), complex)
-    mask = np.zeros((mb, len(cols)), bool)
-    rows = np.repeat(np.arange(mb), np.diff(pr.rowPtrX))
-    for q, (r, c) in enumerate(zip(rows, pr.colIndX - off)):
-        Xd[r, cid[c]] = X[q]; mask[r, cid[c]] = True
-    Bd = np.zeros_like(Xd)
-    rowsB = np.repeat(np.arange(mb), np.diff(pr.rowPtrB))
-    for q, (r, c) in enumerate(zip(rowsB, pr.colIndB - off)):
-        Bd[r, cid[c]] = pr.B[q]
-    Y = np.zeros_like(Xd)
-    rowsA = np.repeat(np.arange(mb), np.diff(pr.rowPtrA))
-    for q, (r, k) in enumerate(zip(rowsA, pr.colIndA - off)):
-        Y[r] += np.einsum("ik,ckj->cij", pr.A[q], Xd[k])
-    R = (Y - Bd) * mask[:, :, None, None]                       # products outside the pattern of X are dropped (SURVEY App. C)
-    r2 = (np.abs(R) ** 2).sum(axis=(0, 2))                      # [cols, LN]
-    b2 = (np.abs(Bd) ** 2).sum(axis=(0, 2))
-    return float(np.sqrt((r2 / b2).max()))
-
-
-def _open(pr, prec="m", kind=None, keep=False, buffer=True):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    if buffer:
-        s.set_buffer(nbytes=nbytes)
-    return s
-
-
-def _loaded(pr, prec="m", **kw):
-    s = _open(pr, prec, **kw)
-    s.set_matrix("A", pr.A)
-    s.set_matrix("B", pr.B)
-    return s
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 def _last(info):
@@ -86,7 +34,7 @@ def _results(s):
 
 
 def _same_results(a, b):
-    return all(_same_bits(x, y) for x, y in zip(a[:4], b[:4])) and a[4] == b[4]
+    return all(same_bits(x, y) for x, y in zip(a[:4], b[:4])) and a[4] == b[4]
 
 
 # ---- 1. it continues, all 15 block shapes ----------------------------------------------------------------------------------------------
@@ -97,7 +45,7 @@ def test_continues_on_all_block_sizes(oracle, LM, LN):
     pr = PR.stencil_2d(5, 4, LM, LN, 2, seed=100 + LM + LN)
     st0, Xz, _ = oracle.solve(pr, "z", threshold=1e-9, max_iterations=300)
     assert st0 == 0
-    with _loaded(pr) as s:
+    with T.Solver.open(pr, "m").load() as s:
         assert s.solve(1e-5, 300) == 0
         first = s.get_info()["iterations"]
         w0 = s.residual()["worst"]
@@ -118,35 +66,35 @@ def test_continues_on_all_block_sizes(oracle, LM, LN):
 # ---- 2. already converged, no iterations, deterministic --------------------------------------------------------------------------------------
 def test_already_converged_and_no_iterations():
     pr = load_problem("fd_16x16_small")
-    with _loaded(pr) as s:
+    with T.Solver.open(pr, "m").load() as s:
         assert s.solve(1e-9, 300) == 0
         X0 = s.get_matrix()
         assert s.refine_from(1e-8, 300) == 0
         info, h = s.get_info(), s.refinement_history()
-        assert info["iterations"] == 0 and _same_bits(s.get_matrix(), X0)
+        assert info["iterations"] == 0 and same_bits(s.get_matrix(), X0)
         assert len(h) == 1 and h[0] == info["residual"] <= 1e-9 * 1.01 and len(s.bound_history()) == 0
         for it in (0, -2):
             assert T.lib.tfqmrgpuExt_refineFrom(s.handle, s.plan, 1e-12, it) == MAX_ITERATIONS
-            assert _same_bits(s.get_matrix(), X0)
+            assert same_bits(s.get_matrix(), X0)
             assert s.get_info()["iterations"] == it and len(s.bound_history()) == 0 and len(s.refinement_history()) == 0
 
 
 def test_two_calls_give_the_same_bits():
     pr = load_problem("fd_16x16_small")
-    with _loaded(pr) as s:
+    with T.Solver.open(pr, "m").load() as s:
         assert s.solve(1e-4, 300) == 0
         X0 = s.get_matrix()
         out = []
         for _ in range(2):
             s.set_matrix("X", X0)
-            assert _same_bits(s.get_matrix(), X0)
+            assert same_bits(s.get_matrix(), X0)
             st = s.refine_from(1e-9, 300)
             out.append((st,) + _results(s))
         a, b = out
         assert a[0] == b[0] == 0 and a[5]["iterations"] > 0
-        assert all(_same_bits(x, y) for x, y in zip(a[1:5], b[1:5])) and _last(a[5]) == _last(b[5])
+        assert all(same_bits(x, y) for x, y in zip(a[1:5], b[1:5])) and _last(a[5]) == _last(b[5])
         assert b[5]["flops_all"] == pytest.approx(a[5]["flops_all"] + a[5]["flops"], rel=1e-12)
-        assert not _same_bits(a[1], X0)
+        assert not same_bits(a[1], X0)
 
 
 # ---- 3. exact and zero right-hand sides ----------------------------------------------------------------------------------------------------
@@ -160,7 +108,7 @@ def test_exact_right_hand_side_keeps_its_bits():
     ptr, ind = np.arange(mb + 1), np.zeros(mb, int)
     pr = T.Problem(np.arange(mb + 1), np.arange(mb), A, ptr, ind, ptr, ind, B)
     thr = 1e-12
-    with _loaded(pr) as s:
+    with T.Solver.open(pr, "m").load() as s:
         X0 = 0.5 * B
         X0[:, :, 5] = B[:, :, 5]
         X0[:, :, 2] = B[:, :, 2]
@@ -169,14 +117,14 @@ def test_exact_right_hand_side_keeps_its_bits():
         assert s.refine_from(thr, 50) == 0
         X, h = s.get_matrix(), s.refinement_history()
         for j in (2, 5):
-            assert _same_bits(X[:, :, j], X0[:, :, j]), j
+            assert same_bits(X[:, :, j], X0[:, :, j]), j
         assert len(h) >= 2 and np.all(np.isfinite(h)) and np.all(np.isfinite(s.bound_history()))
         assert h[0] == pytest.approx(0.5, rel=1e-12) and h[-1] <= thr
         assert np.abs(X - B).max() <= 10 * thr * np.abs(B).max()
         # every right-hand side exact: converged at once, not a breakdown
         s.set_matrix("X", B)
         assert s.refine_from(thr, 50) == 0 and s.get_info()["iterations"] == 0 and s.get_info()["residual"] <= thr
-        assert _same_bits(s.get_matrix(), B.astype(X.dtype))
+        assert same_bits(s.get_matrix(), B.astype(X.dtype))
 
 
 def test_zero_right_hand_side_inside_a_block():
@@ -184,7 +132,7 @@ def test_zero_right_hand_side_inside_a_block():
     pr = PR.stencil_2d(4, 4, 4, 8, 2, seed=17, radius=2.0)
     pr.B[:, :, 5] = 0
     thr = 1e-9
-    with _loaded(pr) as s:
+    with T.Solver.open(pr, "m").load() as s:
         assert s.solve(1e-30, 2) == MAX_ITERATIONS
         X0 = s.get_matrix()
         assert np.all(X0[:, :, 5] == 0)
@@ -199,22 +147,17 @@ def test_zero_right_hand_side_inside_a_block():
 
 
 # ---- 4. energy step -------------------------------------------------------------------------------------------------------------------------
-def _diagonal_blocks(pr):
-    rows = np.repeat(np.arange(pr.mb), np.diff(pr.rowPtrA))
-    return np.flatnonzero(rows == np.asarray(pr.colIndA, dtype=np.int64) - pr.index_offset)
-
-
 @pytest.mark.parametrize("precond", [False, True])
 def test_energy_step(precond):
     """solve A, shift the diagonal blocks by 1e-3 with set_blocks('A'), refine_from: converges to the PATCHED system -- residual() reads the
     caller's A, the kept copy on the preconditioned plan, where the patch is still pending when R is formed"""
     pr = load_problem("fd_16x16_small")
     thr = 1e-9
-    diag = _diagonal_blocks(pr)
+    diag = diagonal_blocks(pr)
     assert len(diag) == pr.mb
     shifted = pr.A.copy()
     shifted[diag] += 1e-3 * np.eye(pr.LM)
-    with _loaded(pr, kind=BJ if precond else None, keep=precond) as s:
+    with T.Solver.open(pr, "m", preconditioner=BJ if precond else None, keep_operator=precond).load() as s:
         assert s.solve(thr, 500) == 0
         cold_its = s.get_info()["iterations"]
         s.set_blocks("A", diag, shifted[diag])
@@ -232,13 +175,13 @@ def test_energy_step(precond):
 
 def test_preconditioned_without_a_kept_copy_is_refused():
     pr = load_problem("fd_16x16_small")
-    with _loaded(pr, kind=BJ) as s:
+    with T.Solver.open(pr, "m", preconditioner=BJ).load() as s:
         assert s.solve(1e-9, 300) == 0
         before = _results(s)
         assert T.decode(T.lib.tfqmrgpuExt_refineFrom(s.handle, s.plan, 1e-10, 100))[::2] == (NO_IMPLEMENTATION, 0)
         assert _same_results(_results(s), before)
     # not scaled yet: R is formed from the buffer's A, then the set-up scales it
-    with _loaded(pr, kind=BJ) as s:
+    with T.Solver.open(pr, "m", preconditioner=BJ).load() as s:
         s.set_matrix("X", 0.5 * before[0])
         assert s.refine_from(1e-9, 300) == 0
         assert s.refinement_history()[0] == pytest.approx(0.5, rel=1e-6)
@@ -261,13 +204,13 @@ def test_c_solve_on_the_old_pattern_seeds_the_m_plan_on_the_grown_one():
             A[q] += 2.0 * np.eye(LM)
     B = PR.hashed_uniform(3, (1, LM, LN)) + 1j * PR.hashed_uniform(4, (1, LM, LN))
     pr = T.Problem(rpA, ciA, A, [0, 1, 2, 3, 3], [0, 0, 0], [0, 0, 1, 1, 1], [0], B)
-    with _loaded(pr, "c") as src:
+    with T.Solver.open(pr, "c").load() as src:
         assert src.solve(1e-4, 200) == 0
         coarse_its = src.get_info()["iterations"]
         grown = src.grow_problem(pr, [0])
         old = src.grow_pattern([0])[2]
         assert grown.nnzbX == 4 and list(old) == [0, 1, 2, -1]
-        with _open(grown) as s:
+        with T.Solver.open(grown, "m") as s:
             s.adopt(src, old)
             assert np.all(s.get_matrix()[3] == 0)
             assert s.refine_from(1e-9, 200) == 0
@@ -289,7 +232,7 @@ def test_cold_solve_does_not_depend_on_a_refine_in_between(name):
     pr = load_problem(name)
     runs = []
     for calls in (("solve", "solve"), ("solve", "refine_from", "solve")):
-        with _loaded(pr) as s:
+        with T.Solver.open(pr, "m").load() as s:
             sts, flops = [], []
             for what in calls:
                 sts.append(getattr(s, what)(1e-9, 300))
@@ -297,7 +240,7 @@ def test_cold_solve_does_not_depend_on_a_refine_in_between(name):
             runs.append((sts, flops) + _results(s))
     a, b = runs
     assert a[0][-1] == b[0][-1] and a[0][0] == b[0][0]
-    assert all(_same_bits(x, y) for x, y in zip(a[2:6], b[2:6]))
+    assert all(same_bits(x, y) for x, y in zip(a[2:6], b[2:6]))
     assert _last(a[6]) == _last(b[6])
     assert a[6]["flops_all"] == pytest.approx(sum(a[1]), rel=1e-12) and b[6]["flops_all"] == pytest.approx(sum(b[1]), rel=1e-12)
 
@@ -310,13 +253,13 @@ def test_refine_from_teaches_the_plan_no_float_floor():
     zero = np.zeros((pr.nnzbX, pr.LM, pr.LN), complex)
     runs = {}
     for calls in (("solve",), ("solve", "solve"), ("refine_from", "solve")):
-        with _loaded(pr) as s:
+        with T.Solver.open(pr, "m").load() as s:
             s.set_matrix("X", zero)
             sts = [getattr(s, what)(1e-9, 300) for what in calls]
             runs[calls] = (sts[-1],) + _results(s)
     first, second, behind = runs[("solve",)], runs[("solve", "solve")], runs[("refine_from", "solve")]
-    assert not (_same_bits(first[2], second[2]) and _same_bits(first[3], second[3])), "this fixture no longer learns a floor: the test shows nothing"
-    assert first[0] == behind[0] and all(_same_bits(x, y) for x, y in zip(first[1:5], behind[1:5])) and _last(first[5]) == _last(behind[5])
+    assert not (same_bits(first[2], second[2]) and same_bits(first[3], second[3])), "this fixture no longer learns a floor: the test shows nothing"
+    assert first[0] == behind[0] and all(same_bits(x, y) for x, y in zip(first[1:5], behind[1:5])) and _last(first[5]) == _last(behind[5])
 
 
 # ---- 7. 'z' / 'c' forward ---------------------------------------------------------------------------------------------------------------------
@@ -325,22 +268,22 @@ def test_z_and_c_plans_forward_to_solve_from(name, prec):
     pr = load_problem(name)
     out = []
     for what in ("solve_from", "refine_from"):
-        with _loaded(pr, prec) as s:
+        with T.Solver.open(pr, prec).load() as s:
             assert s.solve(pr.tolerance, 3) == MAX_ITERATIONS
             X0 = s.get_matrix()
             st = getattr(s, what)(pr.tolerance, 6)
             out.append((st, s.get_matrix(), s.bound_history(), s.get_info(), X0))
     a, b = out
-    assert _same_bits(a[4], b[4])
-    assert a[0] == b[0] and _same_bits(a[1], b[1]) and _same_bits(a[2], b[2]) and a[3] == b[3]
-    assert len(a[2]) > 0 and not _same_bits(a[1], a[4])
+    assert same_bits(a[4], b[4])
+    assert a[0] == b[0] and same_bits(a[1], b[1]) and same_bits(a[2], b[2]) and a[3] == b[3]
+    assert len(a[2]) > 0 and not same_bits(a[1], a[4])
 
 
 # ---- 8. statuses that need a device ----------------------------------------------------------------------------------------------------------
 def test_statuses_change_nothing():
     pr = load_problem("fd_16x16_small")
     raw = lambda s, it=100: T.lib.tfqmrgpuExt_refineFrom(s.handle, s.plan, 1e-10, it)      # noqa: E731
-    with _loaded(pr) as s:
+    with T.Solver.open(pr, "m").load() as s:
         assert s.solve(1e-9, 300) == 0
         before = _results(s)
         # a user-defined operator: refused before A is looked at
@@ -357,13 +300,13 @@ def test_statuses_change_nothing():
         assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, C.cast(None, T.REDUCE_CB), None) == 0
         assert _same_results(_results(s), before)
         # ... and the plan still solves as it did
-        assert s.refine_from(1e-8, 300) == 0 and s.get_info()["iterations"] == 0 and _same_bits(s.get_matrix(), before[0])
+        assert s.refine_from(1e-8, 300) == 0 and s.get_info()["iterations"] == 0 and same_bits(s.get_matrix(), before[0])
     # A has never been set on this buffer
-    with _open(pr) as s:
+    with T.Solver.open(pr, "m") as s:
         s.set_matrix("B", pr.B)
         s.set_matrix("X", before[0])
         info0 = s.get_info()
         assert T.decode(raw(s))[::2] == (UNDOCUMENTED, ord("A"))
-        assert _same_bits(s.get_matrix(), before[0]) and s.get_info() == info0 and len(s.refinement_history()) == 0
-    with _open(pr, buffer=False) as s:
+        assert same_bits(s.get_matrix(), before[0]) and s.get_info() == info0 and len(s.refinement_history()) == 0
+    with T.Solver.open(pr, "m", buffer=False) as s:
         assert T.decode(raw(s))[::2] == (POINTER_INVALID, 0)

@@ -10,6 +10,7 @@ import precond_ref as PC
 import residual_ref as RR
 import tfqmrgpu_amd as T
 from conftest import load_problem
+from helpers import random_x
 from tfqmrgpu_amd import problems as PR
 from tolerances import Z_TOL
 
@@ -20,25 +21,6 @@ SHAPES = [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8,
 NO_INFO_PASSED, POINTER_INVALID, UNDOCUMENTED, NO_IMPLEMENTATION = 3, 7, 14, 19
 BJ = T.PRECOND_BLOCK_JACOBI
 SENTINEL = -12345.0
-
-
-def _open(pr, prec, kind=None, keep=False, shadow=T.SHADOW_HASH, buffer=True):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    s.set_shadow_mode(shadow)
-    if buffer:
-        s.set_buffer(nbytes=nbytes)
-    return s
-
-
-def _random_x(pr, seed):
-    shape = (pr.nnzbX, pr.LM, pr.LN)
-    return PR.hashed_uniform(seed, shape) - 0.5 + 1j * (PR.hashed_uniform(seed + 1, shape) - 0.5)
 
 
 def _compare(got, ref, what=""):
@@ -61,7 +43,7 @@ def _compare_worst(got_worst, ref, what=""):
 
 def _graded(oracle, pr, prec, X, seed_note=""):
     """set A, B and a caller's X on a fresh plan, do not solve, compare with numpy on the data as the plan stores it"""
-    with _open(pr, prec) as s:
+    with T.Solver.open(pr, prec) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         s.set_matrix("X", X)
@@ -83,7 +65,7 @@ def _graded(oracle, pr, prec, X, seed_note=""):
 @pytest.mark.parametrize("LM,LN", SHAPES)
 def test_every_shape_and_precision(oracle, LM, LN, prec):
     pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=100 * LM + LN)
-    _graded(oracle, pr, prec, _random_x(pr, 7 * LM + LN))
+    _graded(oracle, pr, prec, random_x(pr, 7 * LM + LN))
 
 
 @pytest.mark.parametrize("LM,LN,prec", [(4, 5, "z"), (8, 8, "c"), (16, 16, "z"), (16, 32, "m")])
@@ -93,7 +75,7 @@ def test_ragged_columns_and_index_offset(oracle, LM, LN, prec):
     assert len(set(np.bincount(pr.colIndX))) == 3
     one = T.Problem(pr.rowPtrA + 1, pr.colIndA + 1, pr.A, pr.rowPtrX + 1, pr.colIndX + 1, pr.rowPtrB + 1, pr.colIndB + 1, pr.B, None,
                     pr.tolerance, 1)
-    got = _graded(oracle, one, prec, _random_x(pr, 3))
+    got = _graded(oracle, one, prec, random_x(pr, 3))
     assert list(got["columns"]) == [1, 2, 3]
 
 
@@ -104,14 +86,14 @@ def test_long_columns_of_several_chunks(oracle, prec):
     cutChunks), so every column is cut into 25 chunks or more: the chunk records and the order of k_residual_col"""
     pr = PR.stencil_2d(40, 40, 4, 4, ncols=2, seed=40)
     assert np.bincount(pr.colIndX).min() == 1600 and 1600 * 2 * 4 * 4 * 4 > 16 * 1024
-    _graded(oracle, pr, prec, _random_x(pr, 41))
+    _graded(oracle, pr, prec, random_x(pr, 41))
 
 
 # ---- 3. the golden fixtures, after a solve -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["fd_4x4_2d", "dense_random_rect", "julia_kat", "fd_16x16_small"])
 def test_fixtures_after_a_solve(oracle, name):
     pr = load_problem(name)
-    with _open(pr, "z", shadow=T.SHADOW_GLIBC_RAND) as s:
+    with T.Solver.open(pr, "z", shadow_mode=T.SHADOW_GLIBC_RAND) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         st = s.solve(1e-9, 2000)
@@ -136,7 +118,7 @@ def test_float_plan_graded_in_double(oracle):
     """fd_16x16_small in 'c', iterated to the float floor: the call's double sums over the float data against numpy's.
     How far getInfo's float probe is from it is recorded, not asserted."""
     pr = load_problem("fd_16x16_small")
-    with _open(pr, "c") as s:
+    with T.Solver.open(pr, "c") as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         st = s.solve(1e-9, 300)                                      # out of reach in float: the solve runs into its floor
@@ -156,7 +138,7 @@ def test_preconditioned_plan(oracle, prec, LM):
     pr = PR.stencil_2d(4, 4, LM, LM, 2, seed=LM)
     n_cols = 2
     # without the kept copy the caller's A is gone after the solve: status 19, nothing written
-    with _open(pr, prec, kind=BJ) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 200) == 0
@@ -167,7 +149,7 @@ def test_preconditioned_plan(oracle, prec, LM):
         assert T.decode(st)[::2] == (NO_IMPLEMENTATION, 0)
         assert (r2 == SENTINEL).all() and (b2 == SENTINEL).all() and (cols == -77).all() and worst.value == SENTINEL
     # with it: the caller's A and the back-transformed X
-    with _open(pr, prec, kind=BJ, keep=True) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         s.set_matrix("X", np.zeros((pr.nnzbX, LM, LM), np.complex128))
@@ -200,7 +182,7 @@ def test_non_destructive_and_deterministic(prec, LM, LN):
     tol = 1e-9 if prec == "z" else 1e-4
 
     def run(with_call):
-        with _open(pr, prec) as s:
+        with T.Solver.open(pr, prec) as s:
             s.set_matrix("A", pr.A)
             s.set_matrix("B", pr.B)
             assert s.solve(tol, 200) == 0
@@ -231,7 +213,7 @@ def test_zero_right_hand_side(oracle):
     # (the problem of tests/test_gpu_parity.py: test_edge_zero_right_hand_side_column)
     pr = PR.stencil_2d(4, 4, 4, 8, 2, seed=17, radius=2.0)
     pr.B[:, :, 5] = 0
-    with _open(pr, "z", shadow=T.SHADOW_GLIBC_RAND) as s:
+    with T.Solver.open(pr, "z", shadow_mode=T.SHADOW_GLIBC_RAND) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         s.solve(1e-9, 100)
@@ -242,20 +224,20 @@ def test_zero_right_hand_side(oracle):
         assert np.all(np.isfinite(got["relative"][:, keep]))
         assert got["worst"] == got["relative"][:, keep].max()        # NaN entries are left out
         # X = 0 there: r = b = 0 exactly
-        X = _random_x(pr, 5)
+        X = random_x(pr, 5)
         X[:, :, 5] = 0
         s.set_matrix("X", X)
         got = s.residual()
         assert np.all(got["residual2"][:, 5] == 0) and np.all(np.isnan(got["relative"][:, 5]))
         assert np.isfinite(got["worst"]) and got["worst"] == got["relative"][:, keep].max()
         # a non-zero X there: r > 0 = b
-        s.set_matrix("X", _random_x(pr, 6))
+        s.set_matrix("X", random_x(pr, 6))
         got = s.residual()
         assert np.all(np.isposinf(got["relative"][:, 5])) and np.isposinf(got["worst"])
-        _compare(got, RR.residual(oracle, pr, pr.A, _random_x(pr, 6)), "zero right-hand side")
+        _compare(got, RR.residual(oracle, pr, pr.A, random_x(pr, 6)), "zero right-hand side")
     # every right-hand side zero: worst is NaN only then
     pr.B[:] = 0
-    with _open(pr, "z") as s:
+    with T.Solver.open(pr, "z") as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         s.set_matrix("X", np.zeros((pr.nnzbX, 4, 8), np.complex128))
@@ -277,9 +259,9 @@ def test_statuses_change_nothing():
         assert (r2 == SENTINEL).all() and (b2 == SENTINEL).all() and (cols == -77).all() and worst.value == SENTINEL
         return st
 
-    with _open(pr, "z", buffer=False) as s:                         # no buffer
+    with T.Solver.open(pr, "z", buffer=False) as s:                         # no buffer
         assert T.decode(call(s))[::2] == (POINTER_INVALID, 0)
-    with _open(pr, "z") as s:                                       # no A
+    with T.Solver.open(pr, "z") as s:                                       # no A
         s.set_matrix("B", pr.B)
         assert T.decode(call(s))[::2] == (UNDOCUMENTED, ord("A"))
         s.set_matrix("A", pr.A)

@@ -10,6 +10,7 @@ import residual_ref as RR
 import tfqmrgpu_amd as T
 import warm_ref as WR
 from conftest import load_problem
+from helpers import diagonal_blocks, same_bits
 from tfqmrgpu_amd import problems as PR
 from tolerances import C_TOL
 
@@ -20,35 +21,6 @@ BJ = T.PRECOND_BLOCK_JACOBI
 # the smallest shapes at which each path can go wrong: LDS-patch shapes, interleaved MFMA shapes, the quad order (two), LM != LN
 FIXTURES = ["fd_4x4_2d", "fd_16x16_small", "fd_8x8_3d", "stencil_8x32", "dense_random_rect"]
 X_TOL_Z = 1e-7          # cold parity of 'z' (tests/test_gpu_parity.py); 'c': tests/tolerances.py C_TOL[name]["x"] where the table has the fixture
-
-
-def _open(pr, prec, kind=None, keep=False, shadow=T.SHADOW_HASH, buffer=True):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    s.set_shadow_mode(shadow)
-    if buffer:
-        s.set_buffer(nbytes=nbytes)
-    return s
-
-
-def _loaded(pr, prec, **kw):
-    s = _open(pr, prec, **kw)
-    s.set_matrix("A", pr.A)
-    s.set_matrix("B", pr.B)
-    return s
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 # ---- 1. parity with the oracle at a fixed iteration count -----------------------------------------------------------------------------
@@ -63,13 +35,13 @@ def test_parity_with_the_oracle(oracle, name, prec):
     stencil_8x32 2.8e-7, 2.8e-7 | 2.7e-7, 2.7e-7; dense_random_rect 8.3e-7, 1.5e-6 | 2.1e-6, 1.1e-6.  'z': at most 1.0e-11 everywhere."""
     pr = load_problem(name)
     A, B = RR.stored(pr.A, prec), RR.stored(pr.B, prec)
-    with _loaded(pr, prec, shadow=T.SHADOW_GLIBC_RAND) as s:
+    with T.Solver.open(pr, prec, shadow_mode=T.SHADOW_GLIBC_RAND).load() as s:
         assert s.solve(1e-30, 3) == MAX_ITERATIONS
         X0 = s.get_matrix()
         for k in (1, 4):
             if k > 1:
                 s.set_matrix("X", X0)
-                assert _same_bits(s.get_matrix(), X0)
+                assert same_bits(s.get_matrix(), X0)
             assert s.solve_from(1e-30, k) == MAX_ITERATIONS
             X = s.get_matrix()
             assert len(s.bound_history()) == k and np.all(np.isfinite(s.bound_history()))
@@ -103,7 +75,7 @@ def test_continues_a_solve_that_ran_out_of_iterations(prec, thr, margin):
     the same margin of 2 is kept for 'c'."""
     pr = load_problem("fd_16x16_small")
     N = 500
-    with _loaded(pr, prec) as s:
+    with T.Solver.open(pr, prec).load() as s:
         assert s.solve(thr, N) == 0
         k2 = s.get_info()["iterations"]
         cold = s.residual()["worst"]
@@ -125,7 +97,7 @@ def test_continues_a_solve_that_ran_out_of_iterations(prec, thr, margin):
 @pytest.mark.parametrize("prec,thr", [("z", 1e-9), ("c", 1e-4)])
 def test_already_converged(prec, thr):
     pr = load_problem("fd_16x16_small")
-    with _loaded(pr, prec) as s:
+    with T.Solver.open(pr, prec).load() as s:
         assert s.solve(thr, 500) == 0
         X0 = s.get_matrix()
         assert s.solve_from(10 * thr, 500) == 0
@@ -142,7 +114,7 @@ def test_zero_right_hand_side_inside_a_block(prec):
     pr = PR.stencil_2d(4, 4, 4, 8, 2, seed=17, radius=2.0)
     pr.B[:, :, 5] = 0
     thr = 1e-9 if prec == "z" else 1e-4
-    with _loaded(pr, prec) as s:
+    with T.Solver.open(pr, prec).load() as s:
         assert s.solve(1e-30, 2) == MAX_ITERATIONS
         X0 = s.get_matrix()
         assert np.all(X0[:, :, 5] == 0)
@@ -165,7 +137,7 @@ def test_exact_right_hand_side_keeps_its_bits(prec):
     ptr, ind = np.arange(mb + 1), np.zeros(mb, int)
     pr = T.Problem(np.arange(mb + 1), np.arange(mb), A, ptr, ind, ptr, ind, B)
     thr = 1e-12 if prec == "z" else 1e-5
-    with _loaded(pr, prec) as s:
+    with T.Solver.open(pr, prec).load() as s:
         Bs = RR.stored(B, prec)
         X0 = 0.5 * Bs
         X0[:, :, 5] = Bs[:, :, 5]
@@ -175,32 +147,27 @@ def test_exact_right_hand_side_keeps_its_bits(prec):
         assert s.solve_from(thr, 50) == 0
         X = s.get_matrix()
         for j in (2, 5):
-            assert _same_bits(X[:, :, j], X0[:, :, j]), j
+            assert same_bits(X[:, :, j], X0[:, :, j]), j
         assert np.all(np.isfinite(s.bound_history()))
         assert np.abs(X - Bs).max() <= 10 * thr * np.abs(Bs).max()
         # every right-hand side exact: converged at once, not a breakdown
         s.set_matrix("X", Bs)
         assert s.solve_from(thr, 50) == 0 and s.get_info()["iterations"] == 1
-        assert _same_bits(s.get_matrix(), RR.stored(Bs, prec).astype(X.dtype))
+        assert same_bits(s.get_matrix(), RR.stored(Bs, prec).astype(X.dtype))
 
 
 # ---- 5. energy step -------------------------------------------------------------------------------------------------------------------------
-def _diagonal_blocks(pr):
-    rows = np.repeat(np.arange(pr.mb), np.diff(pr.rowPtrA))
-    return np.flatnonzero(rows == np.asarray(pr.colIndA, dtype=np.int64) - pr.index_offset)
-
-
 @pytest.mark.parametrize("prec,thr", [("z", 1e-9), ("c", 1e-4)])
 @pytest.mark.parametrize("precond", [False, True])
 def test_energy_step(oracle, prec, thr, precond):
     """solve A, shift the diagonal blocks by 1e-3 with set_blocks('A'), solve_from: converges to the PATCHED system -- residual() reads
     the caller's A, the kept copy on the preconditioned plan, where the patch is still pending when R is formed"""
     pr = load_problem("fd_16x16_small")
-    diag = _diagonal_blocks(pr)
+    diag = diagonal_blocks(pr)
     assert len(diag) == pr.mb
     shifted = pr.A.copy()
     shifted[diag] += 1e-3 * np.eye(pr.LM)
-    with _loaded(pr, prec, kind=BJ if precond else None, keep=precond) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ if precond else None, keep_operator=precond).load() as s:
         assert s.solve(thr, 500) == 0
         cold_its = s.get_info()["iterations"]
         s.set_blocks("A", diag, shifted[diag])
@@ -217,18 +184,18 @@ def test_energy_step(oracle, prec, thr, precond):
 
 def test_preconditioned_without_a_kept_copy_is_refused():
     pr = load_problem("fd_16x16_small")
-    with _loaded(pr, "z", kind=BJ) as s:
+    with T.Solver.open(pr, "z", preconditioner=BJ).load() as s:
         assert s.solve(1e-9, 3) == MAX_ITERATIONS
         X0, h0, info0 = s.get_matrix(), s.bound_history(), s.get_info()
         assert T.decode(T.lib.tfqmrgpuExt_solveFrom(s.handle, s.plan, 1e-9, 100))[::2] == (NO_IMPLEMENTATION, 0)
-        assert _same_bits(s.get_matrix(), X0) and np.array_equal(s.bound_history(), h0) and s.get_info() == info0
+        assert same_bits(s.get_matrix(), X0) and np.array_equal(s.bound_history(), h0) and s.get_info() == info0
     # not scaled yet: R is formed from the buffer's A, then the set-up scales it
-    with _loaded(pr, "z", kind=BJ) as s:
+    with T.Solver.open(pr, "z", preconditioner=BJ).load() as s:
         s.set_matrix("X", X0)
         assert s.solve_from(1e-9, 100) == 0
         assert T.decode(T.lib.tfqmrgpuExt_residual(s.handle, s.plan, None, None, None, C.byref(C.c_double(0))))[0] == NO_IMPLEMENTATION
         X = s.get_matrix()
-    with _loaded(pr, "z") as s:
+    with T.Solver.open(pr, "z").load() as s:
         s.set_matrix("X", X)
         assert s.residual()["worst"] <= 1.01e-9
 
@@ -248,13 +215,13 @@ def test_grown_pattern_end_to_end():
             A[q] += 2.0 * np.eye(LM)
     B = PR.hashed_uniform(3, (1, LM, LN)) + 1j * PR.hashed_uniform(4, (1, LM, LN))
     pr = T.Problem(rpA, ciA, A, [0, 1, 2, 3, 3], [0, 0, 0], [0, 0, 1, 1, 1], [0], B)
-    with _loaded(pr, "z") as s:
+    with T.Solver.open(pr, "z").load() as s:
         assert s.solve(1e-9, 200) == 0
         cold_its = s.get_info()["iterations"]
         pr.X = s.get_matrix()
         grown = s.grow_problem(pr, [0])
     assert grown.nnzbX == 4 and np.all(grown.X[3] == 0) and np.array_equal(grown.X[:3], pr.X)
-    with _loaded(grown, "z") as s:
+    with T.Solver.open(grown, "z").load() as s:
         s.set_matrix("X", grown.X)
         assert s.solve_from(1e-9, 200) == 0
         assert np.all(s.truncation_leak()["leak2"] == 0.0)
@@ -267,7 +234,7 @@ def test_grown_pattern_end_to_end():
 @pytest.mark.parametrize("name,prec", [("fd_16x16_small", "z"), ("fd_4x4_2d", "c"), ("stencil_8x32", "z")])
 def test_cold_solve_is_bit_for_bit_the_solve_it_was(name, prec):
     pr = load_problem(name)
-    with _loaded(pr, prec) as s:
+    with T.Solver.open(pr, prec).load() as s:
         runs = []
         for what in ("solve", "solve_from", "solve"):
             st = getattr(s, what)(pr.tolerance, 9)
@@ -275,9 +242,9 @@ def test_cold_solve_is_bit_for_bit_the_solve_it_was(name, prec):
             runs.append((st, s.get_matrix(), s.bound_history(), info["residual"], info["iterations"], info["flops"],
                          {w: s.get_work_vector(w) for w in (4, 5, 6, 7, 8, 9)}))
         a, b = runs[0], runs[2]
-        assert a[0] == b[0] and _same_bits(a[1], b[1]) and _same_bits(a[2], b[2]) and a[3:6] == b[3:6]
+        assert a[0] == b[0] and same_bits(a[1], b[1]) and same_bits(a[2], b[2]) and a[3:6] == b[3:6]
         for w in a[6]:
-            assert _same_bits(a[6][w], b[6][w]), w
+            assert same_bits(a[6][w], b[6][w]), w
 
 
 # ---- 8. statuses that need a device -----------------------------------------------------------------------------------------------------------
@@ -285,12 +252,12 @@ def test_statuses_change_nothing():
     pr = load_problem("fd_16x16_small")
     raw = lambda s, it=100: T.lib.tfqmrgpuExt_solveFrom(s.handle, s.plan, 1e-9, it)      # noqa: E731
     # 'm': refused, X and the results of the last solve as they were
-    with _loaded(pr, "m") as s:
+    with T.Solver.open(pr, "m").load() as s:
         assert s.solve(1e-9, 500) == 0
         X0, info0 = s.get_matrix(), s.get_info()
         assert T.decode(raw(s))[::2] == (NO_IMPLEMENTATION, 0)
-        assert _same_bits(s.get_matrix(), X0) and s.get_info() == info0
-    with _loaded(pr, "z") as s:
+        assert same_bits(s.get_matrix(), X0) and s.get_info() == info0
+    with T.Solver.open(pr, "z").load() as s:
         assert s.solve(1e-9, 3) == MAX_ITERATIONS
         X0, h0 = s.get_matrix(), s.bound_history()
         # a user-defined operator: refused before A is looked at
@@ -304,20 +271,20 @@ def test_statuses_change_nothing():
         assert T.decode(raw(s))[::2] == (NO_IMPLEMENTATION, 0)
         assert len(calls) == 1 and calls[0][1] == 1.0
         assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, C.cast(None, T.REDUCE_CB), None) == 0
-        assert _same_bits(s.get_matrix(), X0) and np.array_equal(s.bound_history(), h0)
+        assert same_bits(s.get_matrix(), X0) and np.array_equal(s.bound_history(), h0)
         # no iteration at all: X0 is the answer, bit for bit; the status of a cold solve without an iteration
         for it in (0, -2):
             assert s.solve(1e-9, it) == MAX_ITERATIONS      # (the cold solve: X = 0)
             s.set_matrix("X", X0)
             assert raw(s, it) == MAX_ITERATIONS
-            assert _same_bits(s.get_matrix(), X0) and len(s.bound_history()) == 0 and s.get_info()["iterations"] == it
+            assert same_bits(s.get_matrix(), X0) and len(s.bound_history()) == 0 and s.get_info()["iterations"] == it
     # A has never been set on this buffer
-    with _open(pr, "z") as s:
+    with T.Solver.open(pr, "z") as s:
         s.set_matrix("B", pr.B)
         s.set_matrix("X", X0)
         assert T.decode(raw(s))[::2] == (UNDOCUMENTED, ord("A"))
-        assert _same_bits(s.get_matrix(), X0)
-    with _open(pr, "z", buffer=False) as s:
+        assert same_bits(s.get_matrix(), X0)
+    with T.Solver.open(pr, "z", buffer=False) as s:
         assert T.decode(raw(s))[::2] == (POINTER_INVALID, 0)
 
 
@@ -325,7 +292,7 @@ def test_statuses_change_nothing():
 @pytest.mark.parametrize("name,prec", [("fd_16x16_small", "z"), ("fd_8x8_3d", "c"), ("dense_random_rect", "z")])
 def test_two_calls_give_the_same_bits(name, prec):
     pr = load_problem(name)
-    with _loaded(pr, prec) as s:
+    with T.Solver.open(pr, prec).load() as s:
         assert s.solve(pr.tolerance, 3) == MAX_ITERATIONS
         X0 = s.get_matrix()
         out = []
@@ -333,5 +300,5 @@ def test_two_calls_give_the_same_bits(name, prec):
             s.set_matrix("X", X0)
             st = s.solve_from(pr.tolerance, 6)
             out.append((st, s.get_matrix(), s.bound_history(), s.get_info()["residual"]))
-        assert out[0][0] == out[1][0] and _same_bits(out[0][1], out[1][1]) and _same_bits(out[0][2], out[1][2]) and out[0][3] == out[1][3]
-        assert not _same_bits(out[0][1], X0)
+        assert out[0][0] == out[1][0] and same_bits(out[0][1], out[1][1]) and same_bits(out[0][2], out[1][2]) and out[0][3] == out[1][3]
+        assert not same_bits(out[0][1], X0)

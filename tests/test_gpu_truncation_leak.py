@@ -11,7 +11,8 @@ import leak_ref as LR
 import precond_ref as PC
 import residual_ref as RR
 import tfqmrgpu_amd as T
-from conftest import load_problem
+from conftest import load_problem, offset1
+from helpers import random_x
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -21,30 +22,6 @@ SHAPES = [(4, 4), (4, 5), (4, 8), (4, 32), (8, 8), (8, 9), (8, 10), (8, 32), (8,
 NO_INFO_PASSED, POINTER_INVALID, UNDOCUMENTED, NO_IMPLEMENTATION = 3, 7, 14, 19
 BJ = T.PRECOND_BLOCK_JACOBI
 SENTINEL = -12345.0
-
-
-def _open(pr, prec, kind=None, keep=False, shadow=T.SHADOW_HASH, buffer=True):
-    s = T.Solver()
-    s.create_plan(pr)
-    nbytes = s.buffer_size(pr.LM, pr.LN, prec)
-    if kind is not None:
-        s.set_preconditioner(kind)
-    if keep:
-        s.keep_operator(True)
-    s.set_shadow_mode(shadow)
-    if buffer:
-        s.set_buffer(nbytes=nbytes)
-    return s
-
-
-def _random_x(pr, seed):
-    shape = (pr.nnzbX, pr.LM, pr.LN)
-    return PR.hashed_uniform(seed, shape) - 0.5 + 1j * (PR.hashed_uniform(seed + 1, shape) - 0.5)
-
-
-def _offset1(pr):
-    return T.Problem(pr.rowPtrA + 1, pr.colIndA + 1, pr.A, pr.rowPtrX + 1, pr.colIndX + 1, pr.rowPtrB + 1, pr.colIndB + 1, pr.B, None,
-                     pr.tolerance, 1)
 
 
 def _compare(got, ref, what=""):
@@ -63,7 +40,7 @@ def _compare(got, ref, what=""):
 
 def _graded(pr, prec, X, what=""):
     """set A, B and a caller's X on a fresh plan, do not solve, compare with numpy on the data as the plan stores it"""
-    with _open(pr, prec) as s:
+    with T.Solver.open(pr, prec) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         s.set_matrix("X", X)
@@ -83,7 +60,7 @@ def _graded(pr, prec, X, what=""):
 def test_every_shape_and_precision(LM, LN, prec):
     """one full column -- no position, no unit, exactly 0.0 -- and two truncated ones"""
     pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=100 * LM + LN, radius=[None, 1.1, 2.3])
-    got, ref = _graded(pr, prec, _random_x(pr, 7 * LM + LN))
+    got, ref = _graded(pr, prec, random_x(pr, 7 * LM + LN))
     assert list(ref["blocks_per_column"] > 0) == [False, True, True]
     assert np.all(got["leak2"][0] == 0.0) and np.all(got["leak2"][1:] > 0)
 
@@ -92,10 +69,10 @@ def test_every_shape_and_precision(LM, LN, prec):
 @pytest.mark.parametrize("LM,LN,prec", [(4, 5, "z"), (8, 8, "c"), (16, 16, "z"), (16, 32, "m")])
 def test_index_offset(LM, LN, prec):
     pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=LM + LN, radius=[None, 1.1, 2.3])
-    got, _ = _graded(_offset1(pr), prec, _random_x(pr, 3), " 1-based")
+    got, _ = _graded(offset1(pr), prec, random_x(pr, 3), " 1-based")
     assert list(got["columns"]) == [1, 2, 3]
     assert np.all(got["leak2"][0] == 0.0) and np.all(got["leak2"][1:] > 0)
-    zero, _ = _graded(pr, prec, _random_x(pr, 3))
+    zero, _ = _graded(pr, prec, random_x(pr, 3))
     assert np.array_equal(zero["leak2"], got["leak2"])               # the same listing, the same sums, the same bits
 
 
@@ -106,7 +83,7 @@ def test_long_shells_of_several_units(prec):
     rings of 92 leak positions with 272 products each (184 and 544 in all; the generator's sources sit on the edge, 190 positions is the
     most two columns give).  A unit takes at most 64 products at 4 x 4: several units per column, added in order by k_leak_col"""
     pr = PR.stencil_2d(40, 40, 4, 4, ncols=2, seed=40, radius=24.5, points=13)
-    got, ref = _graded(pr, prec, _random_x(pr, 41))
+    got, ref = _graded(pr, prec, random_x(pr, 41))
     assert ref["n_leak_blocks"] >= 180 and ref["n_leak_pairs"] >= 500
     assert np.all(got["units"] > 1), got["units"]
     assert np.all(got["units"] >= -(-ref["pairs_per_column"] // 64))
@@ -116,14 +93,14 @@ def test_long_shells_of_several_units(prec):
 @pytest.mark.parametrize("prec,LM,LN", [("z", 16, 16), ("c", 4, 8)])
 def test_sum_rule_on_the_device(oracle, prec, LM, LN):
     pr = PR.stencil_2d(5, 4, LM, LN, ncols=3, seed=LM + 3 * LN, radius=[1.5, 2.2, 1.1])
-    X = _random_x(pr, 9)
+    X = random_x(pr, 9)
     twin, Xp = LR.padded(pr, X)
-    with _open(pr, prec) as s:
+    with T.Solver.open(pr, prec) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         s.set_matrix("X", X)
         res, leak = s.residual(), s.truncation_leak()
-    with _open(twin, prec) as s:
+    with T.Solver.open(twin, prec) as s:
         s.set_matrix("A", twin.A)
         s.set_matrix("B", twin.B)
         s.set_matrix("X", Xp)
@@ -146,7 +123,7 @@ def test_fixtures_after_a_solve(name):
     """fd_16x16_small: X is truncated around its sources, 64 leak positions with 96 products.  dense_random_rect: every block row in
     every block column of X -- full columns, so its leak follows from the pattern: no position, exactly 0.0"""
     pr = load_problem(name)
-    with _open(pr, "z", shadow=T.SHADOW_GLIBC_RAND) as s:
+    with T.Solver.open(pr, "z", shadow_mode=T.SHADOW_GLIBC_RAND) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 2000) == 0
@@ -170,7 +147,7 @@ def test_preconditioned_plan(prec, LM):
     pr = PR.stencil_2d(4, 4, LM, LM, 2, seed=LM, radius=[1.5, 2.1])
     n_cols = 2
     # without the kept copy the caller's A is gone after the first solve: status 19, nothing written; the counts need no A
-    with _open(pr, prec, kind=BJ) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         before = s.truncation_leak()                                 # not scaled yet: the buffer's A
@@ -183,7 +160,7 @@ def test_preconditioned_plan(prec, LM):
         assert (leak2 == SENTINEL).all() and (cols == -77).all() and nb.value == 777 and npairs.value == 777
         assert s.leak_counts() == (before["n_leak_blocks"], before["n_leak_pairs"])
     # with it: the caller's A and the back-transformed X
-    with _open(pr, prec, kind=BJ, keep=True) as s:
+    with T.Solver.open(pr, prec, preconditioner=BJ, keep_operator=True) as s:
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
         assert s.solve(1e-9, 200) == 0
@@ -208,7 +185,7 @@ def test_non_destructive_and_deterministic(prec, LM, LN):
     tol = 1e-9 if prec == "z" else 1e-4
 
     def run(with_call):
-        with _open(pr, prec) as s:
+        with T.Solver.open(pr, prec) as s:
             s.set_matrix("A", pr.A)
             s.set_matrix("B", pr.B)
             assert s.solve(tol, 200) == 0
@@ -255,12 +232,12 @@ def test_statuses_change_nothing():
             assert (leak2 == SENTINEL).all() and (cols == -77).all() and nb.value == 777 and npairs.value == 777
         return st
 
-    with _open(pr, "z", buffer=False) as s:                         # no buffer
+    with T.Solver.open(pr, "z", buffer=False) as s:                         # no buffer
         assert call(s, null=True) == NO_INFO_PASSED                 # ... comes behind the look at the outputs
         assert T.decode(call(s))[::2] == (POINTER_INVALID, 0)
         call(s, counts_only=True)                                   # the counts need neither a buffer nor A
         assert s.leak_counts() == want
-    with _open(pr, "z") as s:                                       # no A
+    with T.Solver.open(pr, "z") as s:                                       # no A
         s.set_matrix("B", pr.B)
         x_before = s.get_work_vector(1)
         s.set_operator(lambda *a: 0.0)                              # a user-defined operator comes before the missing A

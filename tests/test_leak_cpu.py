@@ -11,6 +11,8 @@ import pytest
 import leak_ref as LR
 import residual_ref as RR
 import tfqmrgpu_amd as T
+from conftest import offset1
+from helpers import random_x
 from tfqmrgpu_amd import problems as PR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,21 +33,11 @@ def _problem(name):
     return PR.stencil_2d(kw.pop("nx"), kw.pop("ny"), kw.pop("LM"), kw.pop("LN"), seed=31, **kw)
 
 
-def _random_x(pr, seed):
-    shape = (pr.nnzbX, pr.LM, pr.LN)
-    return PR.hashed_uniform(seed, shape) - 0.5 + 1j * (PR.hashed_uniform(seed + 1, shape) - 0.5)
-
-
-def _offset1(pr):
-    return T.Problem(pr.rowPtrA + 1, pr.colIndA + 1, pr.A, pr.rowPtrX + 1, pr.colIndX + 1, pr.rowPtrB + 1, pr.colIndB + 1, pr.B, None,
-                     pr.tolerance, 1)
-
-
 # ---- the reference on cases that can be derived by hand ------------------------------------------------------------------------------
 def test_full_columns_leak_nothing():
     pr = _problem("full columns")
     assert LR.counts(pr) == (0, 0)
-    ref = LR.leak(pr, pr.A, _random_x(pr, 1))
+    ref = LR.leak(pr, pr.A, random_x(pr, 1))
     assert (ref["n_leak_blocks"], ref["n_leak_pairs"]) == (0, 0)
     assert np.all(ref["leak2"] == 0.0) and np.all(ref["bound"] == 0.0)
 
@@ -56,7 +48,7 @@ def test_chain_leaks_two_positions_per_column():
     pr = _problem("chain")
     assert np.array_equal(np.bincount(pr.colIndX), [3, 3, 3])
     assert LR.counts(pr) == (6, 6)
-    X = _random_x(pr, 2)
+    X = random_x(pr, 2)
     ref = LR.leak(pr, pr.A, X)
     assert list(ref["blocks_per_column"]) == [2, 2, 2] and list(ref["pairs_per_column"]) == [2, 2, 2]
     # ... and the value, by hand, for the first column: source row 2, rows 1 2 3 held, rows 0 and 4 reached
@@ -71,7 +63,7 @@ def test_chain_leaks_two_positions_per_column():
 @pytest.mark.parametrize("name", list(CASES))
 def test_counts_agree_between_sets_and_scatter(name):
     pr = _problem(name)
-    ref = LR.leak(pr, pr.A, _random_x(pr, 3))
+    ref = LR.leak(pr, pr.A, random_x(pr, 3))
     assert LR.counts(pr) == (ref["n_leak_blocks"], ref["n_leak_pairs"])
     assert np.all((ref["leak2"] > 0) == (ref["blocks_per_column"] > 0)[:, None])
     assert np.all(ref["bound"] <= 1e-11 * ref["leak2"])             # the bound is a rounding bound, not a tolerance
@@ -81,7 +73,7 @@ def test_counts_agree_between_sets_and_scatter(name):
 def test_sum_rule_in_numpy(oracle, name):
     """the residual of the padded problem (full columns, X zero-padded) = residual2 + leak2 of the truncated one"""
     pr = _problem(name)
-    X = _random_x(pr, 4)
+    X = random_x(pr, 4)
     twin, Xp = LR.padded(pr, X)
     whole = RR.residual(oracle, twin, twin.A, Xp)["residual2"]
     parts = RR.residual(oracle, pr, pr.A, X)["residual2"] + LR.leak(pr, pr.A, X)["leak2"]
@@ -96,7 +88,7 @@ def test_library_counts_without_a_device(name, one_based):
     pr = _problem(name)
     want = LR.counts(pr)
     if one_based:
-        pr = _offset1(pr)
+        pr = offset1(pr)
         assert LR.counts(pr) == want
     with T.Solver() as s:
         s.create_plan(pr)

@@ -11,22 +11,12 @@ import pytest
 import leak_map_ref as MR
 import leak_ref as LR
 import tfqmrgpu_amd as T
-from test_plan_layout import unordered_pattern
+from helpers import ptr, stencil, unordered_pattern
 from tfqmrgpu_amd import problems as PR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NO_INFO_PASSED, POINTER_INVALID, UNDOCUMENTED = 3, 7, 14
 SENTINEL = -12345.0
-
-
-def _offset1(pr):
-    return T.Problem(pr.rowPtrA + 1, pr.colIndA + 1, pr.A, pr.rowPtrX + 1, pr.colIndX + 1, pr.rowPtrB + 1, pr.colIndB + 1, pr.B, None,
-                     pr.tolerance, 1)
-
-
-def _stencil(LM=4, LN=5, one_based=False):
-    pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=100 * LM + LN, radius=[None, 1.1, 2.3])
-    return _offset1(pr) if one_based else pr
 
 
 def _open(pr, LM=None, LN=None, prec="z"):
@@ -36,15 +26,11 @@ def _open(pr, LM=None, LN=None, prec="z"):
     return s
 
 
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data)
-
-
 # ---- the positions: rows, cols, count ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("one_based", [False, True])
 @pytest.mark.parametrize("LM,LN", [(4, 5), (16, 16)])
 def test_positions_of_the_stencil(LM, LN, one_based):
-    pr = _stencil(LM, LN, one_based)
+    pr = stencil(LM, LN, one_based)
     want = MR.positions(pr)
     assert len(want) == LR.counts(pr)[0] > 0
     with _open(pr) as s:
@@ -87,7 +73,7 @@ def _check_grown(pr, old, take, rowPtrX, colIndX, oldBlock, positions, columns):
 
 @pytest.mark.parametrize("which", ["stencil", "stencil 1-based", "unordered"])
 def test_grown_pattern(which):
-    pr = unordered_pattern() if which == "unordered" else _stencil(one_based=which.endswith("1-based"))
+    pr = unordered_pattern() if which == "unordered" else stencil(one_based=which.endswith("1-based"))
     LM, LN = (4, 4) if which == "unordered" else (pr.LM, pr.LN)
     positions = MR.positions(pr)
     columns = np.unique(pr.colIndX)
@@ -128,7 +114,7 @@ def test_closure_of_repeated_growing():
 
 
 def test_values_move_with_their_blocks():
-    pr = _stencil()
+    pr = stencil()
     pr.X = PR.hashed_uniform(5, (pr.nnzbX, pr.LM, pr.LN)) + 0j
     with _open(pr) as s:
         grown = s.grow_problem(pr)
@@ -151,15 +137,15 @@ def test_symbols_header_and_binding():
 
 
 def test_leak_map_argument_checks_in_order_without_a_device():
-    pr = _stencil()
+    pr = stencil()
     n = len(MR.positions(pr))
     rows, cols = np.full(n, -77, np.int32), np.full(n, -77, np.int32)
     pos2 = np.full((n, pr.LN), SENTINEL)
     nb = C.c_uint64(777)
 
     def raw(handle, plan, capacity=n, with_pos2=True, lists=True, count=True):
-        return T.lib.tfqmrgpuExt_leakMap(handle, plan, capacity, _ptr(rows) if lists else None, _ptr(cols) if lists else None,
-                                         _ptr(pos2) if with_pos2 else None, C.byref(nb) if count else None)
+        return T.lib.tfqmrgpuExt_leakMap(handle, plan, capacity, ptr(rows) if lists else None, ptr(cols) if lists else None,
+                                         ptr(pos2) if with_pos2 else None, C.byref(nb) if count else None)
 
     def untouched(count=True):
         return bool((rows == -77).all() and (cols == -77).all() and (pos2 == SENTINEL).all() and (not count or nb.value == 777))
@@ -200,12 +186,12 @@ def test_leak_map_argument_checks_in_order_without_a_device():
 
 
 def test_grow_pattern_statuses():
-    pr = _stencil()
+    pr = stencil()
     n = len(MR.positions(pr))
 
     def raw(plan, take, g):
         idx = np.asarray(take, dtype=np.uint64)
-        return T.lib.tfqmrgpuExt_growPattern(plan, len(idx), _ptr(idx), C.byref(g) if g is not None else None)
+        return T.lib.tfqmrgpuExt_growPattern(plan, len(idx), ptr(idx), C.byref(g) if g is not None else None)
 
     def zeroed(g):
         return (g.mb, g.nnzbX) == (0, 0) and not g.rowPtrX and not g.colIndX and not g.oldBlock

@@ -5,7 +5,6 @@ changes its size moves it.  Host code only: bufferSize touches no device.
 
 The recorded table was written by this file's main with the library of the commit in front of that change:
     TFQMRGPU_LIB=<that commit's libtfQMRgpu.so> python tests/test_plan_layout.py"""
-import gzip
 import json
 import os
 
@@ -13,6 +12,7 @@ import numpy as np
 
 from conftest import GOLDEN, load_problem   # (first: it puts the repository on sys.path when this file runs as a script)
 import tfqmrgpu_amd as T
+from helpers import first_blocks, index_problem, unordered_pattern
 
 TABLE = os.path.join(GOLDEN, "plan_layout_sizes.json")
 PRECISIONS = "zcm"
@@ -25,35 +25,6 @@ def shapes():
     return [(arr[2 * i], arr[2 * i + 1]) for i in range(15)]
 
 
-def _problem(rpA, ciA, rpX, ciX, rpB, ciB):
-    """index arrays only: the plan never looks at a value"""
-    return T.Problem(rpA, ciA, np.zeros((len(ciA), 1, 1)), rpX, ciX, rpB, ciB, np.zeros((len(ciB), 1, 1)))
-
-
-def _first_blocks(mb, rpX, ciX):
-    """B: the first block of every block column of X, as (rowPtrB, colIndB)"""
-    rows = np.repeat(np.arange(mb), np.diff(rpX))
-    first = np.sort(np.unique(ciX, return_index=True)[1])
-    return np.concatenate([[0], np.cumsum(np.bincount(rows[first], minlength=mb))]), np.asarray(ciX)[first]
-
-
-def unordered_pattern():
-    """An unsorted pattern from the reference's multiplication plan file ("#nnzb_for_Y_A_X= nY nA nX", then iY iA iX beta; despite its
-    name the file lists every iY group in ascending order): A has a block (iY, iX) for every line, the odd block rows in the file's order
-    reversed (columns descending); X has five block columns, column c missing in the rows with (row + c) % 3 == 0, and the blocks of a
-    row start at column row % 5 and wrap around."""
-    with gzip.open(os.path.join(GOLDEN, "plan_unordered.14-287-16.gz"), "rt") as f:
-        mb = int(f.readline().split()[1])
-        lines = np.loadtxt(f, dtype=np.int64)
-    rpA = np.concatenate([[0], np.cumsum(np.bincount(lines[:, 0], minlength=mb))])
-    ciA = np.concatenate([lines[rpA[r]:rpA[r + 1], 2][::-1 if r % 2 else 1] for r in range(mb)])
-    rpX, ciX = [0], []
-    for r in range(mb):
-        ciX += [c for c in ((r + k) % 5 for k in range(5)) if (r + c) % 3]
-        rpX.append(len(ciX))
-    return _problem(rpA, ciA, rpX, ciX, *_first_blocks(mb, np.array(rpX), ciX))
-
-
 def dense_columns_pattern(mb=512, ncols=8):
     """Identical dense block columns, 512 chunks at 8 x 8 `z` (8 blocks each): more than the 384 up to which a plan folds, so that this
     shape keeps its column batches and their launch order (Plan::colBatch, ChunkTable::orderB)"""
@@ -62,7 +33,7 @@ def dense_columns_pattern(mb=512, ncols=8):
         ciA += [c for c in (r - 1, r, r + 1) if 0 <= c < mb]
         rpA.append(len(ciA))
     rpX, ciX = np.arange(mb + 1) * ncols, np.tile(np.arange(ncols), mb)
-    return _problem(rpA, ciA, rpX, ciX, *_first_blocks(mb, rpX, ciX))
+    return index_problem(rpA, ciA, rpX, ciX, *first_blocks(mb, rpX, ciX))
 
 
 def problems():

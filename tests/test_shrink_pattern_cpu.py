@@ -11,7 +11,7 @@ import pytest
 import drop_cost_ref as DR
 import leak_map_ref as MR
 import tfqmrgpu_amd as T
-from test_plan_layout import unordered_pattern
+from helpers import ptr, stencil, unordered_pattern
 from tfqmrgpu_amd import problems as PR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,25 +19,11 @@ NO_INFO_PASSED, POINTER_INVALID, UNDOCUMENTED = 3, 7, 14
 SENTINEL = -12345.0
 
 
-def _offset1(pr):
-    return T.Problem(pr.rowPtrA + 1, pr.colIndA + 1, pr.A, pr.rowPtrX + 1, pr.colIndX + 1, pr.rowPtrB + 1, pr.colIndB + 1, pr.B, None,
-                     pr.tolerance, 1)
-
-
-def _stencil(LM=4, LN=5, one_based=False):
-    pr = PR.stencil_2d(4, 4, LM, LN, ncols=3, seed=100 * LM + LN, radius=[None, 1.1, 2.3])
-    return _offset1(pr) if one_based else pr
-
-
 def _planned(pr):
     """createPlan only: shrinkPattern needs no bufferSize"""
     s = T.Solver()
     s.create_plan(pr)
     return s
-
-
-def _ptr(a):
-    return C.c_void_p(a.ctypes.data)
 
 
 def _droppable(pr):
@@ -48,7 +34,7 @@ def _droppable(pr):
 # ---- the shrunk pattern ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("which", ["stencil", "stencil 1-based", "unordered"])
 def test_shrunk_pattern(which):
-    pr = unordered_pattern() if which == "unordered" else _stencil(one_based=which.endswith("1-based"))
+    pr = unordered_pattern() if which == "unordered" else stencil(one_based=which.endswith("1-based"))
     free = _droppable(pr)
     assert 0 < len(free) < pr.nnzbX
     old = MR.pattern_set(pr, pr.rowPtrX - pr.index_offset)
@@ -74,7 +60,7 @@ def test_shrunk_pattern(which):
 
 
 def test_no_blocks_to_drop_with_a_null_list():
-    pr = _stencil()
+    pr = stencil()
     with _planned(pr) as s:
         g = T.GrownPattern()
         assert T.lib.tfqmrgpuExt_shrinkPattern(s.plan, 0, None, C.byref(g)) == 0
@@ -86,7 +72,7 @@ def test_no_blocks_to_drop_with_a_null_list():
 
 @pytest.mark.parametrize("one_based", [False, True])
 def test_grow_then_shrink_is_the_identity(one_based):
-    pr = _stencil(one_based=one_based)
+    pr = stencil(one_based=one_based)
     with _planned(pr) as s:
         s.buffer_size(pr.LM, pr.LN, "z")                             # growPattern needs it
         take = list(range(0, s.leak_counts()[0], 2))
@@ -101,7 +87,7 @@ def test_grow_then_shrink_is_the_identity(one_based):
 
 
 def test_values_stay_with_their_blocks():
-    pr = _stencil()
+    pr = stencil()
     pr.X = PR.hashed_uniform(5, (pr.nnzbX, pr.LM, pr.LN)) + 0j
     drop = _droppable(pr)[1::2]
     with _planned(pr) as s:
@@ -140,7 +126,7 @@ def test_no_column_of_a_plan_can_empty():
 # ---- the product count --------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("which", ["stencil", "stencil 1-based", "unordered"])
 def test_product_count_without_a_buffer(which):
-    pr = unordered_pattern() if which == "unordered" else _stencil(one_based=which.endswith("1-based"))
+    pr = unordered_pattern() if which == "unordered" else stencil(one_based=which.endswith("1-based"))
     LM, LN = (4, 4) if which == "unordered" else (pr.LM, pr.LN)
     with _planned(pr) as s:
         s.buffer_size(LM, LN, "z")
@@ -163,12 +149,12 @@ def test_symbols_header_and_binding():
 
 
 def test_drop_cost_argument_checks_in_order_without_a_device():
-    pr = _stencil()
+    pr = stencil()
     cost2, weight2 = np.full((pr.nnzbX, pr.LN), SENTINEL), np.full((pr.nnzbX, pr.LN), SENTINEL)
     count = C.c_uint64(777)
 
     def raw(handle, plan, cost=True, weight=True, with_count=True):
-        return T.lib.tfqmrgpuExt_dropCost(handle, plan, _ptr(cost2) if cost else None, _ptr(weight2) if weight else None,
+        return T.lib.tfqmrgpuExt_dropCost(handle, plan, ptr(cost2) if cost else None, ptr(weight2) if weight else None,
                                           C.byref(count) if with_count else None)
 
     def untouched():
@@ -198,14 +184,14 @@ def test_drop_cost_argument_checks_in_order_without_a_device():
 
 
 def test_shrink_pattern_statuses():
-    pr = _stencil(one_based=True)
+    pr = stencil(one_based=True)
     free, carries_b = _droppable(pr), DR.b_blocks(pr)
     n = pr.nnzbX
     assert len(carries_b) == pr.nnzbB == 3
 
     def raw(plan, drop, g, null_list=False):
         idx = np.asarray(drop, dtype=np.int32)
-        return T.lib.tfqmrgpuExt_shrinkPattern(plan, len(idx), None if null_list else _ptr(idx), C.byref(g) if g is not None else None)
+        return T.lib.tfqmrgpuExt_shrinkPattern(plan, len(idx), None if null_list else ptr(idx), C.byref(g) if g is not None else None)
 
     def zeroed(g):
         return (g.mb, g.nnzbX) == (0, 0) and not g.rowPtrX and not g.colIndX and not g.oldBlock

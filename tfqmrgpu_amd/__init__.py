@@ -220,6 +220,16 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
+def _addr(a):
+    """the address of `a` even where it has no entries (_ptr would make that NULL, which means "not asked for"); None stays NULL"""
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _copied(p, n):
+    """a host copy of the n int32 that the library's pointer p shows"""
+    return np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, np.int32)
+
+
 class Problem:
     """A*X==B in BSR form: index arrays plus complex block values (C row-major blocks
     A[nnzbA, LM, LM], B[nnzbB, LM, LN]); the shape the reference's readers produce (bsr.hxx:10-24)."""
@@ -252,6 +262,44 @@ class Solver:
         self.buffer = C.c_void_p(None)
         self._own_buffer = False
         self._keep = []
+
+    @classmethod
+    def open(cls, pr, precision, *, preconditioner=None, keep_operator=False, keep_starts=None, keep_sum=False, allow_padding=False,
+             three_products=False, shadow_mode=None, data_precision=None, buffer=True, stream=None):
+        """a Solver with a plan for `pr`; the calls below stand in the one order the plan's options take.  An option left at its default
+        makes no library call; buffer=False leaves set_buffer to the caller (self.buffer_bytes has the size); a step that raises closes"""
+        s = cls(stream)
+        try:
+            s.create_plan(pr)
+            if allow_padding:
+                s.allow_padding(True)
+            s.buffer_size(pr.LM, pr.LN, precision)
+            if data_precision:
+                s.data_precision = data_precision
+            if three_products:
+                s.set_three_product_multiply(True)
+            if preconditioner is not None:
+                s.set_preconditioner(preconditioner)
+            if keep_operator:
+                s.keep_operator(True)
+            if keep_starts is not None:
+                s.keep_starts(keep_starts)
+            if keep_sum:
+                s.keep_sum(True)
+            if shadow_mode is not None:
+                s.set_shadow_mode(shadow_mode)
+            if buffer:
+                s.set_buffer(nbytes=s.buffer_bytes)
+        except BaseException:
+            s.close()
+            raise
+        return s
+
+    def load(self, A=None, B=None):
+        """set_matrix('A') and set_matrix('B'), from the plan's problem where not given; returns self"""
+        self.set_matrix("A", self.problem.A if A is None else A)
+        self.set_matrix("B", self.problem.B if B is None else B)
+        return self
 
     # -- plan ------------------------------------------------------------------------------------------
     def create_plan(self, pr, echo=0):
@@ -295,6 +343,7 @@ class Solver:
         # precision of the host arrays handed to set_matrix / returned by get_matrix: the plan's, for a mixed-precision plan ('m',
         # which takes both) double unless the caller sets data_precision = "c"
         self.data_precision = "z" if precision in "zm" else "c"
+        self.buffer_bytes = n.value
         return n.value
 
     def set_shadow_mode(self, mode):
@@ -324,13 +373,24 @@ class Solver:
     def _real_dtype(self):
         return np.float64 if self.data_precision == "z" else np.float32
 
-    def set_matrix(self, var, blocks, trans="n", layout=LAYOUT_RIRIRIRI):
-        """blocks: complex array [nnzb, rows, cols] (interleaved layout) or a raw real array for other layouts"""
+    def _values(self, blocks):
+        """the caller's values in data_precision, contiguous: complex stays complex, anything else is taken as raw reals"""
         a = np.asarray(blocks)
         if np.iscomplexobj(a):
-            a = np.ascontiguousarray(a.astype(np.complex128 if self.data_precision == "z" else np.complex64))
-        else:
-            a = np.ascontiguousarray(a, dtype=self._real_dtype())
+            return np.ascontiguousarray(a.astype(np.complex128 if self.data_precision == "z" else np.complex64))
+        return np.ascontiguousarray(a, dtype=self._real_dtype())
+
+    def _blocks_out(self, out, trans, layout, raw):
+        """what get_matrix and get_blocks return from out[n, lm, ln, 2]: complex blocks, reshaped if transposed; raw reals otherwise"""
+        n = out.shape[0]
+        if raw or layout != LAYOUT_RIRIRIRI:
+            return out.reshape(n, -1)
+        c = out[..., 0] + 1j * out[..., 1]
+        return c if trans in "n*" else c.reshape(n, self.ln, self.lm)
+
+    def set_matrix(self, var, blocks, trans="n", layout=LAYOUT_RIRIRIRI):
+        """blocks: complex array [nnzb, rows, cols] (interleaved layout) or a raw real array for other layouts"""
+        a = self._values(blocks)
         self._keep.append(a)
         st = lib.tfqmrgpu_bsrsv_setMatrix(self.handle, self.plan, var.encode(), _ptr(a), self.data_precision.encode(),
                                           self.ln if var in "XBxb" else self.lm, self.lm, trans.encode(), layout)
@@ -354,21 +414,14 @@ class Solver:
         st = lib.tfqmrgpu_bsrsv_getMatrix(self.handle, self.plan, b"X", _ptr(out), self.data_precision.encode(),
                                           self.ln, self.lm, trans.encode(), layout)
         _check(st, "tfqmrgpu_bsrsv_getMatrix")
-        if raw or layout != LAYOUT_RIRIRIRI:
-            return out.reshape(nnzb, -1)
-        c = out[..., 0] + 1j * out[..., 1]
-        return c if trans in "n*" else c.reshape(nnzb, self.ln, self.lm)
+        return self._blocks_out(out, trans, layout, raw)
 
     # -- listed blocks (tfqmrgpu_ext.h section 8) -------------------------------------------------------
     def set_blocks(self, var, blocks, values, trans="n", layout=LAYOUT_RIRIRIRI):
         """set the blocks of operand `var` that `blocks` lists (positions in the caller's block order) from `values`, compact: complex
         [len(blocks), rows, cols] (interleaved layout) or a raw real array for other layouts, as set_matrix; returns the raw status"""
         idx = _i32(blocks)
-        a = np.asarray(values)
-        if np.iscomplexobj(a):
-            a = np.ascontiguousarray(a.astype(np.complex128 if self.data_precision == "z" else np.complex64))
-        else:
-            a = np.ascontiguousarray(a, dtype=self._real_dtype())
+        a = self._values(values)
         st = lib.tfqmrgpuExt_setBlocks(self.handle, self.plan, var.encode(), len(idx), _ptr(idx), _ptr(a), self.data_precision.encode(),
                                        trans.encode(), layout)
         return _check(st, "tfqmrgpuExt_setBlocks('%s')" % var)
@@ -394,10 +447,7 @@ class Solver:
         st = lib.tfqmrgpuExt_getBlocks(self.handle, self.plan, b"X", n, None if idx is None else _ptr(idx), _ptr(out),
                                        self.data_precision.encode(), trans.encode(), layout)
         _check(st, "tfqmrgpuExt_getBlocks")
-        if raw or layout != LAYOUT_RIRIRIRI:
-            return out.reshape(n, -1)
-        c = out[..., 0] + 1j * out[..., 1]
-        return c if trans in "n*" else c.reshape(n, self.ln, self.lm)
+        return self._blocks_out(out, trans, layout, raw)
 
     def get_blocks_device(self, device_ptr, blocks=None, trans="n", layout=LAYOUT_RIRIRIRI):
         idx, n = self._block_list(blocks)
@@ -614,9 +664,7 @@ class Solver:
         rows, cols = np.zeros(n, np.int32), np.zeros(n, np.int32)
         pos2 = np.zeros((n, self.LN), np.float64) if values else None
         nb = C.c_uint64(0)
-        # (an array without entries still has an address: _ptr would make it NULL, which means "not asked for")
-        addr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)      # noqa: E731
-        _check(lib.tfqmrgpuExt_leakMap(self.handle, self.plan, n, addr(rows), addr(cols), addr(pos2), C.byref(nb)), "tfqmrgpuExt_leakMap")
+        _check(lib.tfqmrgpuExt_leakMap(self.handle, self.plan, n, _addr(rows), _addr(cols), _addr(pos2), C.byref(nb)), "tfqmrgpuExt_leakMap")
         return dict(rows=rows, cols=cols, pos2=pos2, n_leak_blocks=int(nb.value))
 
     def grow_pattern(self, take=None):
@@ -630,10 +678,13 @@ class Solver:
             idx = np.ascontiguousarray(take, dtype=np.uint64).reshape(-1)
             st = lib.tfqmrgpuExt_growPattern(self.plan, len(idx), C.c_void_p(idx.ctypes.data), C.byref(g))
         _check(st, "tfqmrgpuExt_growPattern")
+        return self._read_pattern(g)
+
+    @staticmethod
+    def _read_pattern(g):
+        """(rowPtrX, colIndX, oldBlock) as host copies of a GrownPattern that the library filled, which is freed here"""
         try:
-            def arr(p, n):
-                return np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, np.int32)
-            return arr(g.rowPtrX, g.mb + 1), arr(g.colIndX, g.nnzbX), arr(g.oldBlock, g.nnzbX)
+            return _copied(g.rowPtrX, g.mb + 1), _copied(g.colIndX, g.nnzbX), _copied(g.oldBlock, g.nnzbX)
         finally:
             lib.tfqmrgpuExt_freeGrownPattern(C.byref(g))
 
@@ -657,8 +708,7 @@ class Solver:
         cost2 = np.zeros((n, self.LN), np.float64) if cost else None
         weight2 = np.zeros((n, self.LN), np.float64) if weight else None
         count = C.c_uint64(0)
-        addr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)      # noqa: E731
-        _check(lib.tfqmrgpuExt_dropCost(self.handle, self.plan, addr(cost2), addr(weight2), C.byref(count)), "tfqmrgpuExt_dropCost")
+        _check(lib.tfqmrgpuExt_dropCost(self.handle, self.plan, _addr(cost2), _addr(weight2), C.byref(count)), "tfqmrgpuExt_dropCost")
         return dict(cost2=cost2, weight2=weight2, n_products=int(count.value))
 
     def shrink_pattern(self, drop):
@@ -668,12 +718,7 @@ class Solver:
         g = GrownPattern()
         idx = np.ascontiguousarray(drop, dtype=np.int32).reshape(-1)
         _check(lib.tfqmrgpuExt_shrinkPattern(self.plan, len(idx), C.c_void_p(idx.ctypes.data), C.byref(g)), "tfqmrgpuExt_shrinkPattern")
-        try:
-            def arr(p, n):
-                return np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, np.int32)
-            return arr(g.rowPtrX, g.mb + 1), arr(g.colIndX, g.nnzbX), arr(g.oldBlock, g.nnzbX)
-        finally:
-            lib.tfqmrgpuExt_freeGrownPattern(C.byref(g))
+        return self._read_pattern(g)
 
     def shrink_problem(self, pr, drop):
         """the Problem with the shrunk pattern of X (shrink_pattern) and the same A and B as `pr`, the problem of this plan; where `pr`
@@ -751,19 +796,8 @@ def solve_problem(pr, precision="z", threshold=None, max_iterations=2000, transA
     """createPlan .. getMatrix in one go; returns (status, X[nnzbX, LM, LN] complex, info dict).
     preconditioner=PRECOND_BLOCK_JACOBI: info["n_identity"] = block rows whose M_ii is the unit matrix.
     allow_padding=True (tfqmrgpu_ext.h section 18): any block shape up to 64 x 64; info["padded_shape"] = (lm, ln, LM, LN)."""
-    with Solver(stream) as s:
-        s.create_plan(pr)
-        if allow_padding:
-            s.allow_padding(True)
-        nbytes = s.buffer_size(pr.LM, pr.LN, precision)
-        if data_precision:
-            s.data_precision = data_precision
-        if three_products:
-            s.set_three_product_multiply(True)
-        if preconditioner != PRECOND_NONE:
-            s.set_preconditioner(preconditioner)
-        s.set_shadow_mode(shadow_mode)
-        s.set_buffer(nbytes=nbytes)
+    with Solver.open(pr, precision, preconditioner=None if preconditioner == PRECOND_NONE else preconditioner, allow_padding=allow_padding,
+                     three_products=three_products, shadow_mode=shadow_mode, data_precision=data_precision, stream=stream) as s:
         s.set_matrix("A", pr.A, transA)
         s.set_matrix("B", pr.B, "n")
         status = s.solve(pr.tolerance if threshold is None else threshold, max_iterations)
@@ -772,7 +806,7 @@ def solve_problem(pr, precision="z", threshold=None, max_iterations=2000, transA
             info["n_identity"] = s.get_preconditioner(values=False)[1]
         info["bound_history"] = s.bound_history()
         info["refinement_history"] = s.refinement_history()
-        info["buffer_bytes"] = nbytes
+        info["buffer_bytes"] = s.buffer_bytes
         if allow_padding:
             info["padded_shape"] = s.padded_shape()
         X = s.get_matrix()
@@ -787,13 +821,11 @@ def shard_columns(pr, nranks, rank):
                                       _ptr(pr.colIndB), pr.index_offset, nranks, rank, C.byref(sh))
     _check(st, "tfqmrgpuExt_shardColumns")
     try:
-        def arr(p, n):
-            return np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, np.int32)
-        xb, bb = arr(sh.xBlocks, sh.nnzbX), arr(sh.bBlocks, sh.nnzbB)
+        xb, bb = _copied(sh.xBlocks, sh.nnzbX), _copied(sh.bBlocks, sh.nnzbB)
         off = pr.index_offset
         sub = Problem(pr.rowPtrA - off, pr.colIndA - off, pr.A,
-                      arr(sh.rowPtrX, sh.mb + 1), arr(sh.colIndX, sh.nnzbX),
-                      arr(sh.rowPtrB, sh.mb + 1), arr(sh.colIndB, sh.nnzbB), pr.B[bb],
+                      _copied(sh.rowPtrX, sh.mb + 1), _copied(sh.colIndX, sh.nnzbX),
+                      _copied(sh.rowPtrB, sh.mb + 1), _copied(sh.colIndB, sh.nnzbB), pr.B[bb],
                       None if pr.X is None else pr.X[xb], pr.tolerance, 0)
         sub.first_col, sub.n_cols = sh.firstCol, sh.nCols
     finally:
