@@ -96,6 +96,12 @@ def state_deviation(oracle, pr, prec, k, got, v3=None, status=9, failed=None):
     return worst
 
 
+def rounding_factor(n, prec):
+    """sqrt(2) (n + 3) eps: what one element of A x - b, a complex sum of n rounded products and b, moves by in the plan's precision,
+    relative to |A| |x| + |b| (true_residual below has the derivation); n may be an array"""
+    return np.sqrt(2.0) * (n + 3) * EPS[prec]
+
+
 def true_residual(pr, X, prec):
     """(max over right-hand sides of |A x - b| / |b| in float64 from the returned X, the a-priori rounding bound of the GPU's value of it)
     The GPU forms r = A x - b in the plan's precision: per element a complex sum of n = (block products of the row) x LM terms and b, each
@@ -126,5 +132,5 @@ def true_residual(pr, X, prec):
     bn = np.sqrt((np.abs(bd) ** 2).sum(axis=(0, 2)))          # [nc, LN]
     rn = np.sqrt((np.abs(r) ** 2).sum(axis=(0, 2))) / bn
     n = int(np.diff(pr.rowPtrA).max()) * LM
-    bound = np.sqrt(2.0) * (n + 3) * EPS[prec] * np.sqrt((envelope ** 2).sum(axis=(0, 2))) / bn
+    bound = rounding_factor(n, prec) * np.sqrt((envelope ** 2).sum(axis=(0, 2))) / bn
     return float(rn.max()), float(bound.max())
