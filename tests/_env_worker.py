@@ -22,6 +22,9 @@ def problem(name):
         _, nx, ny, lm, ln, nc, seed, points = f[:8]
         radius = [None if r == "-" else float(r) for r in f[8].split(",")] if len(f) > 8 else None
         return PR.stencil_2d(int(nx), int(ny), int(lm), int(ln), int(nc), seed=int(seed), points=int(points), radius=radius)
+    if name.startswith("cfg4:"):       # BASELINE config 4's pattern (bench.py --workload cfg4) at a reduced grid: cfg4:nx:ncols
+        from bench import build_problem
+        return build_problem(name, 0, 1)[0]
     from conftest import load_problem
     return load_problem(name)
 

@@ -152,7 +152,7 @@ def gpu_solve(c, prec, reduce_callback=None, residual=False, max_iterations=None
         s.set_matrix("A", pr.A, "n")
         s.set_matrix("B", pr.B, "n")
         if reduce_callback is not None:
-            assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, reduce_callback, None) == 0
+            s.set_reduce_callback(reduce_callback)
         status = s.solve(THRESHOLD[prec], MAX_ITERATIONS[prec] if max_iterations is None else max_iterations)
         info = s.get_info()
         info["bound_history"] = s.bound_history()

@@ -1,16 +1,17 @@
 """One copy of what the test files share: small helpers around problems, patterns and arrays, the comparison pieces that several files
-use, and the `torch_cuda` fixture, which a test file imports by name.  A plan is opened with tfqmrgpu_amd.Solver.open.
+use, the launcher of the multi-rank worker, and the `torch_cuda` fixture, which a test file imports by name.  A plan is opened with tfqmrgpu_amd.Solver.open.
 Not a conftest, like plan_paths.py: pytest does not rewrite the asserts here, so each one that can fail on a result carries its message."""
 import ctypes as C
 import gzip
 import os
+import subprocess
 
 import numpy as np
 import pytest
 
 import tfqmrgpu_amd as T
 import project_ref as P
-from conftest import GOLDEN, offset1
+from conftest import GOLDEN, ROOT, offset1, torchrun
 from tfqmrgpu_amd import problems as PR
 
 Z_BOUND = {1: 7e-14, 2: 2e-10}     # work vectors after k iterations against the oracle (tests/test_gpu_hash_mode.py: Z_STATE)
@@ -23,6 +24,17 @@ def torch_cuda():
     assert torch.cuda.is_available(), "the gpu tests need a GPU; there is no CPU fallback"
     torch.cuda.set_device(0)
     return torch
+
+
+# ---- several ranks ------------------------------------------------------------------------------------------------------------------------
+def run_ranks(world, scenario, out, *args, timeout):
+    """tests/rank_worker.py <scenario> <out> <args> on `world` ranks (gloo; the scenarios of the product share cuda:0) in a fresh child:
+    what rank 0 wrote to `out`.  A rank that hangs ends the child, and the test, at `timeout` seconds"""
+    env = dict(os.environ, OMP_NUM_THREADS="2" if world < 4 else "1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = torchrun(world) + [os.path.join(ROOT, "tests", "rank_worker.py"), scenario, out] + [str(a) for a in args]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return np.load(out)
 
 
 # ---- arrays ------------------------------------------------------------------------------------------------------------------------------
@@ -125,28 +137,3 @@ def deviations(pr, ref, got, X, starts, prec):
     reach = sum(np.abs(np.asarray(S)) for S in starts)                   # sum |S_i| per element
     bound_x = (tol * gmax)[col][:, None, :] * reach + P.EPS[prec] * np.abs(ref["X"]) + 1e-300
     return dg, tol * gmax + 1e-300, np.abs(X - ref["X"]), bound_x
-
-
-def true_residual(pr, X):
-    """max_rhs |A X - B| / |B| on the pattern of X, dense numpy arithmetic in double (small systems only)"""
-    mb, LM, LN = pr.mb, pr.LM, pr.LN
-    off = pr.index_offset
-    cols = sorted(set((pr.colIndX - off).tolist()))
-    cid = {c: i for i, c in enumerate(cols)}
-    Xd = np.zeros((mb, len(cols), LM, LN), complex)
-    mask = np.zeros((mb, len(cols)), bool)
-    rows = np.repeat(np.arange(mb), np.diff(pr.rowPtrX))
-    for q, (r, c) in enumerate(zip(rows, pr.colIndX - off)):
-        Xd[r, cid[c]] = X[q]; mask[r, cid[c]] = True
-    Bd = np.zeros_like(Xd)
-    rowsB = np.repeat(np.arange(mb), np.diff(pr.rowPtrB))
-    for q, (r, c) in enumerate(zip(rowsB, pr.colIndB - off)):
-        Bd[r, cid[c]] = pr.B[q]
-    Y = np.zeros_like(Xd)
-    rowsA = np.repeat(np.arange(mb), np.diff(pr.rowPtrA))
-    for q, (r, k) in enumerate(zip(rowsA, pr.colIndA - off)):
-        Y[r] += np.einsum("ik,ckj->cij", pr.A[q], Xd[k])
-    R = (Y - Bd) * mask[:, :, None, None]                       # products outside the pattern of X are dropped (SURVEY App. C)
-    r2 = (np.abs(R) ** 2).sum(axis=(0, 2))                      # [cols, LN]
-    b2 = (np.abs(Bd) ** 2).sum(axis=(0, 2))
-    return float(np.sqrt((r2 / b2).max()))

@@ -121,8 +121,7 @@ def test_fold_limit_changes_no_bit_of_a_segmented_column_with_a_broken_rhs(tmp_p
 def test_reduce_callback_slot_changes_no_bit(kind):
     """the several-rank form of the slot (reduce | callback | decide) on one rank, 16 x 16 z"""
     calls = []
-    keep = T.REDUCE_CB(lambda ctx, values, n: calls.append(n))
-    st, X, info = BC.gpu_solve(_case(kind, "16x16"), "z", reduce_callback=keep)
+    st, X, info = BC.gpu_solve(_case(kind, "16x16"), "z", reduce_callback=lambda values, n: calls.append(n))
     st0, X0, info0 = _solve(kind, "16x16", "z")
     assert st == st0 == _case(kind, "16x16").status and info["iterations"] == info0["iterations"]
     assert np.array_equal(info["bound_history"], info0["bound_history"], equal_nan=True) and info["residual"] == info0["residual"]

@@ -3,16 +3,12 @@ shape that is fed the padded problem (tests/pad_ref.py: pad_problem) through the
 then hold the same bytes by construction, the same launches run on them, and every comparison is exact (np.array_equal), not a tolerance.
 Only the last section compares with the truth: the residual of the caller's system and the dense solution of it.
 Needs an MI355X (`pytest -m gpu`)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import pad_ref as PD
 import tfqmrgpu_amd as T
-from conftest import ROOT, torchrun
-from helpers import exact_random_blocks, real_dtype, torch_cuda  # noqa: F401  (torch_cuda: a fixture)
+from helpers import exact_random_blocks, real_dtype, run_ranks, torch_cuda  # noqa: F401  (torch_cuda: a fixture)
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -468,12 +464,7 @@ def test_two_ranks_on_a_padded_plan(tmp_path):
     """block columns sharded over 2 ranks that share cuda:0 (3 processes with this one): every rank pads alike, and the gathered X is
     the X of one rank bit for bit"""
     lm, ln, prec, tol = 9, 9, "z", 1e-9
-    out = str(tmp_path / "sharded.npz")
-    env = dict(os.environ, OMP_NUM_THREADS="2", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = torchrun(2) + [os.path.join(ROOT, "tests", "_gpu_pad_rank_worker.py"), out, str(lm), str(ln), str(100 * lm + ln), prec, repr(tol)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    g = np.load(out)
+    g = run_ranks(2, "solve", str(tmp_path / "sharded.npz"), "stencil:4:3:%d:%d:3:%d:5" % (lm, ln, 100 * lm + ln), prec, tol, "pad", timeout=300)
     pr = _problem(lm, ln)
     with T.Solver() as s:
         s.create_plan(pr)

@@ -375,19 +375,18 @@ def test_reduce_paths_single_rank(torch_cuda):
     st0, X0, info0 = T.solve_problem(pr, "z")
     calls = []
 
-    def cb(ctx, values, n):
+    def cb(values, n):
         calls.append([values[i] for i in range(n)])
     with T.Solver() as s:
         s.create_plan(pr)
         s.set_buffer(nbytes=s.buffer_size(16, 16, "z"))
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        keep = T.REDUCE_CB(cb)
-        assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, keep, None) == 0
+        s.set_reduce_callback(cb)
         assert s.solve(pr.tolerance, 2000) == 0
         assert s.get_info()["iterations"] == info0["iterations"] and np.array_equal(s.get_matrix(), X0)
         assert len(calls) >= 2 * info0["iterations"]
-        assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, C.cast(None, T.REDUCE_CB), None) == 0
+        s.set_reduce_callback(None)
         uid = (C.c_char * 128)()
         assert T.lib.tfqmrgpuExt_commUniqueId(uid) == 0
         assert T.lib.tfqmrgpuExt_commInit(s.handle, 1, 0, uid) == 0
@@ -405,8 +404,7 @@ def test_profile_with_a_reduce_callback(torch_cuda):
         s.set_buffer(nbytes=s.buffer_size(16, 16, "z"))
         s.set_matrix("A", pr.A)
         s.set_matrix("B", pr.B)
-        keep = T.REDUCE_CB(lambda ctx, values, n: None)
-        assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, keep, None) == 0
+        s.set_reduce_callback(lambda values, n: None)
         assert s.solve(pr.tolerance, 2000) == 0
         it, X = s.get_info()["iterations"], s.get_matrix()
         s.set_profiling(1)

@@ -2,15 +2,12 @@
 columns sharded with tfqmrgpuExt_shardColumns, every rank inverts the diagonal blocks of the whole A itself and back-transforms its
 own block columns.  The solution blocks must be bit-identical whatever the number of ranks, the iterations equal, and equal to those
 of a plain single-process solve with the preconditioner.  Run with `pytest -m gpu`."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import tfqmrgpu_amd as T
 from _env_worker import problem
-from conftest import ROOT, torchrun
+from helpers import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -18,14 +15,9 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("name,prec,tol", [("fd_16x16_small", "z", 1e-9), ("fd_16x16_2d", "m", 1e-9)])
 def test_block_jacobi_on_ranks_sharing_one_gpu(tmp_path, name, prec, tol):
     pr = problem(name)
-    env = dict(os.environ, OMP_NUM_THREADS="2", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     runs = {}
     for world in (1, 2, 3):
-        out = str(tmp_path / ("sharded%d.npz" % world))
-        cmd = torchrun(world) + [os.path.join(ROOT, "tests", "_gpu_precond_rank_worker.py"), out, name, prec, repr(tol)]
-        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-        runs[world] = np.load(out)
+        runs[world] = run_ranks(world, "solve", str(tmp_path / ("sharded%d.npz" % world)), name, prec, tol, "jacobi", timeout=600)
     st, X, info = T.solve_problem(pr, prec, threshold=tol, max_iterations=300, preconditioner=T.PRECOND_BLOCK_JACOBI)
     assert st == 0
     for world, g in runs.items():

@@ -3,8 +3,6 @@ and the projected X, the optimality of the projected residual, the edge cases of
 side effects, two ranks, and the energy loop it is for.  The shifts of every fixture are those that tests/test_project_start_cpu.py has
 checked on the CPU: every pivot ratio a factor 100 away from the threshold."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,8 +10,8 @@ import pytest
 import project_ref as P
 import residual_ref as RR
 import tfqmrgpu_amd as T
-from conftest import ROOT, load_problem, torchrun
-from helpers import deviations, same_bits
+from conftest import load_problem
+from helpers import deviations, run_ranks, same_bits
 from precond_ref import _product, diagonal_blocks
 
 pytestmark = pytest.mark.gpu
@@ -277,11 +275,7 @@ def test_two_ranks_give_the_bits_of_one(tmp_path):
         X = s.get_matrix()
     src, out = str(tmp_path / "starts.npz"), str(tmp_path / "sharded.npz")
     np.savez(src, A=P.shifted(pr, P.shifts(pr, name)[-1]), starts=np.array(starts))
-    env = dict(os.environ, OMP_NUM_THREADS="2", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = torchrun(2) + [os.path.join(ROOT, "tests", "_gpu_project_worker.py"), src, out, name, prec]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    g = np.load(out)
+    g = run_ranks(2, "project", out, name, prec, src, timeout=300)
     assert len(g["n_cols"]) == 2 and all(n > 0 for n in g["n_cols"]) and list(g["calls"]) == [0, 0]      # local: no collective
     assert same_bits(g["gamma"], got["coefficients"]) and np.array_equal(g["used"], got["n_used"]) and same_bits(g["X"], X)
 

@@ -3,16 +3,12 @@ tfqmrgpuExt_shardColumns, stopping test max-reduced over ranks through the host 
 must take the iterations of the single-rank run and return bit-identical solution blocks:
 columns are independent systems, the default shadow vector is a hash of (column, row, element), every reduction is
 in a fixed order.  At most 4 processes touch the GPU.  Run with `pytest -m gpu`."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import tfqmrgpu_amd as T
 from _env_worker import problem
-from conftest import ROOT, torchrun
+from helpers import run_ranks
 from plan_paths import FOLD_MAX, plan_paths
 
 pytestmark = pytest.mark.gpu
@@ -26,13 +22,7 @@ pytestmark = pytest.mark.gpu
                                                  # same order either way
                                                  (2, "stencil:20:15:8:64:2:5:5:-,3", "z", 1e-9)])
 def test_ranks_sharing_one_gpu(tmp_path, world, name, prec, tol):
-    out = str(tmp_path / "sharded.npz")
-    env = dict(os.environ, OMP_NUM_THREADS="2", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = torchrun(world) + [
-           os.path.join(ROOT, "tests", "_gpu_rank_worker.py"), out, name, prec, repr(tol)]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    g = np.load(out)
+    g = run_ranks(world, "solve", str(tmp_path / "sharded.npz"), name, prec, tol, timeout=600)
     pr = problem(name)
     if name.startswith("stencil:"):
         ch, seg, folds = plan_paths(pr, prec)
@@ -57,14 +47,9 @@ def test_ranks_sharing_one_gpu(tmp_path, world, name, prec, tol):
 def test_a_failing_rank_stops_every_rank(tmp_path):
     """a rank whose operator fails completes its slot with the failure marked in the reduced record: every rank stops at that
     slot and returns an error, none waits in an all-reduce for ever (the reduction carries {bound, alive, a rank failed})"""
-    out = str(tmp_path / "status.txt")
-    env = dict(os.environ, OMP_NUM_THREADS="2", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = torchrun(2) + [os.path.join(ROOT, "tests", "_gpu_fail_worker.py"), out, "1", "5"]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)    # a hang would end here
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    rows = [tuple(int(v) for v in line.split()) for line in open(out)]
-    assert len(rows) == 2
-    (r0, st0, calls0), (r1, st1, calls1) = sorted(rows)
+    g = run_ranks(2, "fail_operator", str(tmp_path / "status.npz"), "fd_16x16_small", 1, 5, timeout=300)    # a hang would end here
+    assert len(g["status"]) == 2
+    (st0, st1), (calls0, calls1) = g["status"].tolist(), g["operator_calls"].tolist()      # by rank
     assert T.decode(st1)[0] == 14                       # the failing rank returns its operator's status
     assert st0 != 0 and T.decode(st0)[0] == 2           # the other one: stopped by a peer (LAUNCH_FAILED class)
     assert calls1 in (5, 6) and calls0 in (5, 6)        # both stopped in the slot of the failure (2 operator calls per iteration), far from the 300 iterations asked for
@@ -75,14 +60,9 @@ def test_a_refusing_rank_ends_a_mixed_precision_solve_on_every_rank(tmp_path, ho
     """'m' plans: a rank that cannot start -- no work buffer, or a user-defined operator, which mixed-precision plans refuse --
     takes part in the FIRST collective its peers enter, the refinement's max-reduction of 3 doubles, with "a rank failed" set; every rank
     leaves there: same number and sizes of reductions on both ranks, the refusing rank returns its own status (7 | 19), the other one 2."""
-    out = str(tmp_path / "status.txt")
-    env = dict(os.environ, OMP_NUM_THREADS="2", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = torchrun(2) + [os.path.join(ROOT, "tests", "_gpu_mixed_fail_worker.py"), out, "1", how]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)    # a hang would end here
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    rows = sorted(line.split() for line in open(out))
-    assert len(rows) == 2
-    (r0, st0, n0, sz0), (r1, st1, n1, sz1) = rows
-    assert T.decode(int(st1))[0] == (7 if how == "nobuffer" else 19)      # the refusing rank: its own status
-    assert int(st0) != 0 and T.decode(int(st0))[0] == 2                   # its peer: stopped by a rank's failure
-    assert n0 == n1 == "1" and sz0 == sz1 == "3"                          # ONE collective, the same on both: the refinement's {res^2, not finite, a rank failed}
+    g = run_ranks(2, "refuse_mixed", str(tmp_path / "status.npz"), "fd_16x16_small", 1, how, timeout=300)    # a hang would end here
+    assert len(g["status"]) == 2
+    (st0, st1), (n0, n1), (sz0, sz1) = g["status"].tolist(), g["calls"].tolist(), g["sizes"].tolist()      # by rank; sizes: "n,n,..."
+    assert T.decode(st1)[0] == (7 if how == "nobuffer" else 19)           # the refusing rank: its own status
+    assert st0 != 0 and T.decode(st0)[0] == 2                             # its peer: stopped by a rank's failure
+    assert n0 == n1 == 1 and sz0 == sz1 == "3"                            # ONE collective, the same on both: the refinement's {res^2, not finite, a rank failed}

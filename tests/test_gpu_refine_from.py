@@ -1,17 +1,16 @@
 """tfqmrgpuExt_refineFrom (include/tfqmrgpu_ext.h section 16) on the GPU: the mixed-precision refinement started from the X in the plan.
 The oracle has no 'm' mode; as in tests/test_gpu_mixed.py the call is graded against the system itself -- residual() of section 10 (an
-independent double kernel), true_residual (dense numpy, restated from test_gpu_mixed.py) and the oracle's 'z' solution -- and against
+independent double kernel), true_residual (dense numpy, tests/plan_paths.py) and the oracle's 'z' solution -- and against
 the cold solve, solve_from and its own second run where bits are promised.
 get_info()["flops_all"] is the sum over every solve of the plan: where two runs of different length are compared, the fields that
 describe the LAST solve (residual, iterations, flops) are compared bit for bit and flops_all is checked to have grown by flops."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import tfqmrgpu_amd as T
 from conftest import load_problem
-from helpers import bits, diagonal_blocks, same_bits, true_residual
+from helpers import bits, diagonal_blocks, same_bits
+from plan_paths import true_residual
 from tfqmrgpu_amd import problems as PR
 
 pytestmark = pytest.mark.gpu
@@ -58,7 +57,7 @@ def test_continues_on_all_block_sizes(oracle, LM, LN):
         assert worst <= 1.01e-9 and info["residual"] <= 1e-9
         assert h[0] == pytest.approx(w0, rel=1e-9) and h[0] < 1 and h[-1] == info["residual"]
         assert np.abs(X - Xz).max() <= 1e-7 * np.abs(Xz).max()
-        assert abs(true_residual(pr, X) - info["residual"]) <= 1e-3 * info["residual"]
+        assert abs(true_residual(pr, X, "z")[0] - info["residual"]) <= 1e-3 * info["residual"]
         assert info["iterations"] <= cold
         assert info["flops"] > 0
 
@@ -170,7 +169,7 @@ def test_energy_step(precond):
         assert got["worst"] <= 1.01 * thr and info["residual"] <= thr
         assert h[0] == pytest.approx(stale, rel=1e-9)
         patched = T.Problem(pr.rowPtrA, pr.colIndA, shifted, pr.rowPtrX, pr.colIndX, pr.rowPtrB, pr.colIndB, pr.B, None, thr, pr.index_offset)
-        assert true_residual(patched, s.get_matrix()) <= 1.01 * thr
+        assert true_residual(patched, s.get_matrix(), "z")[0] <= 1.01 * thr
 
 
 def test_preconditioned_without_a_kept_copy_is_refused():
@@ -186,7 +185,7 @@ def test_preconditioned_without_a_kept_copy_is_refused():
         assert s.refine_from(1e-9, 300) == 0
         assert s.refinement_history()[0] == pytest.approx(0.5, rel=1e-6)
         X = s.get_matrix()
-    assert true_residual(pr, X) <= 1.01e-9
+    assert true_residual(pr, X, "z")[0] <= 1.01e-9
 
 
 # ---- 5. seeding across precisions and patterns --------------------------------------------------------------------------------------------------
@@ -293,11 +292,10 @@ def test_statuses_change_nothing():
         assert _same_results(_results(s), before)
         # several ranks (a reduce callback): refused through the mixed solve's own first collective, exactly one
         calls = []
-        keep = T.REDUCE_CB(lambda ctx, values, n: calls.append([values[i] for i in range(n)]))
-        assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, keep, None) == 0
+        s.set_reduce_callback(lambda values, n: calls.append([values[i] for i in range(n)]))
         assert T.decode(raw(s))[::2] == (NO_IMPLEMENTATION, 0)
         assert len(calls) == 1 and len(calls[0]) == 3 and calls[0][2] == 1.0
-        assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, C.cast(None, T.REDUCE_CB), None) == 0
+        s.set_reduce_callback(None)
         assert _same_results(_results(s), before)
         # ... and the plan still solves as it did
         assert s.refine_from(1e-8, 300) == 0 and s.get_info()["iterations"] == 0 and same_bits(s.get_matrix(), before[0])

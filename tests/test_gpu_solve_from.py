@@ -270,11 +270,10 @@ def test_statuses_change_nothing():
         s.set_operator(None)
         # several ranks (a reduce callback): refused through the vote in front of a solve, one collective
         calls = []
-        keep = T.REDUCE_CB(lambda ctx, values, n: calls.append([values[i] for i in range(n)]))
-        assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, keep, None) == 0
+        s.set_reduce_callback(lambda values, n: calls.append([values[i] for i in range(n)]))
         assert T.decode(raw(s))[::2] == (NO_IMPLEMENTATION, 0)
         assert len(calls) == 1 and calls[0][1] == 1.0
-        assert T.lib.tfqmrgpuExt_setReduceCallback(s.handle, C.cast(None, T.REDUCE_CB), None) == 0
+        s.set_reduce_callback(None)
         assert same_bits(s.get_matrix(), X0) and np.array_equal(s.bound_history(), h0)
         # no iteration at all: X0 is the answer, bit for bit; the status of a cold solve without an iteration
         for it in (0, -2):

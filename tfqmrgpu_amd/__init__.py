@@ -262,6 +262,7 @@ class Solver:
         self.buffer = C.c_void_p(None)
         self._own_buffer = False
         self._keep = []
+        self._reduce = None
 
     @classmethod
     def open(cls, pr, precision, *, preconditioner=None, keep_operator=False, keep_starts=None, keep_sum=False, allow_padding=False,
@@ -587,6 +588,13 @@ class Solver:
             self._operator = OPERATOR_CB(thunk)     # keep the thunk alive as long as the plan may call it
         _check(lib.tfqmrgpuExt_setOperator(self.plan, self._operator, None), "tfqmrgpuExt_setOperator")
 
+    def set_reduce_callback(self, fn):
+        """several ranks (tfqmrgpu_ext.h section 4): fn(values, n) max-reduces the n doubles behind the ctypes pointer `values` over the
+        ranks, in place; None makes the handle one rank again.  A call on the handle: it needs neither plan nor buffer"""
+        self._reduce = REDUCE_CB(0) if fn is None else REDUCE_CB(lambda ctx, values, n: fn(values, n))
+        # (kept alive as long as the handle may call it, also where the call below raises: the library has taken the pointer by then)
+        _check(lib.tfqmrgpuExt_setReduceCallback(self.handle, self._reduce, None), "tfqmrgpuExt_setReduceCallback")
+
     def get_info(self):
         r, f, fa, it = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int32(0)
         _check(lib.tfqmrgpu_bsrsv_getInfo(self.handle, self.plan, C.byref(r), C.byref(it), C.byref(f), C.byref(fa)),
@@ -765,6 +773,7 @@ class Solver:
         if self.handle:
             lib.tfqmrgpuDestroyHandle(self.handle)
             self.handle = C.c_void_p(None)
+            self._reduce = None
 
     def __enter__(self):
         return self
