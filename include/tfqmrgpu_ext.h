@@ -67,6 +67,12 @@ tfqmrgpuStatus_t tfqmrgpuExt_getProfileFirst(tfqmrgpuBsrsvPlan_t plan, int64_t *
  * by bufferSize / setBuffer), e.g. "k_spmm_ilv16" -- so that kept profiler figures (profiles/pmc_traffic.json) can be told apart from
  * figures of a kernel that no longer runs.  Writes at most `capacity` bytes including the terminating 0. */
 tfqmrgpuStatus_t tfqmrgpuExt_getMultiplyKernel(tfqmrgpuBsrsvPlan_t plan, char *name, int32_t capacity);
+/* *on = 1: a solve of this plan on one rank runs the "late v5" form of the iteration slot -- V5_NRM sums |v5 + alfa v9|^2 without storing v5 and
+ * SPMM_V5_NRM_DOT applies that half step in its epilogue (2 and 5 vectors moved where the other form moves 3 and 4; the same bits).  Plans whose
+ * fused multiplies run on k_spmm_ilv16 with the built-in operator and that do not fold their column operations; 0 for every other plan.  On
+ * several ranks (section 4) no plan folds, so there every such plan takes this form, also one for which this call answers 0 because it folds on
+ * one rank.  Needs the buffer, as getMultiplyKernel does. */
+tfqmrgpuStatus_t tfqmrgpuExt_getLateV5(tfqmrgpuBsrsvPlan_t plan, int32_t *on);
 
 /* ---- (2) shadow vector v3 -------------------------------------------------------------- */
 enum {

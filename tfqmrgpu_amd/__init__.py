@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [  # include/tfqmrgpu.h
 ]
 EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_planView", "tfqmrgpuExt_getBoundHistory", "tfqmrgpuExt_setProfiling", "tfqmrgpuExt_getProfile",
-    "tfqmrgpuExt_getProfileGated", "tfqmrgpuExt_getProfileFirst", "tfqmrgpuExt_getMultiplyKernel",
+    "tfqmrgpuExt_getProfileGated", "tfqmrgpuExt_getProfileFirst", "tfqmrgpuExt_getMultiplyKernel", "tfqmrgpuExt_getLateV5",
     "tfqmrgpuExt_setShadowMode",
     "tfqmrgpuExt_setShadowVector", "tfqmrgpuExt_getShadowVector", "tfqmrgpuExt_getWorkVector", "tfqmrgpuExt_multiply", "tfqmrgpuExt_multiplyPrepare", "tfqmrgpuExt_multiplyOrdered", "tfqmrgpuExt_multiplyRelease", "tfqmrgpuExt_applyOperator", "tfqmrgpuExt_shardColumns",
     "tfqmrgpuExt_freeShard", "tfqmrgpuExt_commUniqueId", "tfqmrgpuExt_commInit",
@@ -131,6 +131,7 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_getProfileGated.argtypes = [P, P, P]
     lib.tfqmrgpuExt_getProfileFirst.argtypes = [P, P, P]
     lib.tfqmrgpuExt_getMultiplyKernel.argtypes = [P, P, C.c_int32]
+    lib.tfqmrgpuExt_getLateV5.argtypes = [P, C.POINTER(C.c_int32)]
     lib.tfqmrgpuExt_setShadowMode.argtypes = [P, I]
     lib.tfqmrgpuExt_setShadowVector.argtypes = [P, P, P]
     lib.tfqmrgpuExt_getShadowVector.argtypes = [P, P, P]
@@ -762,6 +763,12 @@ class Solver:
         buf = C.create_string_buffer(64)
         _check(lib.tfqmrgpuExt_getMultiplyKernel(self.plan, buf, 64), "tfqmrgpuExt_getMultiplyKernel")
         return buf.value.decode()
+
+    def late_v5(self):
+        """whether a one-rank solve of this plan runs the 'late v5' slot: v5_nrm stores nothing, spmm_v5_nrm_dot applies its half step (needs the buffer)"""
+        on = C.c_int32(-1)
+        _check(lib.tfqmrgpuExt_getLateV5(self.plan, C.byref(on)), "tfqmrgpuExt_getLateV5")
+        return bool(on.value)
 
     def close(self):
         if self.plan:

@@ -653,6 +653,14 @@ tfqmrgpuStatus_t tfqmrgpuExt_getMultiplyKernel(tfqmrgpuBsrsvPlan_t plan, char* n
     std::snprintf(name, size_t(capacity), "%s", spmm_kernel_family(d));
     return TFQMRGPU_STATUS_SUCCESS;
 }
+tfqmrgpuStatus_t tfqmrgpuExt_getLateV5(tfqmrgpuBsrsvPlan_t plan, int32_t* on) {
+    auto p = asPlan(plan);
+    if (!p || !on || !p->buffer) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);
+    DevPlan d = resolve(*p);
+    d.fold = folds(*p, false) ? 1 : 0;            // one rank, as tfqmrgpuExt_getMultiplyKernel
+    *on = late_v5(*p, d) ? 1 : 0;
+    return TFQMRGPU_STATUS_SUCCESS;
+}
 tfqmrgpuStatus_t tfqmrgpuExt_setThreeProductMultiply(tfqmrgpuBsrsvPlan_t plan, int on) {
     auto p = asPlan(plan);
     if (!p) return TFQ_ERR(TFQMRGPU_POINTER_INVALID);

@@ -45,6 +45,10 @@ struct DevPlan {
                                                // zero and v5 is B scattered onto zeros by definition there (tfqmrgpu_core.hxx:125,147-153) --
                                                // the kernels take that as given instead of reading it, and the start of a solve writes none of
                                                // them (13 S of traffic per solve)
+    int lateV5;                                // the slot's "late v5" form (tfq_solve.hpp: late_v5; plans on k_spmm_ilv16 that do not fold): k_v5_nrm sums
+                                               // |v5 + alfa v9|^2 and stores nothing, the second fused multiply applies that half step to v5 in front of
+                                               // its own (same alfa, same two fused multiply-adds: the same bits) -- between the two kernels v5 in
+                                               // memory is the OLD v5, and in the first iteration still undefined
     void *x, *v4, *v5, *v6, *v7, *v8, *v9, *B, *A;
     float* v3;
     void *rho, *alfa, *beta, *c67, *eta;       // [nCols][2][LN] real

@@ -173,6 +173,7 @@ struct Slots {
           histScale(histScale_), prof(p_.profiling)
     {
         d.fold = fold ? 1 : 0;
+        d.lateV5 = late_v5(p, d) ? 1 : 0;   // (in front of the copies: dFirst and, folded, the device-resident one of refresh_self see the flag)
         dFirst = d; dFirst.first = 1;
         if (p.opFn) op = op_scratch(p);
         last.state = (maxIt > 0) ? 0 : 3; last.residual2_reached = 1e300; last.iterations_needed = maxIt;

@@ -2,6 +2,7 @@
 // the entry points of the solve that the ABI calls, and the status check of runtime calls that all three use.
 #pragma once
 #include "tfq_device.hpp"
+#include "tfq_vec.hpp"
 
 namespace tfq {
 
@@ -39,6 +40,13 @@ tfqmrgpuStatus_t run_refine_from(Handle& h, Plan& p, double tol, int maxIt, void
 // a reduction over ranks or a foreign multiply sits between the producer and the decision otherwise
 inline bool several_ranks(Handle const& h) { return h.comm != nullptr || h.reduceFn != nullptr; }
 inline bool folds(Plan const& p, bool severalRanks) { return p.foldOk && !severalRanks && !p.opFn; }
+// the "late v5" form of the iteration slot (DevPlan::lateV5): k_v5_nrm stores nothing and the second fused multiply applies its half step.  Built-in
+// operator (the epilogue of a foreign product is k_spmm_direct's), no fold (a folded k_v5_nrm hands its sum to the column operation in its own tail,
+// and the slot of a small system is launch latency, not bytes), fused multiplies on k_spmm_ilv16 (d: the plan as resolved, d.fold as the solve
+// sets it).  One rank or several: a plan that does not fold on one rank takes the same slot on several.  Nothing reads v5 between the two kernels -- decT and k_x_v6_v7 do not, a reduction over ranks moves control records only, the
+// probe, the warm start, the start projection and the refinement's set-up run in front of a solve or behind the second multiply -- and the two gate off
+// together: the control block's state changes only in the decisions behind the second multiply
+inline bool late_v5(Plan const& p, DevPlan const& d) { return !p.opFn && !d.fold && spmm_late_v5(d); }
 
 extern Rccl g_rccl;
 

@@ -146,7 +146,8 @@ static SpmmArgs spmm_args(int epi, DevPlan const& d) {
     a.colBatch = d.colBatch; a.colStart = d.colStart; a.colChunkPtr = d.colChunkPtr;
     switch (epi) {
     case EPI_XPAY_DOT:     a.X = d.v6; a.Y = d.v9; a.e0 = d.v4; a.e1 = d.v8; a.sc = d.beta; a.gate = 1; a.first = d.first; break;
-    case EPI_AXPY_NRM_DOT: a.X = d.v6; a.Y = d.v8; a.e0 = d.v5; a.sc = d.alfa; a.gate = 1; break;
+    case EPI_AXPY_NRM_DOT: a.X = d.v6; a.Y = d.v8; a.e0 = d.v5; a.sc = d.alfa; a.gate = 1;
+                           if (d.lateV5) { a.late = 1; a.e2 = d.v9; a.first = d.first; } break;   // (late_v5 grants the flag to plans on k_spmm_ilv16 alone)
     case EPI_RESIDUAL:     a.X = d.x;  a.Y = nullptr; a.gate = 2; break;
     default: break;
     }
@@ -162,6 +163,13 @@ char const* spmm_kernel_family(DevPlan const& d) {
                                          "k_spmm_ilv8f", "k_spmm_ilv8w", "k_spmm_mfma", "k_spmm_mfma8", "k_spmm_small4", "k_spmm_direct" };
     static_assert(sizeof(names) / sizeof(names[0]) == int(SpmmKernel::direct) + 1, "a name per family");
     return names[int(spmm_select(d.dbl, d.LM, d.LN, EPI_XPAY_DOT, spmm_args(EPI_XPAY_DOT, d)))];
+}
+
+// the multiply's side of the "late v5" slot (tfq_solve.hpp: late_v5): the second fused multiply of this plan runs on k_spmm_ilv16, the one kernel
+// whose epilogue takes the pending half step.  Lab builds: TFQMRGPU_LATE_V5=0 keeps the slot in which k_v5_nrm stores v5
+bool spmm_late_v5(DevPlan const& d) {
+    static int const lateEnv = lab_switch("TFQMRGPU_LATE_V5", 1);
+    return lateEnv && SpmmKernel::ilv16 == spmm_select(d.dbl, d.LM, d.LN, EPI_AXPY_NRM_DOT, spmm_args(EPI_AXPY_NRM_DOT, d));
 }
 
 void spmm_launch(int epi, DevPlan const& d, hipStream_t s) {

@@ -61,6 +61,9 @@ struct SpmmArgs {
     int ilv;                           // element order of the plan's blocks (tfq_device.hpp: ilv_offset); the plain mode is always native
     int aOnce;                         // every A block is used about once per multiply (few block columns): stream A past the caches
     int first;                         // EPI_XPAY_DOT in the first iteration of a solve: old v4 = v8 = 0 by definition, not read (DevPlan::first)
+                                       // (EPI_AXPY_NRM_DOT with `late`: v5 is B under X, or R, there -- nothing has written it yet)
+    void const* e2; int late;          // EPI_AXPY_NRM_DOT of the "late v5" slot (DevPlan::lateV5, k_spmm_ilv16 only): e0 holds the v5 in FRONT of k_v5_nrm's half
+                                       // step, which that kernel has summed but not stored; the epilogue applies it first -- v5 := alfa v8 + (alfa v9 + v5), v9 = e2
     int m3;                            // double shapes above 16 x 16: three real products per complex one (tfqmrgpuExt_setThreeProductMultiply)
     DevPlan const* foldPlan;           // not null: the column operation that consumes this launch's records runs in its tail (tfq_colops.hpp)
     uint8_t const* colBatch; uint32_t const* colStart; uint32_t const* colChunkPtr;   // k_spmm_ilv8b: (batch size << 4) | position per block column; block / chunk ranges of the columns
@@ -84,6 +87,7 @@ template <typename R> __device__ inline void epi_xpay2(R& nr, R& ni, R yr, R yi,
     nr = fma_(-si, ti, fma_(sr, tr, yr)); ni = fma_(sr, ti, fma_(si, tr, yi));
 }
 // v5 := s v8 + v5   (u = old v5, y = v8 = A v6; tfqmrgpu_core.hxx:224-228)
+// (the "late v5" slot, SpmmArgs::late: the same form twice with the same s, first with y = v9 -- k_v5_nrm's half step, tfqmrgpu_core.hxx:205 -- then with y = v8)
 template <typename R> __device__ inline void epi_axpy(R& nr, R& ni, R yr, R yi, R ur, R ui, R sr, R si) {
     nr = fma_(-si, yi, fma_(sr, yr, ur)); ni = fma_(sr, yi, fma_(si, yr, ui));
 }

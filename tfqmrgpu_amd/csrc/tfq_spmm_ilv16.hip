@@ -22,8 +22,13 @@ __device__ inline int ilv_rowp(int a) { return 2 * ((a & 3) + 4 * (a >> 3)) + ((
 // once per multiply -- the kernel is a stream of A through HBM, and 16-byte non-temporal loads take it from 5.5 to 6.6 TB/s
 // (one block column, 1.3 GB of A: plain multiply 0.69 -> 0.82 of 8 TB/s, fused 0.76 -> 0.85, profiles/r02_lab.txt); with
 // many columns A is re-used out of the caches and must stay there (the plan decides: SpmmArgs::aOnce).
-template <int EPI, bool HASH, bool ANT = false, bool FIRST = false>   // FIRST: the launch of the first iteration of a solve (SpmmArgs::first)
+// LATE (EPI_AXPY_NRM_DOT, SpmmArgs::late): the v5 this launch finds is the one in FRONT of k_v5_nrm's half step, which that kernel has summed but not
+// stored.  The epilogue requests the v9 piece of its Y block with its other operands and forms v5 + alfa v9 first -- the two fused multiply-adds of
+// k_v5_nrm on the same operands, the same bits -- then its own step, and stores v5 once: a store of S leaves a kernel that is bound by HBM and enters one
+// that is not.  With FIRST the old v5 is the right-hand side (the B block under the Y block, or zeros; DevPlan::R: block y of R), as ld_rhs reads it
+template <int EPI, bool HASH, bool ANT = false, bool FIRST = false, bool LATE = false>   // FIRST: the launch of the first iteration of a solve (SpmmArgs::first)
 __global__ __launch_bounds__(256, 2) void k_spmm_ilv16(SpmmArgs a) {
+    static_assert(!LATE || EPI == EPI_AXPY_NRM_DOT, "the pending half step belongs to the v5 update");
     if (gate_closed(a)) return;
     using R = double;
     constexpr int LN = 16, P = 256, NPL = EpiPlanes<EPI>::N;
@@ -84,11 +89,21 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16(SpmmArgs a) {
         int const eb[2] = { (lr * 16 + lc) * 2, ((lr + 4) * 16 + lc) * 2 };
         size_t const yoff = size_t(y) * 2 * P;
         d2v ur[2], ui[2], vr[2], vi[2]; f2v wr[2], wi[2];
+        d2v pr[2], pi[2];                   // LATE: the v9 piece
+        uint32_t bu = 0xffffffffu;          // LATE && FIRST: the block of the right-hand side that is the old v5 of this Y block (none: zeros)
+        if constexpr (LATE && FIRST) bu = a.bOfX ? a.bOfX[y] : y;
         if constexpr (UPD) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {   // old v4 | v5, v8, v3: touched once, non-temporal
+            for (int h = 0; h < 2; ++h) {   // old v4 | v5, v8, v3 [, v9]: touched once, non-temporal
+                if constexpr (LATE) { pr[h] = ld_stream<true>((d2v const*)((R const*)a.e2 + yoff + eb[h])); pi[h] = ld_stream<true>((d2v const*)((R const*)a.e2 + yoff + eb[h] + P)); }
                 if constexpr (EPI == EPI_XPAY_DOT && FIRST) { ur[h] = d2v{0, 0}; ui[h] = d2v{0, 0}; vr[h] = d2v{0, 0}; vi[h] = d2v{0, 0}; }   // first iteration: old v4 = v8 = 0, not read
-                else {
+                else if constexpr (LATE && FIRST) {   // first iteration: v5 = B scattered onto zeros, not yet in memory
+                    ur[h] = d2v{0, 0}; ui[h] = d2v{0, 0};
+                    if (bu != 0xffffffffu) {
+                        R const* b = (R const*)a.B + size_t(bu) * 2 * P;
+                        ur[h] = ld_stream<true>((d2v const*)(b + eb[h])); ui[h] = ld_stream<true>((d2v const*)(b + eb[h] + P));
+                    }
+                } else {
                 ur[h] = ld_stream<true>((d2v const*)((R const*)a.e0 + yoff + eb[h])); ui[h] = ld_stream<true>((d2v const*)((R const*)a.e0 + yoff + eb[h] + P));
                 if constexpr (EPI == EPI_XPAY_DOT) { vr[h] = ld_stream<true>((d2v const*)((R const*)a.e1 + yoff + eb[h])); vi[h] = ld_stream<true>((d2v const*)((R const*)a.e1 + yoff + eb[h] + P)); }
                 }
@@ -134,8 +149,13 @@ __global__ __launch_bounds__(256, 2) void k_spmm_ilv16(SpmmArgs a) {
                     nr[e] = __builtin_fma(-si, ti, __builtin_fma(sr, tr, yr[e]));
                     ni[e] = __builtin_fma(sr, ti, __builtin_fma(si, tr, yi[e]));
                 } else if constexpr (EPI == EPI_AXPY_NRM_DOT) { // v8 := A v6; v5 := alfa v8 + v5 (tfqmrgpu_core.hxx:224-228)
-                    nr[e] = __builtin_fma(-si, yi[e], __builtin_fma(sr, yr[e], ur[h][e]));
-                    ni[e] = __builtin_fma(sr, yi[e], __builtin_fma(si, yr[e], ui[h][e]));
+                    R tr = ur[h][e], ti = ui[h][e];
+                    if constexpr (LATE) {                       // v5 := alfa v9 + v5 first, as k_v5_nrm has summed it (tfqmrgpu_core.hxx:205; tfq_vec.hip: axpy)
+                        tr = __builtin_fma(-si, pi[h][e], __builtin_fma(sr, pr[h][e], ur[h][e]));
+                        ti = __builtin_fma(sr, pi[h][e], __builtin_fma(si, pr[h][e], ui[h][e]));
+                    }
+                    nr[e] = __builtin_fma(-si, yi[e], __builtin_fma(sr, yr[e], tr));
+                    ni[e] = __builtin_fma(sr, yi[e], __builtin_fma(si, yr[e], ti));
                 }
                 if constexpr (UPD) {
                     double w0, w1;      // the logical elements (rows 2 (lr + 4 h) + e, column lc) are one quad of the shadow vector's hash
@@ -498,9 +518,12 @@ template <typename R, int LM, int LN, int EPI> struct Ilv16Family {
         // (the first-iteration launch of EPI_XPAY_DOT is its own instance: a test of the flag per Y block costs the steady launches 0.5 %)
         constexpr bool canFirst = (EPI == EPI_XPAY_DOT);
         constexpr bool canHash = (EPI == EPI_XPAY_DOT || EPI == EPI_AXPY_NRM_DOT);
+        // (late v5: only this kernel has the form, spmm_late_v5 in tfq_spmm.hip grants the flag to no other; its first iteration is an instance too)
+        constexpr bool canLate = (EPI == EPI_AXPY_NRM_DOT);
         if constexpr (takes_ilv16(dbl, LM, LN)) if (SpmmKernel::ilv16 == k) {
-            variant<canHash>(a.hashV3, [&](auto H) { variant<true>(a.aOnce, [&](auto ANT) { variant<canFirst>(a.first, [&](auto F) {
-                k_spmm_ilv16<EPI, H, ANT, F><<<dim3(nWG), dim3(256), 0, s>>>(a); }); }); });
+            variant<canHash>(a.hashV3, [&](auto H) { variant<true>(a.aOnce, [&](auto ANT) { variant<canLate>(a.late, [&](auto L) {
+                variant<canFirst || decltype(L)::value>(a.first, [&](auto F) {
+                    k_spmm_ilv16<EPI, decltype(H)::value, decltype(ANT)::value, decltype(F)::value, decltype(L)::value><<<dim3(nWG), dim3(256), 0, s>>>(a); }); }); }); });
             return;
         }
         if constexpr (takes_ilv16f(dbl, LM, LN)) if (SpmmKernel::ilv16f == k) {

@@ -137,7 +137,8 @@ __device__ inline void ld_b_under_x(R (&r)[VEC], R (&i)[VEC], DevPlan const& d, 
     }
 }
 // At the start of a solve v5 is B scattered onto zeros (tfqmrgpu_core.hxx:153): the kernels of the first iteration that read it
-// take the B block under an X block, or zeros, directly -- v5 itself is first WRITTEN by k_v5_nrm of that iteration.
+// take the B block under an X block, or zeros, directly -- v5 itself is first WRITTEN by k_v5_nrm of that iteration, or, in the "late v5"
+// slot (DevPlan::lateV5), by the second fused multiply of that iteration, which reads the right-hand side the same way.
 template <typename R, int VEC>
 __device__ inline void ld_rhs(R (&r)[VEC], R (&i)[VEC], DevPlan const& d, uint32_t xblock, size_t inner, int P) {
     if (d.R) {   // the right-hand side of this solve is a whole X-shaped vector (mixed-precision refinement)

@@ -101,10 +101,13 @@ __global__ __launch_bounds__(256) void k_xpay_v6(DevPlan d) {
     if (d.first) sweep(std::true_type{}); else sweep(std::false_type{});
 }
 
-// ---- KC: v5 := alfa v9 + v5 ; pd <- |v5|^2 ---------------------------------------------------------
+// ---- KC: v5 := alfa v9 + v5 ; pd <- |v5|^2   (DevPlan::lateV5: pd <- |alfa v9 + v5|^2 alone) --------
 // (the v7 update that the reference does here, tfqmrgpu_core.hxx:207, needs v6 and v7 again in KD and
 // is done there: same arithmetic, one read of v6 and one read+write of v7 less)
-template <typename R, int LM, int LN>
+// LATE (DevPlan::lateV5; 16 x 16 z only): the sum alone, nothing is stored -- the second fused multiply forms the same v5 + alfa v9 again from the same
+// operands (tfq_spmm_ilv16.hip: LATE) and stores the v5 behind ITS half step: one write and one read of S less, and this pass is read-only.
+// An instance of its own, chosen in vec_run: the storing kernel keeps its code
+template <typename R, int LM, int LN, bool LATE = false>
 __global__ __launch_bounds__(256) void k_v5_nrm(DevPlan d) {
     using G = Geo<R, LM, LN>;
     __shared__ double s[256 * G::VEC];
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(256) void k_v5_nrm(DevPlan d) {
                 TFQ_ITEM_OFFSETS(G)
                 R ar[G::VEC], ai[G::VEC], br[G::VEC], bi[G::VEC];
                 ldv(ar, v9 + re); ldv(ai, v9 + im);
-                if constexpr (decltype(firstTag)::value) ld_rhs<R, G::VEC>(br, bi, d, first + blk, size_t(w - blk * G::IPB) * G::VEC, G::P);   // v5 = B on zeros: first written here
+                if constexpr (decltype(firstTag)::value) ld_rhs<R, G::VEC>(br, bi, d, first + blk, size_t(w - blk * G::IPB) * G::VEC, G::P);   // v5 = B on zeros: first written here (LATE: by the multiply)
                 else { ldv(br, v5 + re); ldv(bi, v5 + im); }
 #pragma unroll
                 for (int v = 0; v < G::VEC; ++v) {
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(256) void k_v5_nrm(DevPlan d) {
                     double const r = br[v], i = bi[v];
                     acc[0][v] = __builtin_fma(i, i, __builtin_fma(r, r, acc[0][v]));
                 }
-                stv(v5 + re, br); stv(v5 + im, bi);
+                if constexpr (!LATE) { stv(v5 + re, br); stv(v5 + im, bi); }
             }
         };
         if (d.first) sweep(std::true_type{}); else sweep(std::false_type{});
@@ -475,7 +478,10 @@ static hipError_t vec_run(int op, DevPlan const& d, double tol, int maxIt, hipSt
     case VEC_DEC35:    k_dec35<R, LN><<<cols, blk, 0, s>>>(d); break;
     case VEC_XPAY_V6:  k_xpay_v6<R, LM, LN><<<grid, blk, 0, s>>>(d); break;
     case VEC_DEC34:    k_dec34<R, LN><<<cols, blk, 0, s>>>(d); break;
-    case VEC_V5_NRM:   k_v5_nrm<R, LM, LN><<<grid, blk, 0, s>>>(d); break;
+    case VEC_V5_NRM:
+        if constexpr (std::is_same<R, double>::value && 16 == LM && 16 == LN) if (d.lateV5) { k_v5_nrm<R, LM, LN, true><<<grid, blk, 0, s>>>(d); break; }
+        if (d.lateV5) return hipErrorInvalidValue;   // (late_v5 grants the flag to plans on k_spmm_ilv16 alone: no instance for another shape)
+        k_v5_nrm<R, LM, LN><<<grid, blk, 0, s>>>(d); break;
     case VEC_DECT_C67: k_decT<R, LN, true, false><<<cols, blk, 0, s>>>(d); break;
     case VEC_X_V6_V7:  k_x_v6_v7<R, LM, LN><<<grid, blk, 0, s>>>(d); break;
     case VEC_DECT_FIN: k_decT<R, LN, false, true><<<cols, blk, 0, s>>>(d); break;

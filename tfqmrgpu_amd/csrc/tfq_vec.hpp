@@ -11,7 +11,7 @@ enum {
     VEC_DEC35,         // beta, rho from pz
     VEC_XPAY_V6,       // v6 := v5 + beta v6
     VEC_DEC34,         // alfa, c67 from pz
-    VEC_V5_NRM,        // v5 += alfa v9 ; pd <- |v5|^2
+    VEC_V5_NRM,        // v5 += alfa v9 ; pd <- |v5|^2   (DevPlan::lateV5: the sum alone, the second fused multiply stores v5)
     VEC_DECT_C67,      // tau, var, eta, c67 from pd
     VEC_X_V6_V7,       // [x += eta2 v7] ; v7 := v6 + c67a v7 ; x += eta v7 ; v6 += alfa v4 ; v7 := v6 + c67 v7
     VEC_DECT_FIN,      // tau, var, eta from pd + per-column stopping record
@@ -26,6 +26,8 @@ void spmm_launch(int epi, DevPlan const& d, hipStream_t s);
 
 // the kernel family spmm_launch runs for this plan (tfqmrgpuExt_getMultiplyKernel)
 char const* spmm_kernel_family(DevPlan const& d);
+// whether the second fused multiply of this plan runs on the kernel that can take k_v5_nrm's half step (one condition of tfq_solve.hpp: late_v5)
+bool spmm_late_v5(DevPlan const& d);
 
 // Y = A*X on two X-shaped vectors of the plan, no epilogue (tfqmrgpuExt_applyOperator)
 void spmm_apply(DevPlan const& d, void const* X, void* Y, hipStream_t s);
