@@ -916,6 +916,77 @@ tfqmrgpuStatus_t tfqmrgpuExt_solveMesh(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPla
     int32_t *iterations, double *residual, tfqmrgpuStatus_t *status /* HOST [nE] each, may be NULL */,
     int32_t *nDone       /* may be NULL */);
 
+/* ---- (20) selection on the device: the blocks to drop and the leak positions to take ------------------------------------------------ */
+/* The loop of sections 10 to 15 -- residual, truncationLeak, leakMap, growPattern, dropCost, shrinkPattern, createPlan, carry,
+ * solveFrom -- moves whole record arrays to the host in two places, for a rule of one line that the caller then applies: cost2
+ * [nnzbX][LN] of section 13 to find the blocks to drop, pos2 [nLeakBlocks][LN] of section 12 to find the positions to take.  The operands
+ * of both rules are on the device already.  selectDrop and selectLeak apply them there, and only the chosen indices (and one [LN] sum per
+ * block column) cross to the host.
+ *
+ * selectDrop.  Block n of X, at block row k and compressed block column c, is selected when
+ *   (1) it carries no block of B (tfqmrgpuPlanView_t::subset) -- shrinkPattern refuses such a block --, and
+ *   (2) cost2[n*LN + j] <= (eta*eta) * bnorm2[c*LN + j]  for EVERY j < LN.
+ * blocks[0 .. *nSelected) = the selected blocks in the caller's block order of X, ascending, a HOST array [capacity], may be NULL: the
+ *                           `drop` argument of shrinkPattern as it stands;
+ * spent[c*LN + j]         = the sum over the selected blocks n of block column c of sqrt(cost2[n*LN + j]), a HOST array [nCols][LN] of
+ *                           double, may be NULL: the triangle-inequality bound of section 13 on what dropping the whole set adds to
+ *                           the residual norm of that right-hand side.  A caller checks a budget with it and bisects eta.
+ *
+ * selectLeak.  Position p of the leak map (section 12: ascending compressed block column, then block row), in block column c, is
+ * selected when there is a j < LN with  bnorm2[c*LN + j] > 0  and  pos2[p*LN + j] > (eta*eta) * bnorm2[c*LN + j].
+ * take[0 .. *nSelected) = the selected positions, ascending, a HOST array [capacity], may be NULL: the `take` argument of growPattern as
+ *                         it stands;
+ * left[c*LN + j]        = the sum of pos2[p*LN + j] over the positions of block column c that were NOT selected, a HOST array
+ *                         [nCols][LN] of double, may be NULL: the leak that stays.
+ *
+ * Both.  *nSelected = the number selected, may be NULL.  All three outputs NULL: TFQMRGPU_STATUS_NO_INFO_PASSED.
+ * The rules are part of the interface: applied in numpy to what dropCost, leakMap and residual return at that moment, they give the
+ *   same index lists, entry for entry.  cost2 is bit for bit dropCost's, pos2 leakMap's, bnorm2 residual's -- the same kernels write
+ *   them into the same library-owned memory; eta*eta is rounded once in double (on the host), its product with bnorm2 once (on the
+ *   device); nothing is contracted into a fused multiply-add.  A comparison that involves a NaN is false: a block with a NaN in its
+ *   record is not dropped, a NaN never makes a position taken.
+ * Padded right-hand sides (section 18) have bnorm2 = 0 and cost2 = pos2 = 0: they pass the <= of selectDrop and never meet the > of
+ *   selectLeak.  No special case.
+ * Operands and arithmetic are those of sections 10, 12 and 13: the caller's A -- the buffer's, or the kept copy (section 9) while the
+ *   buffer holds A M^-1 --; X what getMatrix('X') would return at that moment; every product and sum in double on 'z', 'c' and 'm'.
+ * Deterministic.  The list ascends by construction: one flag per block (position), then an ordered compaction in three plain passes --
+ *   the flags set per tile of 256 items, one work group that turns the tile counts into prefix sums, one work group per tile that writes
+ *   its indices behind its prefix.  No work group waits for another.  spent and left: one work group per block column; lane t has
+ *   right-hand side t % LN and is number r = t / LN of the R = floor(256 / LN) lanes of that right-hand side; it adds the column's
+ *   entries r, r + R, r + 2 R, ... in that order -- the column's blocks in the plan's internal order, sorted by block row, for spent;
+ *   its leak positions, sorted by block row, for left --, and the R partial sums are added in ascending r.  No atomics: two calls on
+ *   the same data give the same bits.  The values are those of that order, not of a host sum; compare them within
+ *   (entries of the column) * 2^-52 * (the sum of the magnitudes).
+ * Non-destructive: nothing in the caller's buffer is written.  Work vectors, bound history, and a solve, residual, dropCost or leakMap
+ *   that follows are bit for bit what they would have been.  bufferSize and the buffer layout do not change.
+ * Memory: the records are those of sections 10, 12 and 13, in their memory.  The flags, the tile counts, the index list, the per-column
+ *   sums and three index lists of the plan (selectDrop: the block column of every block, the blocks of every column; selectLeak: the
+ *   block column of every position, the first position of every column) are device memory that the library owns, allocated and
+ *   uploaded by the first call of each kind, released by destroyPlan and by bufferSize.  A plan that never makes the call allocates
+ *   nothing and launches nothing new.
+ * Stream: asynchronous on the handle's stream up to ONE synchronise for the copy-out (one more in a first call that uploads a listing).
+ *   What is copied: the count, min(capacity, items) 32-bit indices if the index array is given, [nCols][LN] doubles if the sums are.
+ *   With only nSelected given the call counts and copies out eight bytes or fewer.  Do not call it during a solve.
+ * All checks but one come before the first device call, in the order of sections 12 and 13: plan / handle pointers:
+ *   TFQMRGPU_POINTER_INVALID; no bufferSize yet: TFQMRGPU_UNDOCUMENTED_ERROR; all three outputs NULL: TFQMRGPU_STATUS_NO_INFO_PASSED;
+ *   eta < 0 or a NaN: TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'E'; no buffer: TFQMRGPU_POINTER_INVALID; a plan with a
+ *   user-defined operator: TFQMRGPU_NO_IMPLEMENTATION; A never set whole on this buffer: TFQMRGPU_UNDOCUMENTED_ERROR with the key
+ *   character 'A'; the A in the buffer has been scaled by the preconditioner and the plan keeps no copy: TFQMRGPU_NO_IMPLEMENTATION.
+ *   The exception needs the count, so it comes behind the kernels: the index array given and capacity < the number selected:
+ *   TFQMRGPU_UNDOCUMENTED_ERROR with the key character 'X'; *nSelected (if given) HAS been filled in -- the room to come back with --
+ *   and nothing else.  After any other error nothing has been written, neither the host arrays nor *nSelected.
+ * Several ranks (section 4): local to the rank's plan, no collective. */
+tfqmrgpuStatus_t tfqmrgpuExt_selectDrop(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double eta, uint64_t capacity,
+    int32_t  *blocks,             /* HOST [capacity], may be NULL: the selected X blocks, caller's order, ascending */
+    uint64_t *nSelected,          /* may be NULL */
+    double   *spent);             /* HOST [nCols][LN], may be NULL */
+tfqmrgpuStatus_t tfqmrgpuExt_selectLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan,
+    double eta, uint64_t capacity,
+    uint64_t *take,               /* HOST [capacity], may be NULL: the selected leak-map positions, ascending */
+    uint64_t *nSelected,          /* may be NULL */
+    double   *left);              /* HOST [nCols][LN], may be NULL */
+
 #ifdef __cplusplus
 }
 #endif

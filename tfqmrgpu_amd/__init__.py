@@ -48,6 +48,7 @@ EXT_SYMBOLS = [  # include/tfqmrgpu_ext.h
     "tfqmrgpuExt_allowPadding", "tfqmrgpuExt_paddedShape",
     "tfqmrgpuExt_shiftDiagonal", "tfqmrgpuExt_keepSum", "tfqmrgpuExt_addToSum", "tfqmrgpuExt_getSum", "tfqmrgpuExt_clearSum",
     "tfqmrgpuExt_solveMesh",
+    "tfqmrgpuExt_selectDrop", "tfqmrgpuExt_selectLeak",
 ]
 FORTRAN_SYMBOLS = [  # tfqmrgpu_amd/csrc/tfq_fortran.c
     "tfqmrgpuprinterror_", "tfqmrgpucreatehandle_", "tfqmrgpudestroyhandle_", "tfqmrgpusetstream_",
@@ -184,6 +185,8 @@ def load_library(path=LIB_PATH):
     lib.tfqmrgpuExt_getSum.argtypes = [P, P, P, C.POINTER(C.c_int32)]
     lib.tfqmrgpuExt_clearSum.argtypes = [P, P]
     lib.tfqmrgpuExt_solveMesh.argtypes = [P, P, C.c_int32, P, P, C.c_double, I, I, P, P, P, C.POINTER(C.c_int32)]
+    lib.tfqmrgpuExt_selectDrop.argtypes = [P, P, C.c_double, C.c_uint64, P, C.POINTER(C.c_uint64), P]
+    lib.tfqmrgpuExt_selectLeak.argtypes = [P, P, C.c_double, C.c_uint64, P, C.POINTER(C.c_uint64), P]
     return lib
 
 
@@ -735,6 +738,32 @@ class Solver:
         rowPtrX, colIndX, old = self.shrink_pattern(drop)
         X = None if pr.X is None else pr.X[old]
         return Problem(pr.rowPtrA, pr.colIndA, pr.A, rowPtrX, colIndX, pr.rowPtrB, pr.colIndB, pr.B, X, pr.tolerance, pr.index_offset)
+
+    # -- selection on the device (tfqmrgpu_ext.h section 20) --------------------------------------------------
+    def _select(self, fn, where, eta, index_dtype, sums):
+        """the two calls of a selection: one for the count, one with exactly that room"""
+        count = C.c_uint64(0)
+        _check(fn(self.handle, self.plan, float(eta), 0, None, C.byref(count), None), where)
+        idx = np.zeros(int(count.value), index_dtype)
+        out = np.zeros((int(self.plan_view()["nCols"]), self.LN), np.float64) if sums else None
+        _check(fn(self.handle, self.plan, float(eta), len(idx), _addr(idx), C.byref(count), _addr(out)), where)
+        return idx, out
+
+    def select_drop(self, eta, spent=True):
+        """tfqmrgpu_ext.h section 20: the blocks of X (the caller's order, ascending, int32) that carry no block of B and whose
+        cost2 <= eta^2 bnorm2 for every right-hand side, decided on the device from the records of drop_cost() and residual() -- what
+        shrink_pattern and shrink_problem take as `drop`.  Returns a dict: blocks, and spent [nCols, LN] float64, the sum of sqrt(cost2)
+        over the selected blocks of each block column (None with spent=False)"""
+        blocks, out = self._select(lib.tfqmrgpuExt_selectDrop, "tfqmrgpuExt_selectDrop", eta, np.int32, spent)
+        return dict(blocks=blocks, spent=out)
+
+    def select_leak(self, eta, left=True):
+        """tfqmrgpu_ext.h section 20: the leak positions (the order of leak_map(), ascending, uint64) with pos2 > eta^2 bnorm2 for some
+        right-hand side with bnorm2 > 0, decided on the device from the records of leak_map() and residual() -- what grow_pattern and
+        grow_problem take as `take`.  Returns a dict: take, and left [nCols, LN] float64, the sum of pos2 over the positions of each
+        block column that were NOT selected (None with left=False)"""
+        take, out = self._select(lib.tfqmrgpuExt_selectLeak, "tfqmrgpuExt_selectLeak", eta, np.uint64, left)
+        return dict(take=take, left=out)
 
     def bound_history(self):
         n = lib.tfqmrgpuExt_getBoundHistory(self.plan, None, 0)

@@ -1,9 +1,12 @@
 // The calls that grade the caller's system on the device (tfqmrgpu_ext.h sections 10 to 13): the per-right-hand-side residual, the
-// truncation leak, the leak map with the grown pattern, the drop cost with the shrunk pattern.  Host code only: the kernels are reached
-// through the launchers of tfq_vec.hpp (tfq_residual.hip, tfq_leak.hip, tfq_leak_map.hip, tfq_drop_cost.hip), the listings are built by
+// truncation leak, the leak map with the grown pattern, the drop cost with the shrunk pattern; and the two that decide on those grades
+// there (section 20): selectDrop and selectLeak.  Host code only: the kernels are reached through the launchers of tfq_vec.hpp
+// (tfq_residual.hip, tfq_leak.hip, tfq_leak_map.hip, tfq_drop_cost.hip) and tfq_select.hpp (tfq_select.hip), the listings are built by
 // tfq_leak_host.cpp.  Every call has the same three steps, each written once here: its checks in front of the first device call, in the
 // documented order; its lists and records in ONE library-owned piece of device memory (dev_listing); its results through a host vector
-// (Result, fetch), so that a failed copy leaves the caller's arrays untouched.
+// (Result, fetch), so that a failed copy leaves the caller's arrays untouched.  The step in the middle of sections 10, 12 and 13 -- the
+// records on the device -- is a function of its own (residual_records, leak_map_records, drop_records): the public call is that step and
+// its copy-out, a call of section 20 is that step and its own kernels.
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
@@ -13,6 +16,7 @@
 #include "tfq_solve.hpp"
 #include "tfq_precond.hpp"
 #include "tfq_vec.hpp"
+#include "tfq_select.hpp"
 
 using namespace tfq;
 
@@ -100,6 +104,105 @@ tfqmrgpuStatus_t leak_device(Plan& p, size_t (&at)[kLeakPieces], hipStream_t s) 
     return dev_listing(p.layout.leakDev, piece, at, s);
 }
 
+// ---- the records on the device: what sections 10, 12 and 13 do between their checks and their copy-out
+// section 10: col = [nCols][2][LN], |B - A X|^2 and |B|^2 of every block column
+tfqmrgpuStatus_t residual_records(Plan& p, hipStream_t s, double const*& col) {
+    DevPlan const d = resolve_callers(p);                           // 'm': the double copies of X, B and A
+    size_t const nRec = size_t(d.nChunks) * 2 * p.LN, nCol = size_t(p.nCols) * 2 * p.LN;
+    if (auto const st = p.layout.residualScratch.reserve(std::max<size_t>((nRec + nCol) * sizeof(double), 256))) return st;
+    double* const rec = p.layout.residualScratch.as<double>();
+    residual_launch(d, callers_a(p, d), rec, rec + nRec, s);
+    col = rec + nRec;
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// section 12: rec = [nPos][LN]; behind leak_host, for nPos > 0
+tfqmrgpuStatus_t leak_map_records(Plan& p, hipStream_t s, double const*& rec) {
+    size_t const nPos = p.layout.leak.nPositions();
+    size_t at[kLeakPieces];
+    if (auto const st = leak_device(p, at, s)) return st;           // the listing of section 11, uploaded once for both calls
+    if (auto const st = p.layout.leakMapRec.reserve(std::max<size_t>(nPos * size_t(p.LN) * sizeof(double), 256))) return st;
+    char* const dev = p.layout.leakDev.as<char>();
+    DevPlan const d = resolve_callers(p);                           // 'm': the double copies of X and A
+    leak_map_launch(d, callers_a(p, d), uint32_t(nPos), (uint32_t const*)(dev + at[kLeakPairs]), (uint32_t const*)(dev + at[kLeakPos]), p.layout.leakMapRec.as<double>(), s);
+    rec = p.layout.leakMapRec.as<double>();
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// section 13: cost, weight = [nnzbX][LN] each, in the caller's block order; only what is asked for is computed
+tfqmrgpuStatus_t drop_records(Plan& p, bool const wantCost, bool const wantWeight, hipStream_t s, double const*& cost, double const*& weight) {
+    try {
+        if (!p.drop.built) drop_listing(p.drop, p.nnzbX, p.nPairs(), p.pairs.data(), p.u2i.data());
+    } catch (std::bad_alloc const&) { p.drop = DropListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    auto const& l = p.drop;
+    size_t const n = size_t(p.nnzbX) * size_t(p.LN);
+    // the listing on the device, Plan::layout.dropDev
+    enum { kStart, kAOf, kXOf, kCost, kWeight, kPieces };
+    Piece const piece[kPieces] = {{l.start.data(), l.start.size() * 4}, {l.aOf.data(), l.aOf.size() * 4}, {l.xOf.data(), l.xOf.size() * 4},
+                                  {nullptr, n * sizeof(double)}, {nullptr, n * sizeof(double)}};
+    size_t at[kPieces];
+    if (auto const st = dev_listing(p.layout.dropDev, piece, at, s)) return st;
+    char* const dev = p.layout.dropDev.as<char>();
+    cost = (double const*)(dev + at[kCost]); weight = (double const*)(dev + at[kWeight]);
+    DevPlan const d = resolve_callers(p);                           // 'm': the double copies of X and A
+    // the kernel writes the record of a block at the caller's index of that block: the copy-out is a plain copy
+    drop_cost_launch(d, wantCost ? callers_a(p, d) : nullptr, p.nnzbX, (uint32_t const*)(dev + at[kStart]), (uint32_t const*)(dev + at[kAOf]),
+                     (uint32_t const*)(dev + at[kXOf]), wantCost ? (double*)(dev + at[kCost]) : nullptr, wantWeight ? (double*)(dev + at[kWeight]) : nullptr, s);
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// ---- section 20: flags, ordered list and per-column sums from records that are on the device -------------------------------------------
+// what a call copies out, through host memory of its own (sized in front of the first device call)
+struct Selection {
+    std::vector<uint32_t> list; uint32_t total = 0; Result sums;
+};
+// `mem`: the call's device memory, its pieces in this order (the host lists in front, `nLists` of them; then flags | tile counts |
+// list | sums).  rec [nItems][LN], bnorm2 as select_flag_launch reads it; start [nCols + 1] and order (or nullptr) as select_sum_launch does
+struct SelectPieces { uint32_t const *colOf, *start, *order; uint8_t* flag; uint32_t *tiles, *list; double* sums; };
+tfqmrgpuStatus_t select_run(Plan const& p, SelectPieces const& m, uint32_t nItems, double const* rec, double const* col, double eta,
+    bool leak, Selection& out, hipStream_t s)
+{
+    uint32_t const nTiles = select_tiles(nItems);
+    // bnorm2 of column c: the second [LN] of its pair of records
+    select_flag_launch(nItems, p.LN, rec, col + p.LN, uint32_t(2 * p.LN), m.colOf, eta * eta, leak, m.flag, m.tiles, s);
+    select_compact_launch(nItems, m.flag, m.tiles, m.list, s);
+    if (!out.sums.host.empty()) select_sum_launch(p.nCols, p.LN, rec, m.flag, m.start, m.order, !leak, !leak, m.sums, s);
+    TFQ_HIP(hipGetLastError(), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    if (nItems) TFQ_HIP(hipMemcpyAsync(&out.total, m.tiles + nTiles, sizeof(uint32_t), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    // as many entries as the caller has room for: whether that is all of them is known behind the synchronise
+    if (!out.list.empty()) TFQ_HIP(hipMemcpyAsync(out.list.data(), m.list, out.list.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    if (!out.sums.host.empty()) TFQ_HIP(hipMemcpyAsync(out.sums.host.data(), m.sums, out.sums.host.size() * sizeof(double), hipMemcpyDeviceToHost, s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    TFQ_HIP(hipStreamSynchronize(s), TFQMRGPU_STATUS_LAUNCH_FAILED)
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
+// the checks of both calls, in the documented order
+tfqmrgpuStatus_t select_checks(Plan const* p, Handle const* h, double eta, bool const anyOutput) {
+    if (auto const st = prologue(p, h, anyOutput)) return st;
+    if (!(eta >= 0)) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'E');    // negative, or a NaN
+    return operands_ready(*p, true);
+}
+// the host memory of the copy-out: room for as many indices as the caller has, at most all items
+bool select_host(Plan const& p, Selection& out, bool wantList, uint64_t capacity, size_t nItems, bool wantSums) {
+    try {
+        if (wantList) out.list.resize(size_t(std::min<uint64_t>(capacity, nItems)));
+    } catch (std::bad_alloc const&) { return false; }
+    return out.sums.size(wantSums ? size_t(p.nCols) * size_t(p.LN) : 0);
+}
+
+// behind the synchronise: the count first -- with too little room it is all the caller gets --, then the arrays
+template <typename Index>
+tfqmrgpuStatus_t select_deliver(Selection const& out, uint64_t capacity, Index* index, uint64_t* nSelected, double* sums) {
+    if (index && capacity < uint64_t(out.total)) {
+        if (nSelected) *nSelected = uint64_t(out.total);
+        return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'X');
+    }
+    if (index) for (uint32_t n = 0; n < out.total; ++n) index[n] = Index(out.list[n]);
+    if (sums) std::copy(out.sums.host.begin(), out.sums.host.end(), sums);
+    if (nSelected) *nSelected = uint64_t(out.total);
+    return TFQMRGPU_STATUS_SUCCESS;
+}
+
 // a pattern of sections 12 and 13 into malloc'ed arrays for the caller (tfqmrgpuExt_freeGrownPattern releases them)
 tfqmrgpuStatus_t export_pattern(Plan const& p, GrownPattern const& g, tfqmrgpuGrownPattern_t* to) {
     auto dup = [](std::vector<int32_t> const& v) {
@@ -130,14 +233,11 @@ tfqmrgpuStatus_t tfqmrgpuExt_residual(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
     if (auto const st = operands_ready(*p, true)) return st;
 
     hipStream_t const s = (hipStream_t)h->stream;
-    DevPlan const d = resolve_callers(*p);                          // 'm': the double copies of X, B and A
-    size_t const nRec = size_t(d.nChunks) * 2 * p->LN, nCol = size_t(p->nCols) * 2 * p->LN;
     Result col;
-    if (!col.size(nCol)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
-    if (auto const st = p->layout.residualScratch.reserve(std::max<size_t>((nRec + nCol) * sizeof(double), 256))) return st;
-    double* const rec = p->layout.residualScratch.as<double>();
-    col.dev = rec + nRec;
-    residual_launch(d, callers_a(*p, d), rec, rec + nRec, s);
+    if (!col.size(size_t(p->nCols) * 2 * p->LN)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
+    double const* dev = nullptr;
+    if (auto const st = residual_records(*p, s, dev)) return st;
+    col.dev = dev;
     if (auto const st = fetch(s, col)) return st;
 
     size_t const LN = size_t(p->LN);
@@ -204,13 +304,9 @@ tfqmrgpuStatus_t tfqmrgpuExt_leakMap(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_
         hipStream_t const s = (hipStream_t)h->stream;
         Result rec; rec.to = pos2;
         if (!rec.size(nPos * LN)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
-        size_t at[kLeakPieces];
-        if (auto const st = leak_device(*p, at, s)) return st;      // the listing of section 11, uploaded once for both calls
-        if (auto const st = p->layout.leakMapRec.reserve(std::max<size_t>(nPos * LN * sizeof(double), 256))) return st;
-        char* const dev = p->layout.leakDev.as<char>();
-        rec.dev = p->layout.leakMapRec.ptr;
-        DevPlan const d = resolve_callers(*p);                      // 'm': the double copies of X and A
-        leak_map_launch(d, callers_a(*p, d), uint32_t(nPos), (uint32_t const*)(dev + at[kLeakPairs]), (uint32_t const*)(dev + at[kLeakPos]), p->layout.leakMapRec.as<double>(), s);
+        double const* dev = nullptr;
+        if (auto const st = leak_map_records(*p, s, dev)) return st;
+        rec.dev = dev;
         if (auto const st = fetch(s, rec)) return st;
     }
     if (rows) for (size_t n = 0; n < nPos; ++n) rows[n] = int32_t(l.posRow[n]);
@@ -251,24 +347,11 @@ tfqmrgpuStatus_t tfqmrgpuExt_dropCost(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan
 
     size_t const n = size_t(p->nnzbX) * size_t(p->LN);
     Result cost, weight; cost.to = cost2; weight.to = weight2;
-    try {
-        if (!cost.size(cost2 ? n : 0) || !weight.size(weight2 ? n : 0)) throw std::bad_alloc();
-        if (!p->drop.built) drop_listing(p->drop, p->nnzbX, p->nPairs(), p->pairs.data(), p->u2i.data());
-    } catch (std::bad_alloc const&) { p->drop = DropListing{}; return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    if (!cost.size(cost2 ? n : 0) || !weight.size(weight2 ? n : 0)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
     hipStream_t const s = (hipStream_t)h->stream;
-    auto const& l = p->drop;
-    // the listing on the device, Plan::layout.dropDev
-    enum { kStart, kAOf, kXOf, kCost, kWeight, kPieces };
-    Piece const piece[kPieces] = {{l.start.data(), l.start.size() * 4}, {l.aOf.data(), l.aOf.size() * 4}, {l.xOf.data(), l.xOf.size() * 4},
-                                  {nullptr, n * sizeof(double)}, {nullptr, n * sizeof(double)}};
-    size_t at[kPieces];
-    if (auto const st = dev_listing(p->layout.dropDev, piece, at, s)) return st;
-    char* const dev = p->layout.dropDev.as<char>();
-    cost.dev = dev + at[kCost]; weight.dev = dev + at[kWeight];
-    DevPlan const d = resolve_callers(*p);                          // 'm': the double copies of X and A
-    // the kernel writes the record of a block at the caller's index of that block: the copy-out is a plain copy
-    drop_cost_launch(d, cost2 ? callers_a(*p, d) : nullptr, p->nnzbX, (uint32_t const*)(dev + at[kStart]), (uint32_t const*)(dev + at[kAOf]),
-                     (uint32_t const*)(dev + at[kXOf]), cost2 ? (double*)(dev + at[kCost]) : nullptr, weight2 ? (double*)(dev + at[kWeight]) : nullptr, s);
+    double const *costDev = nullptr, *weightDev = nullptr;
+    if (auto const st = drop_records(*p, nullptr != cost2, nullptr != weight2, s, costDev, weightDev)) return st;
+    cost.dev = costDev; weight.dev = weightDev;
     if (auto const st = fetch(s, cost, &weight)) return st;
     if (nProducts) *nProducts = uint64_t(p->nPairs());
     return TFQMRGPU_STATUS_SUCCESS;
@@ -289,6 +372,74 @@ tfqmrgpuStatus_t tfqmrgpuExt_shrinkPattern(tfqmrgpuBsrsvPlan_t plan, uint64_t nD
         if (bad) return err(TFQMRGPU_UNDOCUMENTED_ERROR, __LINE__ % 10000, 'B');        // the block carries a block of B
     } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
     return export_pattern(*p, g, shrunk);
+}
+
+// ---- selection on the device: the blocks to drop, the leak positions to take (tfqmrgpu_ext.h section 20) ---------------------------------
+tfqmrgpuStatus_t tfqmrgpuExt_selectDrop(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double eta, uint64_t capacity,
+    int32_t* blocks, uint64_t* nSelected, double* spent)
+{
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (auto const st = select_checks(p, h, eta, blocks || nSelected || spent)) return st;
+    hipStream_t const s = (hipStream_t)h->stream;
+    uint32_t const nX = p->nnzbX, nTiles = select_tiles(nX);
+    Selection out;
+    if (!select_host(*p, out, nullptr != blocks, capacity, nX, nullptr != spent)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
+    // the lists: the column of every block in the caller's order, none for a block that carries B | the blocks of every column in the
+    // internal order, which is sorted by (column, row), and the caller's index of each
+    enum { kColOf, kStart, kOrder, kFlag, kTiles, kList, kSums, kPieces };
+    std::vector<uint32_t> colOf;
+    if (!p->layout.selectDrop) {
+        try {
+            colOf = p->col32;
+            for (auto const x : p->subset) colOf[x] = kSelExcluded;
+        } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    }
+    Piece const piece[kPieces] = {{colOf.data(), size_t(nX) * 4}, {p->colStart.data(), p->colStart.size() * 4}, {p->i2u.data(), size_t(nX) * 4},
+        {nullptr, nX}, {nullptr, (size_t(nTiles) + 1) * 4}, {nullptr, size_t(nX) * 4}, {nullptr, size_t(p->nCols) * size_t(p->LN) * sizeof(double)}};
+    size_t at[kPieces];
+    if (auto const st = dev_listing(p->layout.selectDrop, piece, at, s)) return st;
+    char* const dev = p->layout.selectDrop.as<char>();
+    SelectPieces const m{(uint32_t const*)(dev + at[kColOf]), (uint32_t const*)(dev + at[kStart]), (uint32_t const*)(dev + at[kOrder]),
+                         (uint8_t*)(dev + at[kFlag]), (uint32_t*)(dev + at[kTiles]), (uint32_t*)(dev + at[kList]), (double*)(dev + at[kSums])};
+    double const *cost = nullptr, *weight = nullptr, *col = nullptr;
+    if (auto const st = drop_records(*p, true, false, s, cost, weight)) return st;      // cost2 as dropCost returns it
+    if (auto const st = residual_records(*p, s, col)) return st;                        // bnorm2 as residual returns it
+    if (auto const st = select_run(*p, m, nX, cost, col, eta, false, out, s)) return st;
+    return select_deliver(out, capacity, blocks, nSelected, spent);
+}
+
+tfqmrgpuStatus_t tfqmrgpuExt_selectLeak(tfqmrgpuHandle_t handle, tfqmrgpuBsrsvPlan_t plan, double eta, uint64_t capacity,
+    uint64_t* take, uint64_t* nSelected, double* left)
+{
+    auto p = asPlan(plan); auto h = (Handle*)handle;
+    if (auto const st = select_checks(p, h, eta, take || nSelected || left)) return st;
+    if (auto const st = leak_host(*p)) return st;
+    auto const& l = p->layout.leak;
+    uint32_t const nPos = uint32_t(l.nPositions()), nTiles = select_tiles(nPos);
+    hipStream_t const s = (hipStream_t)h->stream;
+    Selection out;
+    if (!select_host(*p, out, nullptr != take, capacity, nPos, nullptr != left)) return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED);
+    enum { kColOf, kStart, kFlag, kTiles, kList, kSums, kPieces };
+    std::vector<uint32_t> start;                                    // the first position of every column: they are sorted by column
+    try {
+        if (!p->layout.selectLeak) {
+            start.assign(size_t(p->nCols) + 1, 0u);
+            for (auto const c : l.posCol) ++start[c + 1];
+            for (uint32_t c = 0; c < p->nCols; ++c) start[c + 1] += start[c];
+        }
+    } catch (std::bad_alloc const&) { return TFQ_ERR(TFQMRGPU_STATUS_ALLOCATION_FAILED); }
+    Piece const piece[kPieces] = {{l.posCol.data(), size_t(nPos) * 4}, {start.data(), (size_t(p->nCols) + 1) * 4},
+        {nullptr, nPos}, {nullptr, (size_t(nTiles) + 1) * 4}, {nullptr, size_t(nPos) * 4}, {nullptr, size_t(p->nCols) * size_t(p->LN) * sizeof(double)}};
+    size_t at[kPieces];
+    if (auto const st = dev_listing(p->layout.selectLeak, piece, at, s)) return st;
+    char* const dev = p->layout.selectLeak.as<char>();
+    SelectPieces const m{(uint32_t const*)(dev + at[kColOf]), (uint32_t const*)(dev + at[kStart]), nullptr,
+                         (uint8_t*)(dev + at[kFlag]), (uint32_t*)(dev + at[kTiles]), (uint32_t*)(dev + at[kList]), (double*)(dev + at[kSums])};
+    double const *pos = nullptr, *col = nullptr;
+    if (nPos) if (auto const st = leak_map_records(*p, s, pos)) return st;              // pos2 as leakMap returns it
+    if (auto const st = residual_records(*p, s, col)) return st;
+    if (auto const st = select_run(*p, m, nPos, pos, col, eta, true, out, s)) return st;
+    return select_deliver(out, capacity, take, nSelected, left);
 }
 
 // how the listing is cut: work units per compressed block column

@@ -296,6 +296,10 @@ struct Plan {
         DevMem leakDev;
         DevMem leakMapRec;             // tfqmrgpuExt_leakMap (section 12): one [LN] record of doubles per leak position; the listing on the device is leakDev's
         DevMem dropDev;                // tfqmrgpuExt_dropCost (section 13): Plan::drop on the device [start | aOf | xOf | cost records [nnzbX][LN] | weight records [nnzbX][LN]]
+        // tfqmrgpuExt_selectDrop / selectLeak (section 20), each allocated and its lists uploaded by the first call of its kind:
+        // [colOf (kSelExcluded: carries B) | colStart | i2u | flags [nnzbX] | tile counts | selected blocks | spent [nCols][LN]] and
+        // [posCol | first position of each column | flags [nPos] | tile counts | selected positions | left [nCols][LN]]
+        DevMem selectDrop, selectLeak;
         DevMem precond;                // block-Jacobi: [M^-1 | diagOfRow | colOfA | counter | flags], allocated at the first preconditioned solve
     } layout;
 

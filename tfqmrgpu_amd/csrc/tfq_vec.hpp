@@ -1,5 +1,5 @@
 // internal launch interface of the vector / column kernels (tfq_vec.hip), the multiply (tfq_spmm.hip, tfq_spmm.hpp), the grading kernels
-// (tfq_residual.hip, tfq_leak.hip, tfq_leak_map.hip, tfq_drop_cost.hip; device helpers tfq_grade.hpp, host side tfq_grade_host.cpp) and the warm start
+// (tfq_residual.hip, tfq_leak.hip, tfq_leak_map.hip, tfq_drop_cost.hip, tfq_select.hip; device helpers tfq_grade.hpp, host side tfq_grade_host.cpp) and the warm start
 // (tfq_warm.hip).  Device pieces that the chunk-streaming kernels share: tfq_stream.hpp; column operations and the set-up of a solve: tfq_colops.hpp
 #pragma once
 #include "tfq_device.hpp"
